@@ -4,7 +4,7 @@
 A "step" is one epoch of buildModel(): one pass of the fused gather-dot-AXPY update over every training
 tuple, through the C ABI (libcarskit_mi355x.so), with tuples and model already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|northstar|c5|small]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|northstar|c5|small] [--dump-outputs DIR]
 
 N>1 is launched by the driver through torch.distributed.run (one rank per GPU): tuples are sharded by
 user (each rank owns its own users and their ratings: weak scaling, per-GPU work fixed), the item-side
@@ -226,6 +226,37 @@ def timed_epochs(inst, lr, steps, warmup):
     return losses, time.perf_counter() - t0, float(np.mean(ms))
 
 
+DUMP_BUDGET = 64 << 20      # --dump-outputs: bytes written in all
+DUMP_SEED = 12345           # the row sample of an output too large for its share of the budget
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET):
+    """--dump-outputs DIR: write what the timed path handed its caller after the last step, one DIR/<name>.npy per array (float32 or
+    float64, as returned).  Smallest first, each array gets an equal share of what is left of the budget; one that does not fit is cut
+    to a fixed, seeded sample of its rows (the same rows for the same shape), written with the row ids as DIR/<name>_rows.npy."""
+    if not path:
+        return
+    os.makedirs(path, exist_ok=True)
+    arrays = {n: np.atleast_1d(np.asarray(a)) for n, a in arrays.items()}
+    for n, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            arrays[n] = a.astype(np.float64)
+    todo = sorted(arrays, key=lambda n: (arrays[n].nbytes, n))
+    left = budget - 2 * 256 * len(todo)          # room for the .npy headers
+    for i, name in enumerate(todo):
+        a = arrays[name]
+        share = left // (len(todo) - i)
+        if a.nbytes > share:
+            n_rows = max(1, share // (a.nbytes // a.shape[0] + 8))      # the rows and their float64 ids
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[0], n_rows, replace=False))
+            a = np.ascontiguousarray(a[rows])
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.size * 8
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+    log("dumped %d output(s) to %s" % (len(todo), path))
+
+
 def secondary_workload(name, steps, warmup, device, flags, regs, lr, calibrate=True):
     """Another workload of WORKLOADS in the same run (the `northstar` object of the N=1 line): generated, scheduled, uploaded and
     timed exactly like the primary one, with its own roofline."""
@@ -288,6 +319,9 @@ def bench_fm(args):
             g.sweep()
         g.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
+        if flags == 0 and args.dump_outputs:          # the default form's model after the last sweep
+            w0, w, V = g.get_model()
+            dump_outputs(args.dump_outputs, {"w0": np.float64(w0), "w": w, "V": V})
         # the dominant kernel: the launch of a factor's user / item phase (65 + 65 of the ~390 launches of a sweep, 85 % of its time), timed
         # with HIP events on the instance's stream (in its non-updating form: it only writes scratch)
         ku, ki = g.time_reduce(4 + 3 * (k // 2) + 0, 10) * 1e-3, g.time_reduce(4 + 3 * (k // 2) + 1, 10) * 1e-3
@@ -412,6 +446,12 @@ def bench_frappe(args):
 
     run(max(1, args.warmup))
     el = run(args.steps)
+    if args.dump_outputs:           # every fold's last loss and model
+        outs = {}
+        for f_, (i, _, _, _) in enumerate(folds):
+            outs["fold%d_loss" % f_] = np.float64(i.last_loss())
+            outs.update({"fold%d_%s" % (f_, n): a for n, a in i.get_states(dtype=np.float32).items()})
+        dump_outputs(args.dump_outputs, outs)
     one_ms = float(np.mean([i.last_epoch_ms() for i, _, _, _ in folds]))
     total = sum(tr.n for _, tr, _, _ in folds)
     # one instance alone (no neighbours): what a fold costs when the GPU has nothing else to do
@@ -488,6 +528,8 @@ def bench_group(args):
     elapsed = time.perf_counter() - t0
     if not np.all(np.isfinite(losses)) or (len(losses) > 1 and losses[-1] > losses[0]):
         raise SystemExit("bench: training diverged (epoch losses %s)" % losses)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(loss=np.float64(losses[-1]), **g.get_states(dtype=np.float32)))
     comp, exch = np.asarray(comp, dtype=np.float64), np.asarray(exch, dtype=np.float64)     # [steps, W] HIP-event ms
     shards, bytes_epoch = [], 0.0
     for s in range(W):
@@ -582,6 +624,8 @@ def bench_rank(args):
     dev = float(np.mean(ms)) * 1e-3
     wall = float(np.mean(walls))
     nq = res["n_queries"]
+    if args.dump_outputs:           # the measures of the last evaluation
+        dump_outputs(args.dump_outputs, {m: np.float64(v) for m, v in res.items()})
     # the two kernels ON THEIR OWN: in the timed evaluations the selection of batch b runs beside the contraction of batch b + 1 (two
     # streams), so their HIP-event times overlap and stretch each other; the roofline prices the contraction alone (one stream)
     overlapped = dict(kern)
@@ -666,6 +710,9 @@ def main():
     ap.add_argument("--folds", type=int, default=1,
                     help="independent recommender instances per GPU trained concurrently (the reference's `cv -p on`: "
                          "one thread per fold), each on its own stream; value then aggregates all of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32/64, "
+                         "at most 64 MB in all: a fixed, seeded row sample of larger outputs), to compare two builds output for output")
     args = ap.parse_args()
 
     if args.workload in ("c4", "rank", "frappe", "depaul"):
@@ -820,6 +867,16 @@ def main():
     # a diverging run is not a measurement: the loss must be finite and must not have grown over the run (one rate, no bold driver)
     if not np.all(np.isfinite(losses)) or (len(losses) > 1 and losses[-1] > losses[0]):
         raise SystemExit("bench: training diverged (epoch losses %s) -- throughput of a diverging run is not reported" % losses)
+    if args.dump_outputs:
+        # the last step's loss and the model(s) it left behind; with several ranks each writes its own shard under rank<r>_
+        sdt = np.float64 if es == 8 else np.float32
+        outs = {"loss": np.float64(losses[-1])}
+        for f, o in enumerate([inst] + extra):
+            outs.update({("fold%d_" % f if extra else "") + n: a for n, a in o.get_states(dtype=sdt).items()})
+        if world > 1:
+            outs = {"rank%d_%s" % (rank, n): a for n, a in outs.items()}
+        dump_outputs(args.dump_outputs, outs, DUMP_BUDGET // world)
+        del outs
     if dist is not None:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -953,7 +1010,7 @@ def main():
             if not args.no_extras:
                 import copy
                 small = copy.copy(args)
-                small.steps, small.warmup, small.no_cpu_baseline = 3, 1, True
+                small.steps, small.warmup, small.no_cpu_baseline, small.dump_outputs = 3, 1, True, None
                 rk = copy.copy(small)
                 rk.steps, rk.warmup = 8, 2      # an evaluation is 15 ms of which a third is host work: more of them, so that one disturbed call weighs less
                 for key, fn in (("c5", lambda: secondary_workload("c5", 3, 1, local_rank, args.flags, regs, lr, not args.no_calibration)),

@@ -155,18 +155,13 @@ def test_driver_rejects_unaccelerated_recommenders(tmp_path):
         main.run(conf, engine_factory=util.OracleEngine, log=lambda *a: None)
 
 
-FRAPPE_ZIP = "/root/reference/context-aware_data_sets/Mobile_Frappe.zip"
-
-
-@pytest.mark.skipif(not os.path.exists(FRAPPE_ZIP), reason="the Frappe data may not be redistributed; only where the reference is mounted")
 def test_frappe_loads_through_transformer_and_dao(tmp_path):
-    """BASELINE config C2's data path on the real file (tab-separated -> comma CSV first, as CARSKit requires)."""
-    import zipfile
+    """BASELINE config C2's data path on the real file (tests/golden/frappe_compact.csv.gz: the tab-separated log already
+    rewritten as the comma CSV CARSKit requires)."""
     from carskit_amd import dao
     from oracle import dao_oracle
-    raw = zipfile.ZipFile(FRAPPE_ZIP).read("Mobile_Frappe/frappe/frappe.csv").decode("utf-8")
-    src = tmp_path / "frappe_compact.csv"
-    src.write_text("\n".join(",".join(line.split("\t")) for line in raw.splitlines()) + "\n")
+    from tests import frappe
+    src = frappe.write_ratings(tmp_path)
     out = tmp_path / "train.csv"
     tree = dao.transform_compact_to_binary(str(src), str(out))
     d = dao.DataDAO(str(out))

@@ -5,18 +5,16 @@ oracle/jvm/javasrc.py: `buildModel()` -> `GpuSupport.buildModel(this)` -> marsha
 `isConverged()`, copy-back; the `NativeMF` natives land in a stand-in that drives the order-exact CPU oracle with the arguments the C ABI
 would get.  The bar is bit-identity with the reference's own `buildModel()` (tests/golden/reference_src.json).
 
-The committed verdict (tests/golden/java_binding_check.json) is checked everywhere; the live re-run needs the reference tree
-(/root/reference: present in the build container, absent on the GPU box) and is skipped without it."""
+The committed verdict (tests/golden/java_binding_check.json) is what these tests check; the live re-run needs the reference's own
+sources and jars, which are not part of this repository, so it is a tool (`python oracle/check_java_binding.py <reference tree>`
+rewrites the verdict), not a test."""
 import json
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _ALL = json.load(open(os.path.join(ROOT, "tests", "golden", "java_binding_check.json")))
 CHECK = _ALL["models"]
-REF = os.environ.get("CARSKIT_REFERENCE", "/root/reference")
 
 
 def test_committed_verdict_covers_every_sgd_drop_in_and_is_bit_identical():
@@ -88,31 +86,3 @@ def test_committed_gpu_ranking_runs_give_the_reference_measures():
         assert tail[0] == "create" and tail[-1] == "destroy" and tail[-2] == "evalRankings", (model, tail)
         assert "setHparams" in tail and any(c.startswith("setRatings") for c in tail) and "setMatrix" in tail
         assert "trainEpoch" not in tail
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src", "carskit")), reason="needs the reference tree (build container only)")
-def test_drop_ins_execute_bit_identically_to_the_reference_buildmodel():
-    from oracle import check_java_binding as chk
-    cases = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_src.json")))["cases"]
-    seen = set()
-    for case in cases:
-        if case["model"] in seen:
-            continue
-        seen.add(case["model"])
-        calls, same, stmts = chk.check(REF, case)
-        assert all(same.values()), (case["model"], same)
-        assert calls == CHECK[case["model"]]["native_calls"], case["model"]
-        assert stmts > 100
-    assert len(seen) == 10
-    fm = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_src.json")))["fm_cases"][0]
-    calls, same, _ = chk.check_fm(REF, fm)
-    assert all(same.values()) and calls == CHECK["FM"]["native_calls"]
-    calls, same = chk.check_early_stop(REF, [c for c in cases if c["model"] == "CAMF_CU"][0])
-    assert all(same.values()) and calls == _ALL["early_stop_rmse"]["native_calls"]
-    rank_case = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_rank.json")))["cases"][0]
-    calls, same = chk.check_rank(REF, rank_case)
-    assert all(same.values()) and calls == _ALL["rank_on_gpu"][rank_case["model"]]["native_calls"]
-    calls, same = chk.check_fm_rank(REF, json.load(open(os.path.join(ROOT, "tests", "golden", "reference_rank.json")))["fm_cases"][0])
-    assert all(same.values()) and calls == _ALL["rank_on_gpu"]["FM"]["native_calls"]
-    calls, same = chk.check_group(REF, [c for c in cases if c["model"] == "CAMF_CI"][0])
-    assert all(same.values()) and calls == _ALL["shards_2"]["native_calls"]
