@@ -3,7 +3,6 @@
 // loop, predict/eval.  Compiled by hipcc together with mf_sgd_kernels.hip into libcarskit_mi355x.so.
 // There is deliberately no CPU code path for any compute entry point.
 #include "../../include/carskit_mi355x.h"
-#include "env_knobs.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -14,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <initializer_list>
 #include <string>
 #include <condition_variable>
 #include <mutex>
@@ -88,45 +88,42 @@ static void free_eval_set(cmi_instance *h) {
     h->n_eval = 0;
 }
 
-// the resident test tuples index the context table of the ratings they were uploaded against: they go with it
-static void free_ratings(cmi_instance *h) {
-    if (h->arena_on && h->arena_valid && !h->table_valid) cmi_sync_table_from_arena(h); // the live rows are in the arena: bring them home first
-    for (void **p : {(void **)&h->d_arena, (void **)&h->d_next, (void **)&h->d_first})
+static void free_and_null(std::initializer_list<void **> ptrs) {
+    for (void **p : ptrs)
         if (*p) {
             hipFree(*p);
             *p = nullptr;
         }
+}
+
+// the spoke arena and its position lists; the model table is the master copy again
+static void release_arena(cmi_instance *h) {
+    free_and_null({(void **)&h->d_arena, (void **)&h->d_next, (void **)&h->d_first});
     h->arena_on = h->arena_valid = false;
-    h->arena_probe = false;
     h->table_valid = true;
+}
+
+// the resident test tuples index the context table of the ratings they were uploaded against: they go with it
+static void free_ratings(cmi_instance *h) {
+    if (h->arena_on && h->arena_valid && !h->table_valid) cmi_sync_table_from_arena(h); // the live rows are in the arena: bring them home first
+    release_arena(h);
+    h->arena_probe = false;
     free_eval_set(h);
     if (h->graph_exec) {
         hipGraphExecDestroy(h->graph_exec);
         h->graph_exec = nullptr;
     }
-    void *ptrs[] = {h->d_su, h->d_sj, h->d_sconds, h->d_ctx_ptr, h->d_ctx_conds, h->d_sr, h->d_loss_part,
-                    h->d_flow_err, h->d_tail_off, h->d_blk_off, h->d_unit_off,
-                    h->d_ui_ptr, h->d_ui_items, h->d_own_recs, h->d_own_off, h->d_tagged};
-    h->d_own_recs = nullptr;
-    h->d_own_off = nullptr;
-    h->d_tagged = nullptr;
+    free_and_null({(void **)&h->d_su, (void **)&h->d_sj, (void **)&h->d_sconds, (void **)&h->d_ctx_ptr, (void **)&h->d_ctx_conds,
+                   (void **)&h->d_sr, (void **)&h->d_loss_part, (void **)&h->d_flow_err, (void **)&h->d_tail_off, (void **)&h->d_blk_off,
+                   (void **)&h->d_unit_off, (void **)&h->d_ui_ptr, (void **)&h->d_ui_items, (void **)&h->d_own_recs, (void **)&h->d_own_off,
+                   (void **)&h->d_tagged});
     h->owner = false;
     h->owner_stalled = false;
-    h->d_ui_ptr = h->d_ui_items = nullptr;
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    h->d_su = h->d_sj = h->d_sconds = h->d_ctx_ptr = h->d_ctx_conds = nullptr;
-    h->d_flow_err = nullptr;
-    h->d_tail_off = nullptr;
-    h->d_blk_off = nullptr;
-    h->d_unit_off = nullptr;
     h->chain = false;
     h->n_units = 0;
     h->blk_off.clear();
     h->n_launches = h->n_tail = 0;
     h->tail_len.clear();
-    h->d_sr = nullptr;
-    h->d_loss_part = nullptr;
     h->have_ratings = false;
     h->n = 0;
 }
@@ -206,18 +203,7 @@ extern "C" int cmi_create(int model, int k, int n_users, int n_items, int n_cond
         e = (x);                                                                                        \
     }
     TRY(hipSetDevice(device));
-    // experiment builds: CMI_STREAM_CUS="m:r0,r1,..." -- the instance's stream may only use the compute units whose index mod m is one of
-    // the residues (the driver deals consecutive mask bits round the XCDs, so m = 8 selects XCDs and m = 16 halves of every XCD)
-    if (const char *cus = cmi_exp_env("CMI_STREAM_CUS")) {
-        int m = atoi(cus), n_cu = 0;
-        uint32_t want = 0, mask[16] = {};
-        for (const char *p = strchr(cus, ':'); p && *p; p = strchr(p + 1, ',')) want |= 1u << (atoi(p + 1) & 31);
-        TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
-        for (int c = 0; c < n_cu && c < 512 && m > 0; ++c)
-            if (want >> (c % m) & 1) mask[c / 32] |= 1u << (c % 32);
-        TRY(hipExtStreamCreateWithCUMask(&h->stream, (uint32_t)((n_cu + 31) / 32), mask));
-    } else
-        TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     TRY(hipEventCreate(&h->ev0));
     TRY(hipEventCreate(&h->ev1));
     for (int w = 0; w < CMI_STATE_COUNT; ++w) {
@@ -492,6 +478,13 @@ extern "C" int cmi_arena_positions(int64_t n, const int32_t *spoke, int32_t n_sp
     return CMI_OK;
 }
 
+// CMI_CHAIN_HUB / CMI_OWNER_HUB = item | user (tests): the hub side forced; unset or anything else keeps `dflt`
+static int hub_from_env(const char *name, int dflt) {
+    const char *env = getenv(name);
+    if (!env) return dflt;
+    return !strcmp(env, "item") ? 1 : (!strcmp(env, "user") ? 0 : dflt);
+}
+
 // Hub-chain level schedule (level_schedule.cpp): used when forced, or when its levels are wide enough to fill the chip
 // (narrow levels -- heavy-tailed degrees, tiny data -- stay with the plain levels and their narrow-run launches).
 static int chain_max_len() {
@@ -503,8 +496,7 @@ static void free_keep(ChainDeviceKeep &keep) { keep.release(); } // (early: 12 b
 static bool try_chain(cmi_instance *h, int64_t n, const int32_t *u, const int32_t *j, ChainSchedule &csch, ChainDeviceKeep &keep) {
     // the side that carries the context-bias rows is preferred as the hub side (CAMF_CI: items, CAMF_CU: users): measured on the C5
     // share (CAMF_CU k=256, 128 conditions) 50.1 ms per epoch along users (36.4 M units) against 64.3 ms along items (31.9 M units)
-    int hub = h->model == CMI_MODEL_CAMF_CU ? -2 : (h->model == CMI_MODEL_CAMF_CI ? -3 : -1);
-    if (const char *env = getenv("CMI_CHAIN_HUB")) hub = !strcmp(env, "item") ? 1 : (!strcmp(env, "user") ? 0 : hub);
+    const int hub = hub_from_env("CMI_CHAIN_HUB", h->model == CMI_MODEL_CAMF_CU ? -2 : (h->model == CMI_MODEL_CAMF_CI ? -3 : -1));
     // large sets: the schedule is built on the device (sched_device.hip: the same schedule, element for element; the host walk is
     // 11 ns per tuple on one core).  CMI_SCHEDULE_DEVICE=0 / 1: never / at any size.
     int64_t dev_min = (int64_t)1 << 21;
@@ -518,8 +510,7 @@ static bool try_chain(cmi_instance *h, int64_t n, const int32_t *u, const int32_
         }
     }
     if (!built && !build_chain_schedule(n, u, j, h->n_users, h->n_items, hub, chain_max_len(), csch)) return false;
-    int64_t min_width = 2048; // mean units per level
-    if (const char *env = cmi_exp_env("CMI_CHAIN_MIN_WIDTH")) min_width = atoll(env);
+    const int64_t min_width = 2048; // mean units per level
     const bool forced = h->flags & CMI_FLAG_SCHED_CHAIN;
     // Narrow levels (heavy-tailed degrees, tiny data) keep the plain levels and their narrow-run launches: measured on C3-size
     // Zipf(0.8) items, the chain schedule has 2.5x fewer levels (434 K vs 1.10 M) but a narrow chain level is latency-bound on
@@ -535,349 +526,348 @@ static bool try_chain(cmi_instance *h, int64_t n, const int32_t *u, const int32_
     return true;
 }
 
-static int set_ratings_impl(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r, int32_t n_ctx,
-                            const int32_t *ctx_ptr, const int32_t *ctx_conds);
+// the tuple arrays of one cmi_set_ratings call
+struct RatingsIn {
+    int64_t n;
+    const int32_t *u, *j, *ctx;
+    const double *r;
+    int32_t n_ctx;
+    const int32_t *ctx_ptr, *ctx_conds;
+};
 
-// the exception barrier of the boundary: the schedule construction allocates O(tuples) host memory on the host pool's threads
-// (host_pool.hpp hands a range body's exception to the caller); nothing C++ may cross into a C / JNI / ctypes host
-extern "C" int cmi_set_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
-                               const double *r, int32_t n_ctx, const int32_t *ctx_ptr, const int32_t *ctx_conds) {
-    if (!h) return CMI_E_INVALID;
-    try {
-        return set_ratings_impl(h, n, u, j, ctx, r, n_ctx, ctx_ptr, ctx_conds);
-    } catch (const std::exception &e) {
-        h->have_ratings = false;
-        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure: %s", e.what());
-    } catch (...) {
-        h->have_ratings = false;
-        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure (unknown exception)");
+// The spoke arena of a large set is tens of GB (north_star: 102 GB).  hipMalloc hands out CLEAN device memory at once (0.001 s for
+// 102 GB) but waits for the driver's wipe of blocks this process freed a moment ago (~30 ms per GB: tools/exp/hipmalloc_probe.py,
+// tools/micro/alloc_time.hip), and the schedule build frees GBs of temporaries.  So when the sizes say an arena is likely (a side's
+// table >= 2 GiB, or it is forced) it is allocated before anything of the schedule build has been freed; setup_arena takes it over
+// or this frees it.  (Round 5 first allocated it on a side thread beside the schedule build: 1.9 s for the same call, and every
+// other HIP call of the build slowed down beside it.)
+struct SpecArena {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+    void *take(size_t want) {
+        if (ptr && bytes == want) {
+            void *p = ptr;
+            ptr = nullptr;
+            return p;
+        }
+        return nullptr;
     }
+    ~SpecArena() {
+        if (ptr) (void)hipFree(ptr);
+    }
+};
+
+// the tuple stream as the host gathers it (empty when the device builds it); the uploads read it asynchronously
+struct HostStream {
+    HostBuf<int32_t> su, sj, sconds;
+    HostBuf<float> sr32;
+    HostBuf<double> sr64;
+};
+
+static bool arena_kernel_ok(const cmi_instance *h) { // the chain kernel's arena form exists and no flag forbids it
+    return !(h->flags & CMI_FLAG_NO_ARENA) && h->k >= 64 && h->k % (h->f64 ? 2 : 4) == 0;
 }
 
-static int set_ratings_impl(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r, int32_t n_ctx,
-                            const int32_t *ctx_ptr, const int32_t *ctx_conds) {
+// refusals that come before anything is released: the current ratings stay
+static int check_ratings_args(cmi_instance *h, const RatingsIn &in) {
     const bool contextual = !is_2d_model(h->model);
-    if (n < 0 || (n > 0 && (!u || !j || !r))) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: null tuple arrays");
+    if (in.n < 0 || (in.n > 0 && (!in.u || !in.j || !in.r))) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: null tuple arrays");
     if (is_ext_model(h->model) && h->model != CMI_MODEL_SVDPP && (!h->sim_params_set || (h->model == CMI_MODEL_CAMF_LCS && h->num_f < 1)))
         CMI_FAIL(h, CMI_E_INVALID, "set_ratings: call cmi_set_sim_params first (EmptyContextConditions%s)", h->model == CMI_MODEL_CAMF_LCS ? ", numF" : "");
-    if (contextual && is_ext_model(h->model) && n_ctx > 0 && ctx_ptr) {
-        for (int32_t c = 0; c < n_ctx; ++c)
-            if (ctx_ptr[c + 1] - ctx_ptr[c] > 16) CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: more than 16 conditions per context");
+    if (contextual && is_ext_model(h->model) && in.n_ctx > 0 && in.ctx_ptr) {
+        for (int32_t c = 0; c < in.n_ctx; ++c)
+            if (in.ctx_ptr[c + 1] - in.ctx_ptr[c] > 16) CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: more than 16 conditions per context");
         // condition i of a context is paired with EmptyContextConditions.get(i) (CAMF_ICS.java:56,88: an IndexOutOfBoundsException in the
         // reference when the data has fewer ':na' conditions than a context has conditions, e.g. Frappe, which has none)
-        for (int32_t c = 0; c < n_ctx; ++c)
-            if (ctx_ptr[c + 1] - ctx_ptr[c] > (int32_t)h->empty_conds.size())
+        for (int32_t c = 0; c < in.n_ctx; ++c)
+            if (in.ctx_ptr[c + 1] - in.ctx_ptr[c] > (int32_t)h->empty_conds.size())
                 CMI_FAIL(h, CMI_E_INVALID, "set_ratings: context %d has %d conditions but EmptyContextConditions has %d entries "
-                         "(IndexOutOfBoundsException in the reference, CAMF_ICS.java:88)", c, ctx_ptr[c + 1] - ctx_ptr[c], (int)h->empty_conds.size());
+                         "(IndexOutOfBoundsException in the reference, CAMF_ICS.java:88)", c, in.ctx_ptr[c + 1] - in.ctx_ptr[c], (int)h->empty_conds.size());
     }
-    if (contextual && (n_ctx < 0 || !ctx_ptr || (n > 0 && !ctx) || (n_ctx > 0 && ctx_ptr[n_ctx] > 0 && !ctx_conds)))
+    if (contextual && (in.n_ctx < 0 || !in.ctx_ptr || (in.n > 0 && !in.ctx) || (in.n_ctx > 0 && in.ctx_ptr[in.n_ctx] > 0 && !in.ctx_conds)))
         CMI_FAIL(h, CMI_E_INVALID, "set_ratings: context table required for model %d", h->model);
-    CMI_HIP(h, hipSetDevice(h->device));
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    free_ratings(h);
+    return CMI_OK;
+}
 
-    const bool times = getenv("CMI_SETUP_TIMES") != nullptr; // per-phase wall times of this call on stderr
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char *w) {
-        if (!times) return;
-        const auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "set_ratings %s %.3f s\n", w, std::chrono::duration<double>(t - T0).count());
-        T0 = t;
-    };
-    // validate ids (the reference would throw ArrayIndexOutOfBounds inside the loop)
-    int dmax = 0;
+// stage 1: the context table and every tuple's ids in range (the reference would throw ArrayIndexOutOfBounds inside the loop);
+// dmax = the most conditions of one context
+static int validate_ratings(cmi_instance *h, const RatingsIn &in, int &dmax) {
+    const bool contextual = !is_2d_model(h->model);
+    const int32_t *u = in.u, *j = in.j, *ctx = in.ctx;
+    dmax = 0;
     if (contextual) {
-        if (ctx_ptr[0] != 0) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: ctx_ptr[0] != 0");
-        for (int32_t c = 0; c < n_ctx; ++c) {
-            const int32_t len = ctx_ptr[c + 1] - ctx_ptr[c];
+        if (in.ctx_ptr[0] != 0) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: ctx_ptr[0] != 0");
+        for (int32_t c = 0; c < in.n_ctx; ++c) {
+            const int32_t len = in.ctx_ptr[c + 1] - in.ctx_ptr[c];
             if (len < 0) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: ctx_ptr not monotone at %d", c);
             if (len > dmax) dmax = len;
         }
-        for (int32_t q = 0; q < ctx_ptr[n_ctx]; ++q)
-            if (ctx_conds[q] < 0 || ctx_conds[q] >= h->n_conds)
-                CMI_FAIL(h, CMI_E_INVALID, "set_ratings: condition id %d out of range [0,%d)", ctx_conds[q], h->n_conds);
+        for (int32_t q = 0; q < in.ctx_ptr[in.n_ctx]; ++q)
+            if (in.ctx_conds[q] < 0 || in.ctx_conds[q] >= h->n_conds)
+                CMI_FAIL(h, CMI_E_INVALID, "set_ratings: condition id %d out of range [0,%d)", in.ctx_conds[q], h->n_conds);
     }
-    {
-        const int nt = host_threads(n);
-        std::vector<int64_t> bad((size_t)nt, -1); // first offending tuple of every range; the earliest is reported, as a sequential scan would
-        parallel_ranges(n, nt, [&](int part, int64_t b, int64_t e) {
-            for (int64_t t = b; t < e; ++t)
-                if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || (contextual && (ctx[t] < 0 || ctx[t] >= n_ctx))) {
-                    bad[(size_t)part] = t;
-                    return;
-                }
-        });
-        for (int64_t t : bad) {
-            if (t < 0) continue;
-            if (u[t] < 0 || u[t] >= h->n_users) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: user id %d out of range at tuple %lld", u[t], (long long)t);
-            if (j[t] < 0 || j[t] >= h->n_items) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: item id %d out of range at tuple %lld", j[t], (long long)t);
-            CMI_FAIL(h, CMI_E_INVALID, "set_ratings: context id %d out of range at tuple %lld", ctx[t], (long long)t);
-        }
+    const int nt = host_threads(in.n);
+    std::vector<int64_t> bad((size_t)nt, -1); // first offending tuple of every range; the earliest is reported, as a sequential scan would
+    parallel_ranges(in.n, nt, [&](int part, int64_t b, int64_t e) {
+        for (int64_t t = b; t < e; ++t)
+            if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || (contextual && (ctx[t] < 0 || ctx[t] >= in.n_ctx))) {
+                bad[(size_t)part] = t;
+                return;
+            }
+    });
+    for (int64_t t : bad) {
+        if (t < 0) continue;
+        if (u[t] < 0 || u[t] >= h->n_users) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: user id %d out of range at tuple %lld", u[t], (long long)t);
+        if (j[t] < 0 || j[t] >= h->n_items) CMI_FAIL(h, CMI_E_INVALID, "set_ratings: item id %d out of range at tuple %lld", j[t], (long long)t);
+        CMI_FAIL(h, CMI_E_INVALID, "set_ratings: context id %d out of range at tuple %lld", ctx[t], (long long)t);
     }
-    if (n >= ((int64_t)1 << 31) - 1024) CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: more than 2^31-1025 tuples per instance");
-    lap("validate");
+    if (in.n >= ((int64_t)1 << 31) - 1024) CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: more than 2^31-1025 tuples per instance");
+    return CMI_OK;
+}
 
-    h->n = n;
-    h->n_ctx = contextual ? n_ctx : 0;
-    h->dmax = dmax;
-    LaunchCfg cfg{h->model, h->strict};
+// stage 2a: the level launch forms, and the schedule flags checked against the kernels that exist.  chain_ok = a hub-chain kernel
+// exists and no flag rules it out
+static int check_schedule_flags(cmi_instance *h, int dmax, bool &chain_ok) {
+    const LaunchCfg cfg{h->model, h->strict};
     h->fast = !h->serial && has_fast_path(h->k, dmax, h->f64, cfg);
     h->small = !h->serial && !h->fast && has_small_path(h->k, dmax, h->f64, cfg);
-
-    // schedule
-    LevelSchedule sch;
-    ChainSchedule csch;
-    OwnerSchedule osch;
-    const bool chain_ok = !h->serial && !h->want_owner && !(h->flags & CMI_FLAG_NO_CHAIN) &&
-                          has_chain_path(h->model, h->k, dmax, h->n_conds, h->f64, h->strict) && !cmi_exp_env("CMI_NO_CHAIN");
+    chain_ok = !h->serial && !h->want_owner && !(h->flags & CMI_FLAG_NO_CHAIN) && has_chain_path(h->model, h->k, dmax, h->n_conds, h->f64, h->strict);
     if ((h->flags & CMI_FLAG_SCHED_CHAIN) && !chain_ok)
         CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: CMI_FLAG_SCHED_CHAIN: no hub-chain kernel for model %d, k=%d, %s state%s (or another "
                  "schedule flag is set)", h->model, h->k, h->f64 ? "fp64" : "fp32", h->strict ? ", strict" : "");
-    h->owner = false;
-    h->owner_stalled = false;
     if (h->want_owner && (h->serial || !has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict)))
         CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: CMI_FLAG_SCHED_OWNER: no owner kernel for model %d, k=%d, %d conditions, %s state%s (or "
                  "another schedule flag is set)", h->model, h->k, h->n_conds, h->f64 ? "fp64" : "fp32", h->strict ? ", strict" : "");
-    // the hub-chain levels first: wide data is theirs
-    // The spoke arena of a large set is tens of GB (north_star: 102 GB).  hipMalloc hands out CLEAN device memory at once (0.001 s for
-    // 102 GB) but waits for the driver's wipe of blocks this process freed a moment ago (~30 ms per GB: tools/exp/hipmalloc_probe.py,
-    // tools/micro/alloc_time.hip), and the schedule build below frees GBs of temporaries.  So when the sizes say an arena is likely (a
-    // side's table >= 2 GiB, or it is forced) it is allocated HERE, before anything of this call has been freed; the arena block below
-    // takes it over or frees it.  (Round 5 first allocated it on a side thread beside the schedule build: 1.9 s for the same call, and
-    // every other HIP call of the build slowed down beside it.)
-    struct SpecArena {
-        void *ptr = nullptr;
-        size_t bytes = 0;
-        void *take(size_t want) {
-            if (ptr && bytes == want) {
-                void *p = ptr;
-                ptr = nullptr;
-                return p;
-            }
-            return nullptr;
-        }
-        ~SpecArena() {
-            if (ptr) (void)hipFree(ptr);
-        }
-    } spec;
-    if (!h->serial && chain_ok && n >= ((int64_t)1 << 21) && !(h->flags & CMI_FLAG_NO_ARENA) && !cmi_exp_env("CMI_NO_ARENA") && h->k >= 64 &&
-        h->k % (h->f64 ? 2 : 4) == 0) {
-        const size_t row = (size_t)h->k * esize(h), arena_bytes = (size_t)n * row;
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        const bool likely = (h->flags & CMI_FLAG_SPOKE_ARENA) || cmi_exp_env("CMI_ARENA") || (size_t)std::max(h->n_users, h->n_items) * row >= ((size_t)2 << 30);
-        if (likely && (double)arena_bytes <= 0.6 * (double)free_b) {
-            if (hipMalloc(&spec.ptr, arena_bytes) == hipSuccess) spec.bytes = arena_bytes;
-            else {
-                spec.ptr = nullptr;
-                (void)hipGetLastError(); // the arena block decides again (and reports) with what is free then
-            }
+    return CMI_OK;
+}
+
+// the arena allocated ahead of the schedule build when the sizes announce one (SpecArena)
+static void speculative_arena(const cmi_instance *h, int64_t n, bool chain_ok, SpecArena &spec) {
+    if (!chain_ok || n < ((int64_t)1 << 21) || !arena_kernel_ok(h)) return;
+    const size_t row = (size_t)h->k * esize(h), arena_bytes = (size_t)n * row;
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const bool likely = (h->flags & CMI_FLAG_SPOKE_ARENA) || (size_t)std::max(h->n_users, h->n_items) * row >= ((size_t)2 << 30);
+    if (likely && (double)arena_bytes <= 0.6 * (double)free_b) {
+        if (hipMalloc(&spec.ptr, arena_bytes) == hipSuccess) spec.bytes = arena_bytes;
+        else {
+            spec.ptr = nullptr;
+            (void)hipGetLastError(); // setup_arena decides again (and reports) with what is free then
         }
     }
-    lap("arena allocation");
-    ChainDeviceKeep keep; // device-built schedule: the tuple ids and the permutation stay on the device for the stream build
-    const bool use_chain = !h->serial && chain_ok && n > 0 && try_chain(h, n, u, j, csch, keep);
-    const bool dev_stream = use_chain && keep.d_perm != nullptr;
-    bool use_owner = h->want_owner;
+}
+
+// The owner cost model, a function of the tuple arrays alone: true when the degrees are heavy-tailed and the owner epoch is expected
+// to be at least twice faster than the level walk.  Narrow levels on a large data set = heavy-tailed degrees: every level costs a
+// kernel boundary or a workgroup barrier (>= 2 us), and there are at least as many levels as the hottest row has tuples.  The owner
+// epoch pays ~0.3 us per tuple of the hottest row it owns and a hand-off (0.86 us measured, tools/exp_owner_handoff.py) per tuple of
+// the hottest row on the other side, plus ~0.3 ms for the tag / untag passes and the launch (measured: 3.3-3.7x at 100 K - 800 K
+// ratings with Zipf(1.1) items, tests/tools/bench_zipf_small.py).  `note` says why heavy-tailed data stays with the level walk.
+static bool owner_pays_off(int model, int k, int n_conds, bool f64, int32_t n_users, int32_t n_items, int64_t n, const int32_t *u,
+                           const int32_t *j, std::string &note) {
+    std::vector<int32_t> du((size_t)n_users, 0), dj((size_t)n_items, 0);
+    for (int64_t t = 0; t < n; ++t) {
+        du[(size_t)u[t]]++;
+        dj[(size_t)j[t]]++;
+    }
+    const double mu = *std::max_element(du.begin(), du.end()), mj = *std::max_element(dj.begin(), dj.end());
+    const bool hub_item = mj >= mu; // what build_owner_schedule will pick
+    int64_t rows_used = 0;          // rows of the hub side that have tuples at all
+    for (int32_t d : (hub_item ? dj : du)) rows_used += d > 0;
+    // heavy-tailed = the hottest hub row holds at least 8 average rows' worth of tuples (uniform data: 1.5 - 2)
+    const bool skewed = std::max(mu, mj) * (double)rows_used >= 8.0 * (double)n;
+    if (!skewed) return false;
+    // the tagged record table is addressed through one buffer resource: below 4 GB
+    const int64_t rec_bytes = owner_record_stride(model, k, n_conds, f64, hub_item) * 8;
+    if (((int64_t)(hub_item ? n_users : n_items) + 4096) * rec_bytes >= ((int64_t)1 << 32) - 65536) {
+        note = "heavy-tailed degrees, but the owner epoch's tagged record table would exceed 4 GB (too many spoke rows at this k): "
+               "the level walk runs instead -- order-exact, roughly 10x slower on such data";
+        return false;
+    }
+    // owner: the hottest chains, or the bulk spread over ~1 000 owners at ~0.5 us per tuple of a list that switches rows
+    const double est_owner = std::max(std::max(std::max(mu, mj) * 0.3e-6, std::min(mu, mj) * 1e-6), (double)n * 0.5e-6 / 1024.0) + 0.3e-3;
+    // levels: a boundary or barrier per level plus the traffic (2 KB per tuple at ~5 TB/s)
+    const double est_levels = (double)count_plain_levels(n, u, j, n_users, n_items) * 2e-6 + (double)n * 0.4e-9;
+    return est_levels >= 2.0 * est_owner;
+}
+
+// stage 2b: which schedule runs -- serial when asked for, the hub-chain levels when they are wide (try_chain sets h->chain), the owner
+// epoch when forced or when the cost model picks it, the plain levels otherwise -- and the note when a slower one runs than the data
+// calls for.  Returns whether the owner epoch runs.
+static bool choose_schedule(cmi_instance *h, const RatingsIn &in, bool chain_ok, ChainSchedule &csch, ChainDeviceKeep &keep) {
+    const int64_t n = in.n;
     h->sched_note.clear();
-    if (!use_owner && !use_chain && !h->serial && n >= ((int64_t)1 << 16) &&
-        !has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict) && !(h->flags & CMI_FLAG_NO_OWNER))
+    if (chain_ok && n > 0 && try_chain(h, n, in.u, in.j, csch, keep)) return false;
+    if (h->want_owner) return true;
+    if (h->serial) return false;
+    const bool owner_kernel = has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict);
+    if (n >= ((int64_t)1 << 16) && !owner_kernel && !(h->flags & CMI_FLAG_NO_OWNER))
         h->sched_note = "narrow dependency levels on a large data set (heavy-tailed degrees?) and no owner kernel for this configuration "
                         "(limits: <= 384 conditions, k <= 256 (fp64: 128)): the level walk runs -- order-exact, roughly 10x slower on such data";
-    if (!use_owner && !use_chain && !h->serial && !(h->flags & (CMI_FLAG_SCHED_CHAIN | CMI_FLAG_NO_OWNER)) &&
-        !cmi_exp_env("CMI_NO_OWNER") && has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict)) {
-        // Narrow levels on a large data set = heavy-tailed degrees: every level costs a kernel boundary or a workgroup barrier (>= 2 us),
-        // and there are at least as many levels as the hottest row has tuples.  The owner epoch pays ~0.3 us per tuple of the hottest
-        // row it owns and a hand-off (0.86 us measured, tools/exp_owner_handoff.py) per tuple of the hottest row on the other side,
-        // plus ~0.3 ms for the tag / untag passes and the launch.  Taken for heavy-tailed data when that is at least twice faster
-        // (measured: 3.3-3.7x at 100 K - 800 K ratings with Zipf(1.1) items, tests/tools/bench_zipf_small.py).
-        int64_t min_tuples = (int64_t)1 << 16;
-        if (const char *env = cmi_exp_env("CMI_OWNER_MIN_TUPLES")) min_tuples = atoll(env);
-        if (n >= min_tuples) {
-            std::vector<int32_t> du((size_t)h->n_users, 0), dj((size_t)h->n_items, 0);
-            for (int64_t t = 0; t < n; ++t) {
-                du[(size_t)u[t]]++;
-                dj[(size_t)j[t]]++;
-            }
-            const double mu = *std::max_element(du.begin(), du.end()), mj = *std::max_element(dj.begin(), dj.end());
-            const bool hub_item = mj >= mu; // what build_owner_schedule will pick
-            int64_t rows_used = 0;          // rows of the hub side that have tuples at all
-            for (int32_t d : (hub_item ? dj : du)) rows_used += d > 0;
-            // heavy-tailed = the hottest hub row holds at least 8 average rows' worth of tuples (uniform data: 1.5 - 2)
-            const bool skewed = std::max(mu, mj) * (double)rows_used >= 8.0 * (double)n;
-            // the tagged record table is addressed through one buffer resource: below 4 GB
-            const int64_t rec_bytes = owner_record_stride(h->model, h->k, h->n_conds, h->f64, hub_item) * 8;
-            const bool table_fits = ((int64_t)(hub_item ? h->n_users : h->n_items) + 4096) * rec_bytes < ((int64_t)1 << 32) - 65536;
-            h->sched_note.clear();
-            if (skewed && !table_fits)
-                h->sched_note = "heavy-tailed degrees, but the owner epoch's tagged record table would exceed 4 GB (too many spoke rows at this k): "
-                                "the level walk runs instead -- order-exact, roughly 10x slower on such data";
-            if (skewed && table_fits) {
-                // owner: the hottest chains, or the bulk spread over ~1 000 owners at ~0.5 us per tuple of a list that switches rows
-                const double est_owner = std::max(std::max(std::max(mu, mj) * 0.3e-6, std::min(mu, mj) * 1e-6), (double)n * 0.5e-6 / 1024.0) + 0.3e-3;
-                // levels: a boundary or barrier per level plus the traffic (2 KB per tuple at ~5 TB/s)
-                const double est_levels = (double)count_plain_levels(n, u, j, h->n_users, h->n_items) * 2e-6 + (double)n * 0.4e-9;
-                use_owner = est_levels >= 2.0 * est_owner;
-            }
-        }
+    if (n < ((int64_t)1 << 16) || !owner_kernel || (h->flags & (CMI_FLAG_SCHED_CHAIN | CMI_FLAG_NO_OWNER))) return false;
+    return owner_pays_off(h->model, h->k, h->n_conds, h->f64, h->n_users, h->n_items, n, in.u, in.j, h->sched_note);
+}
+
+// stage 3: the owners' lists and the teams.  The owners must all be resident: as many as the device holds wavefronts of the kernel
+// (either hub side: same registers).  The owner epoch is one launch with a loss slot per owner; sch takes the schedule's order.
+static int build_owner_lists(cmi_instance *h, const RatingsIn &in, OwnerSchedule &osch, LevelSchedule &sch) {
+    const int64_t n = in.n;
+    const int32_t *u = in.u, *j = in.j;
+    if (n == 0) return CMI_OK; // (the plain levels of an empty set)
+    const int hub = hub_from_env("CMI_OWNER_HUB", -1);
+    int waves = owner_grid_waves(h->device, h->model, h->n_conds, h->k, h->f64, true);
+    // cmi_set_device_share: this instance's share of the resident wavefronts (whole workgroups of four owners), so that the
+    // persistent launches of the instances that train side by side are co-resident
+    if (h->device_share > 1 && waves > 0) waves = std::max(8, waves / h->device_share / 4 * 4);
+    if (const char *env = getenv("CMI_OWNER_WAVES")) {
+        const int v = atoi(env);
+        if (v >= 1 && v < waves) waves = v;
     }
-    if (use_owner) {
-        int hub = -1;
-        if (const char *env = getenv("CMI_OWNER_HUB")) hub = !strcmp(env, "item") ? 1 : (!strcmp(env, "user") ? 0 : -1);
-        if (n > 0) {
-            // the owners must all be resident: as many as the device holds wavefronts of the kernel (either hub side: same registers)
-            int waves = owner_grid_waves(h->device, h->model, h->n_conds, h->k, h->f64, true);
-            // cmi_set_device_share: this instance's share of the resident wavefronts (whole workgroups of four owners), so that the
-            // persistent launches of the instances that train side by side are co-resident
-            if (h->device_share > 1 && waves > 0) waves = std::max(8, waves / h->device_share / 4 * 4);
-            if (const char *env = getenv("CMI_OWNER_WAVES")) {
-                const int v = atoi(env);
-                if (v >= 1 && v < waves) waves = v;
-            }
-            if (waves < 1) CMI_FAIL(h, CMI_E_HIP, "set_ratings: owner kernel occupancy query failed");
+    if (waves < 1) CMI_FAIL(h, CMI_E_HIP, "set_ratings: owner kernel occupancy query failed");
+    if (!build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, waves, owner_depth(), osch))
+        CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule construction failed");
+    // Teams: the leading owners (the hottest rows, alone in their lists) whose list is long enough to bound the epoch run as three
+    // wavefronts in a workgroup of their own instead of one wavefront among four.  A team takes a whole workgroup, so the owner
+    // count shrinks by three per team and the rows are dealt again.
+    h->n_team = 0;
+    int64_t team_min = 8192;
+    const char *team_env = getenv("CMI_OWNER_TEAM");
+    if (const char *env = getenv("CMI_OWNER_TEAM_MIN")) team_min = atoll(env);
+    auto leading_single_hub = [&](const OwnerSchedule &os, int limit) {
+        int t = 0;
+        for (; t < limit && t < (int)os.n_owners(); ++t) {
+            const int64_t b = os.own_off[(size_t)t], e = os.own_off[(size_t)t + 1];
+            if (e - b < team_min) break;
+            bool single = true;
+            for (int64_t pos = b + 1; pos < e && single; ++pos) single = os.flags[(size_t)pos] & OWN_HUB_FWD;
+            if (!single) break;
+        }
+        return t;
+    };
+    const int wgs = (waves + 3) / 4; // resident workgroups
+    if (h->strict || (team_env && !strcmp(team_env, "0"))) {
+        // one wavefront per owner throughout (the strict form has no team body; CMI_OWNER_TEAM=0: tests and A/B runs).
+        // (Round 5 also refused teams to sharing instances and to fp64 at k <= 64 because that form was measured inexact beside
+        // another owner epoch.  The cause was a store-data hazard in the record stores of BOTH bodies -- the compiler had merely
+        // happened to reuse the data registers at once only in that instantiation -- fixed in owner_kernels.hip owner_st_words;
+        // tests/test_gpu_soak.py holds every instantiation beside other owner epochs bit for bit.  docs/history/r06.md 1.)
+    } else if (team_env && !strcmp(team_env, "all")) { // testing: every owner a team, whatever its list
+        if (waves > wgs) {
+            waves = wgs;
             if (!build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, waves, owner_depth(), osch))
                 CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule construction failed");
-            // Teams: the leading owners (the hottest rows, alone in their lists) whose list is long enough to bound the epoch run as three
-            // wavefronts in a workgroup of their own instead of one wavefront among four.  A team takes a whole workgroup, so the owner
-            // count shrinks by three per team and the rows are dealt again.
-            h->n_team = 0;
-            int64_t team_min = 8192;
-            const char *team_env = getenv("CMI_OWNER_TEAM");
-            if (const char *env = getenv("CMI_OWNER_TEAM_MIN")) team_min = atoll(env);
-            auto leading_single_hub = [&](const OwnerSchedule &os, int limit) {
-                int t = 0;
-                for (; t < limit && t < (int)os.n_owners(); ++t) {
-                    const int64_t b = os.own_off[(size_t)t], e = os.own_off[(size_t)t + 1];
-                    if (e - b < team_min) break;
-                    bool single = true;
-                    for (int64_t pos = b + 1; pos < e && single; ++pos) single = os.flags[(size_t)pos] & OWN_HUB_FWD;
-                    if (!single) break;
-                }
-                return t;
-            };
-            const int wgs = (waves + 3) / 4; // resident workgroups
-            if (h->strict || (team_env && !strcmp(team_env, "0"))) {
-                // one wavefront per owner throughout (the strict form has no team body; CMI_OWNER_TEAM=0: tests and A/B runs).
-                // (Round 5 also refused teams to sharing instances and to fp64 at k <= 64 because that form was measured inexact beside
-                // another owner epoch.  The cause was a store-data hazard in the record stores of BOTH bodies -- the compiler had merely
-                // happened to reuse the data registers at once only in that instantiation -- fixed in owner_kernels.hip owner_st_words;
-                // tests/test_gpu_soak.py holds every instantiation beside other owner epochs bit for bit.  docs/history/r06.md 1.)
-            } else if (team_env && !strcmp(team_env, "all")) { // testing: every owner a team, whatever its list
-                if (waves > wgs) {
-                    waves = wgs;
-                    if (!build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, waves, owner_depth(), osch))
-                        CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule construction failed");
-                }
-                h->n_team = waves;
-            } else {
-                int t = leading_single_hub(osch, wgs / 2);
-                if (t > 0) {
-                    const int fewer = waves - 3 * t;
-                    if (fewer >= t + 1 && build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, fewer, owner_depth(), osch)) {
-                        waves = fewer;
-                        t = std::min(t, leading_single_hub(osch, t));
-                    } else {
-                        t = 0;
-                        if (!build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, waves, owner_depth(), osch))
-                            CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule construction failed");
-                    }
-                }
-                h->n_team = t;
-            }
-            h->owner = true;
-            h->owner_hub_item = osch.hub_is_item != 0;
-            h->n_owners = waves;
         }
-    }
-    if (h->owner) {
-        h->level_off = {0, n};
-        h->max_level = osch.max_load;
-        h->slot_off = {0, (int64_t)h->n_owners};
-        h->n_slots = h->n_owners;
-        h->sched_levels = 1;
-        sch.perm.swap(osch.perm);
+        h->n_team = waves;
     } else {
-        if (h->serial) {
-            sch.level_off = {0, n};
-            sch.max_level = n;
-            // CAMF_C: conflict-free CRS blocks (consecutive tuples sharing no user and no item, <= 64) -- see sgd_camfc_blocks
-            h->blk_off.clear();
-            if (h->model == CMI_MODEL_CAMF_C && !h->strict && h->k <= 256 && dmax <= 16 && n > 0 && n < ((int64_t)1 << 31) &&
-                camfc_blocks_lds(h->n_conds, dmax, esize(h)) <= 64 * 1024 && !getenv("CMI_NO_CAMFC_BLOCKS")) {
-                std::vector<int32_t> off;
-                build_conflict_free_blocks(n, u, j, h->n_users, h->n_items, 64, off);
-                // shorter runs: the serial wave is faster -- the pipelined one (camfc_pipe.hip, 0.55-0.63 us per tuple at any run length)
-                // breaks even with the block kernel (about 1.3 us per block + 0.28 us per tuple) near 5 tuples per block, the one-ahead
-                // wave near 3 (tests/tools/bench_camfc_paths.py)
-                const double min_run = camfc_pipe_supported(h->k, h->n_conds, dmax) ? 5.0 : 3.0;
-                if ((double)n / (double)(off.size() - 1) >= min_run) h->blk_off.swap(off);
-            }
-        } else if (use_chain) {
-            // hub-chain levels: level_off indexes UNITS; sch.perm carries the stream order
-            sch.perm.swap(csch.perm);
-            sch.level_off = csch.level_off;
-            sch.max_level = csch.max_level_units;
-        } else {
-            int order = LEVEL_ORDER_CRS;
-            if (const char *env = getenv("CMI_LEVEL_ORDER")) {
-                if (!strcmp(env, "item")) order = LEVEL_ORDER_ITEM;
-                else if (!strcmp(env, "user")) order = LEVEL_ORDER_USER;
-                else if (!strcmp(env, "xcd")) order = LEVEL_ORDER_XCD;
-            }
-            if (!build_level_schedule(n, u, j, h->n_users, h->n_items, order, sch))
-                CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: schedule construction failed");
-        }
-#ifdef CMI_TIMING_EXPERIMENTS // never in a release build: merging dependent levels gives WRONG results (boundary-cost timing only)
-        if (const char *env = cmi_exp_env("CMI_DEBUG_MERGE_LEVELS")) {
-            const int m = atoi(env);
-            if (m > 1) {
-                fprintf(stderr, "[cmi] CMI_DEBUG_MERGE_LEVELS=%d: dependent levels merged, results are WRONG (timing experiment)\n", m);
-                std::vector<int64_t> lo;
-                for (size_t i = 0; i + 1 < sch.level_off.size(); i += (size_t)m) lo.push_back(sch.level_off[i]);
-                lo.push_back(sch.level_off.back());
-                sch.level_off = lo;
+        int t = leading_single_hub(osch, wgs / 2);
+        if (t > 0) {
+            const int fewer = waves - 3 * t;
+            if (fewer >= t + 1 && build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, fewer, owner_depth(), osch)) {
+                waves = fewer;
+                t = std::min(t, leading_single_hub(osch, t));
+            } else {
+                t = 0;
+                if (!build_owner_schedule(n, u, j, h->n_users, h->n_items, hub, waves, owner_depth(), osch))
+                    CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule construction failed");
             }
         }
-#endif
-        h->level_off = sch.level_off;
-        h->max_level = sch.max_level;
-        const int64_t n_levels = (int64_t)h->level_off.size() - 1;
-        h->sched_levels = n_levels;
-        // narrow runs (heavy-tailed degrees): every maximal run of >= TAIL_MIN_LEVELS consecutive levels with <= TAIL_MAX
-        // tuples each is walked by ONE single-workgroup launch instead of one launch per level
-        h->tail_len.assign((size_t)n_levels, 0);
-        h->n_launches = 0;
-        if (!h->serial && !h->chain && !cmi_exp_env("CMI_NO_TAIL")) build_narrow_runs(h->level_off, 256, 16, h->tail_len);
-        h->slot_off.assign((size_t)n_levels + 1, 0);
-        for (int64_t l = 0; l < n_levels; ++l) {
-            const int cnt = (int)(h->level_off[(size_t)l + 1] - h->level_off[(size_t)l]);
-            int blocks = h->serial ? 0
-                         : h->chain ? chain_level_blocks(h->k, dmax, h->f64, cnt)
-                         : h->fast ? level_blocks_f32_fast(h->k, cnt)
-                         : h->small ? level_blocks_small(h->k, dmax, cnt)
-                                    : level_blocks_generic(cnt);
-            if (h->tail_len[(size_t)l] > 0) blocks = 1;       // a narrow run owns one loss slot ...
-            else if (h->tail_len[(size_t)l] < 0) blocks = 0;  // ... at its first level
-            if (h->tail_len[(size_t)l] >= 0) ++h->n_launches;
-            h->slot_off[(size_t)l + 1] = h->slot_off[(size_t)l] + blocks;
-        }
-        h->n_slots = h->slot_off[(size_t)n_levels];
-        h->n_tail = 0;
-        for (int32_t t : h->tail_len)
-            if (t > 0) h->n_tail += t;
+        h->n_team = t;
     }
+    h->owner = true;
+    h->owner_hub_item = osch.hub_is_item != 0;
+    h->n_owners = waves;
+    const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
+    h->own_stride = owner_record_stride(h->model, h->k, h->n_conds, h->f64, h->owner_hub_item);
+    const int64_t rec_bytes = h->own_stride * 8;
+    if (((int64_t)n_spokes + h->n_owners) * rec_bytes >= ((int64_t)1 << 32) - 65536)
+        CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule: the record table (%d records of %lld bytes) must stay below 4 GB",
+                 n_spokes, (long long)rec_bytes);
+    h->level_off = {0, n};
+    h->max_level = osch.max_load;
+    h->slot_off = {0, (int64_t)h->n_owners};
+    h->n_slots = h->n_owners;
+    h->sched_levels = 1;
+    sch.perm.swap(osch.perm);
+    return CMI_OK;
+}
 
-    lap("schedule");
-    // tuple stream in schedule order, conditions pre-expanded to [n x dmax] (-1 padded) so the kernels
-    // need no ctx -> condition-list indirection.
-    const int64_t ns = n;
-    const int64_t hs = dev_stream ? 0 : ns; // (the device-built schedule builds the stream on the device too: no host copy of it)
-    HostBuf<int32_t> su((size_t)hs), sj((size_t)hs), sconds((size_t)hs * (size_t)dmax);
-    HostBuf<float> sr32(h->f64 ? 0 : (size_t)hs);
-    HostBuf<double> sr64(h->f64 ? (size_t)hs : 0);
-    // every stream slot is a gather through the schedule's permutation: ranges of slots on the host's cores, the tuple arrays' entries
-    // requested 16 slots ahead
-    if (!dev_stream)
+// stage 4a: the levels of the serial, hub-chain and plain forms (the serial form: one level in input order, and CAMF_C's
+// conflict-free CRS blocks -- consecutive tuples sharing no user and no item, <= 64 -- see sgd_camfc_blocks)
+static int build_levels(cmi_instance *h, const RatingsIn &in, int dmax, ChainSchedule &csch, LevelSchedule &sch) {
+    const int64_t n = in.n;
+    if (h->serial) {
+        sch.level_off = {0, n};
+        sch.max_level = n;
+        h->blk_off.clear();
+        if (h->model == CMI_MODEL_CAMF_C && !h->strict && h->k <= 256 && dmax <= 16 && n > 0 && n < ((int64_t)1 << 31) &&
+            camfc_blocks_lds(h->n_conds, dmax, esize(h)) <= 64 * 1024 && !getenv("CMI_NO_CAMFC_BLOCKS")) {
+            std::vector<int32_t> off;
+            build_conflict_free_blocks(n, in.u, in.j, h->n_users, h->n_items, 64, off);
+            // shorter runs: the serial wave is faster -- the pipelined one (camfc_pipe.hip, 0.55-0.63 us per tuple at any run length)
+            // breaks even with the block kernel (about 1.3 us per block + 0.28 us per tuple) near 5 tuples per block, the one-ahead
+            // wave near 3 (tests/tools/bench_camfc_paths.py)
+            const double min_run = camfc_pipe_supported(h->k, h->n_conds, dmax) ? 5.0 : 3.0;
+            if ((double)n / (double)(off.size() - 1) >= min_run) h->blk_off.swap(off);
+        }
+    } else if (h->chain) {
+        // hub-chain levels: level_off indexes UNITS; sch.perm carries the stream order
+        sch.perm.swap(csch.perm);
+        sch.level_off = csch.level_off;
+        sch.max_level = csch.max_level_units;
+    } else {
+        int order = LEVEL_ORDER_CRS;
+        if (const char *env = getenv("CMI_LEVEL_ORDER")) {
+            if (!strcmp(env, "item")) order = LEVEL_ORDER_ITEM;
+            else if (!strcmp(env, "user")) order = LEVEL_ORDER_USER;
+            else if (!strcmp(env, "xcd")) order = LEVEL_ORDER_XCD;
+        }
+        if (!build_level_schedule(n, in.u, in.j, h->n_users, h->n_items, order, sch))
+            CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: schedule construction failed");
+    }
+    return CMI_OK;
+}
+
+// stage 4b: the launches and loss slots of the levels.  Narrow runs (heavy-tailed degrees): every maximal run of >= TAIL_MIN_LEVELS
+// consecutive levels with <= TAIL_MAX tuples each is walked by ONE single-workgroup launch instead of one launch per level.
+static void level_slots(cmi_instance *h, int dmax, const LevelSchedule &sch) {
+    h->level_off = sch.level_off;
+    h->max_level = sch.max_level;
+    const int64_t n_levels = (int64_t)h->level_off.size() - 1;
+    h->sched_levels = n_levels;
+    h->tail_len.assign((size_t)n_levels, 0);
+    h->n_launches = 0;
+    if (!h->serial && !h->chain) build_narrow_runs(h->level_off, 256, 16, h->tail_len);
+    h->slot_off.assign((size_t)n_levels + 1, 0);
+    for (int64_t l = 0; l < n_levels; ++l) {
+        const int cnt = (int)(h->level_off[(size_t)l + 1] - h->level_off[(size_t)l]);
+        int blocks = h->serial ? 0
+                     : h->chain ? chain_level_blocks(h->k, dmax, h->f64, cnt)
+                     : h->fast ? level_blocks_f32_fast(h->k, cnt)
+                     : h->small ? level_blocks_small(h->k, dmax, cnt)
+                                : level_blocks_generic(cnt);
+        if (h->tail_len[(size_t)l] > 0) blocks = 1;       // a narrow run owns one loss slot ...
+        else if (h->tail_len[(size_t)l] < 0) blocks = 0;  // ... at its first level
+        if (h->tail_len[(size_t)l] >= 0) ++h->n_launches;
+        h->slot_off[(size_t)l + 1] = h->slot_off[(size_t)l] + blocks;
+    }
+    h->n_slots = h->slot_off[(size_t)n_levels];
+    h->n_tail = 0;
+    for (int32_t t : h->tail_len)
+        if (t > 0) h->n_tail += t;
+}
+
+// stage 5a: the tuple stream in schedule order on the host, conditions pre-expanded to [n x dmax] (-1 padded) so the kernels need no
+// ctx -> condition-list indirection.  Every stream slot is a gather through the schedule's permutation: ranges of slots on the host's
+// cores, the tuple arrays' entries requested 16 slots ahead.
+static void gather_stream(const cmi_instance *h, const RatingsIn &in, int dmax, const LevelSchedule &sch, HostStream &hs) {
+    const int64_t ns = in.n;
+    const int32_t *u = in.u, *j = in.j, *ctx = in.ctx;
+    const double *r = in.r;
+    hs.su = HostBuf<int32_t>((size_t)ns);
+    hs.sj = HostBuf<int32_t>((size_t)ns);
+    hs.sconds = HostBuf<int32_t>((size_t)ns * (size_t)dmax);
+    hs.sr32 = HostBuf<float>(h->f64 ? 0 : (size_t)ns);
+    hs.sr64 = HostBuf<double>(h->f64 ? (size_t)ns : 0);
     parallel_ranges(ns, host_threads(ns), [&](int, int64_t s0, int64_t s1) {
         for (int64_t s = s0; s < s1; ++s) {
             if (!h->serial && s + 16 < s1) {
@@ -890,37 +880,43 @@ static int set_ratings_impl(cmi_handle h, int64_t n, const int32_t *u, const int
                 }
             }
             const int64_t t = h->serial ? s : sch.perm[(size_t)s];
-            int32_t *row = dmax > 0 ? &sconds[(size_t)s * (size_t)dmax] : nullptr;
+            int32_t *row = dmax > 0 ? &hs.sconds[(size_t)s * (size_t)dmax] : nullptr;
             if (t < 0) { // padding slot
-                su[(size_t)s] = -1;
-                sj[(size_t)s] = 0;
-                if (h->f64) sr64[(size_t)s] = 0.0;
-                else sr32[(size_t)s] = 0.f;
+                hs.su[(size_t)s] = -1;
+                hs.sj[(size_t)s] = 0;
+                if (h->f64) hs.sr64[(size_t)s] = 0.0;
+                else hs.sr32[(size_t)s] = 0.f;
                 for (int d = 0; d < dmax; ++d) row[d] = -1;
                 continue;
             }
-            su[(size_t)s] = u[t];
-            sj[(size_t)s] = j[t];
-            if (h->f64) sr64[(size_t)s] = r[t];
-            else sr32[(size_t)s] = (float)r[t];
+            hs.su[(size_t)s] = u[t];
+            hs.sj[(size_t)s] = j[t];
+            if (h->f64) hs.sr64[(size_t)s] = r[t];
+            else hs.sr32[(size_t)s] = (float)r[t];
             if (dmax > 0) {
-                const int32_t b = ctx_ptr[ctx[t]], e = ctx_ptr[ctx[t] + 1];
+                const int32_t b = in.ctx_ptr[ctx[t]], e = in.ctx_ptr[ctx[t] + 1];
                 int d = 0;
-                for (int32_t q = b; q < e; ++q) row[d++] = ctx_conds[q];
+                for (int32_t q = b; q < e; ++q) row[d++] = in.ctx_conds[q];
                 for (; d < dmax; ++d) row[d] = -1;
             }
         }
     });
-    lap("stream");
+}
+
+// stage 5b: the stream and the context table on the device -- the host stream uploaded, or (dev_stream: the device-built schedule)
+// the stream built on the device from the tuple ids and the permutation it kept -- and the hub-chain units
+static hipError_t upload_stream(cmi_instance *h, const RatingsIn &in, int dmax, bool dev_stream, const HostStream &hs,
+                                ChainDeviceKeep &keep, const ChainSchedule &csch) {
+    const int64_t ns = in.n;
     hipError_t e = hipSuccess;
     if (!dev_stream) {
-        e = upload((void **)&h->d_su, su, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_sj, sj, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_sconds, sconds, h->stream);
-        if (e == hipSuccess) e = h->f64 ? upload(&h->d_sr, sr64, h->stream) : upload(&h->d_sr, sr32, h->stream);
+        e = upload((void **)&h->d_su, hs.su, h->stream);
+        if (e == hipSuccess) e = upload((void **)&h->d_sj, hs.sj, h->stream);
+        if (e == hipSuccess) e = upload((void **)&h->d_sconds, hs.sconds, h->stream);
+        if (e == hipSuccess) e = h->f64 ? upload(&h->d_sr, hs.sr64, h->stream) : upload(&h->d_sr, hs.sr32, h->stream);
     }
-    if (e == hipSuccess && contextual) {
-        std::vector<int32_t> cp(ctx_ptr, ctx_ptr + n_ctx + 1), cc(ctx_conds, ctx_conds + ctx_ptr[n_ctx]);
+    if (e == hipSuccess && !is_2d_model(h->model)) {
+        std::vector<int32_t> cp(in.ctx_ptr, in.ctx_ptr + in.n_ctx + 1), cc(in.ctx_conds, in.ctx_conds + in.ctx_ptr[in.n_ctx]);
         h->ctx_nnz = (int64_t)cc.size();
         e = upload((void **)&h->d_ctx_ptr, cp, h->stream);
         if (e == hipSuccess) e = upload((void **)&h->d_ctx_conds, cc, h->stream);
@@ -932,178 +928,248 @@ static int set_ratings_impl(cmi_handle h, int64_t n, const int32_t *u, const int
         if (e == hipSuccess && dmax > 0) e = hipMalloc((void **)&h->d_sconds, (size_t)ns * (size_t)dmax * 4);
         if (e == hipSuccess) e = hipMalloc(&h->d_sr, (size_t)ns * esize(h));
         if (e == hipSuccess)
-            e = (hipError_t)stream_build_device(h->stream, ns, keep.d_u, keep.d_j, keep.d_perm, ctx, r, h->d_ctx_ptr, h->d_ctx_conds, dmax, h->f64, h->d_su,
-                                                h->d_sj, h->d_sconds, h->d_sr);
+            e = (hipError_t)stream_build_device(h->stream, ns, keep.d_u, keep.d_j, keep.d_perm, in.ctx, in.r, h->d_ctx_ptr, h->d_ctx_conds, dmax,
+                                                h->f64, h->d_su, h->d_sj, h->d_sconds, h->d_sr);
     }
     free_keep(keep);
     if (e == hipSuccess && h->chain) e = upload((void **)&h->d_unit_off, csch.unit_off, h->stream);
-    lap("uploads");
-    if (e == hipSuccess && h->chain && !(h->flags & CMI_FLAG_NO_ARENA) && !cmi_exp_env("CMI_NO_ARENA") && h->k >= 64 && h->k % (h->f64 ? 2 : 4) == 0) {
-        // Spoke arena (SgdArgs::arena): worth its memory when the spoke table is large -- random 512-B rows over >= 2 GiB run at ~0.5 of
-        // the HBM peak (address-translation misses, DRAM page misses), sequential reads + random full-line writes at ~0.7
-        // (tools/micro/row_bias.hip: 4.10 vs 5.73 TB/s) -- and smaller tables gain nothing (5.58 vs 5.61).
-        const int64_t spokes = h->chain_hub_item ? h->n_users : h->n_items;
-        const size_t table_bytes = (size_t)spokes * (size_t)h->k * esize(h), arena_bytes = (size_t)n * (size_t)h->k * esize(h);
-        size_t free_b = 0, total_b = 0;
-        (void)hipMemGetInfo(&free_b, &total_b);
-        // the arena allocated at the top of the call is already OUT of free_b: count it back, or the 0.6 / 0.3 limits below would apply
-        // to (free - arena) and an arena between 0.375 and 0.6 of the free memory -- north_star's 102 GB on 288 GB is within 1 % of that
-        // edge -- would be allocated, judged too large, freed again and the run would silently take the table form
-        if (spec.ptr && spec.bytes == arena_bytes) free_b += spec.bytes;
-        const bool forced = (h->flags & CMI_FLAG_SPOKE_ARENA) || cmi_exp_env("CMI_ARENA");
-        const bool large = table_bytes >= ((size_t)2 << 30) && (double)arena_bytes <= 0.6 * (double)free_b;
-        // In between (spoke tables of 256 MiB .. 2 GiB: BASELINE C5's share has a 1-GiB Q) the better form depends on the BOX: the same
-        // library measures the arena 9 % faster on some MI355X boxes of the pool and 4 % slower on others.  There
-        // the arena is built and the first training call times one epoch of each form at learning rate 0 (which leaves every parameter
-        // as it is) and keeps the faster one (arena_probe below).  CMI_ARENA_PROBE=1 forces the probe at any size (tests), =0 disables it.
-        const char *pe = getenv("CMI_ARENA_PROBE");
-        // (not under CMI_FLAG_STRICT unless asked for: the probe's rate-0 epochs turn a -0.0 parameter into +0.0, a bit-level drift the
-        // strict path promises not to have; strict instances in that range keep the table form)
-        const bool probe = !forced && !large && (pe ? atoi(pe) != 0 : (!h->strict && table_bytes >= ((size_t)256 << 20) && (double)arena_bytes <= 0.3 * (double)free_b));
-        h->arena_probe = false;
-        if (forced || large || probe) {
-            // next_pos[p] = stream position of the next tuple of the same spoke row (its tuples sit in ascending levels, hence ascending
-            // positions); the last one wraps to the first: that is where the row waits for the next epoch
-            // on the device out of the uploaded stream (sched_device.hip arena_positions_device: a stable sort of the positions by spoke
-            // row); the host walk (0.5 s for C3's 50 M tuples) only if that fails
-            e = hipMalloc((void **)&h->d_next, (size_t)n * 4);
-            if (e == hipSuccess) e = hipMalloc((void **)&h->d_first, (size_t)spokes * 4);
-            if (e == hipSuccess && (hipError_t)arena_positions_device(h->stream, n, h->chain_hub_item ? h->d_su : h->d_sj, spokes, h->d_next, h->d_first) != hipSuccess) {
-                (void)hipGetLastError();
-                HostBuf<int32_t> nxt((size_t)n), first((size_t)spokes), back(dev_stream ? (size_t)n : 0);
-                if (dev_stream) { // the stream exists on the device only: the spoke ids come back for the host walk
-                    e = hipMemcpyAsync(back.data(), h->chain_hub_item ? h->d_su : h->d_sj, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-                }
-                if (e == hipSuccess) { // (a failed copy-back must not be walked over, nor its error overwritten: ADVICE r5)
-                    const HostBuf<int32_t> &sp = dev_stream ? back : (h->chain_hub_item ? su : sj);
-                    arena_positions(n, sp.data(), spokes, nxt.data(), first.data());
-                    e = hipMemcpyAsync(h->d_next, nxt.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-                }
-                if (e == hipSuccess) e = hipMemcpyAsync(h->d_first, first.data(), (size_t)spokes * 4, hipMemcpyHostToDevice, h->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // nxt / first are locals
-            }
-            if (e == hipSuccess) {
-                h->d_arena = spec.take(arena_bytes); // allocated at the top of the call (clean memory), if the sizes had announced it
-                if (!h->d_arena) e = hipMalloc(&h->d_arena, arena_bytes);
-            }
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // nxt / first are locals
-            if (e == hipSuccess) {
-                h->arena_on = true;
-                h->arena_valid = false;
-                h->table_valid = true;
-                h->arena_which = h->chain_hub_item ? CMI_STATE_P : CMI_STATE_Q;
-                h->arena_probe = probe;
-                h->arena_probe_table = pe && atoi(pe) < 0; // (CMI_ARENA_PROBE=-1: tests force the "table wins" verdict)
-            } else if (!forced) { // not enough memory after all: run without
-                (void)hipGetLastError();
-                for (void **q : {(void **)&h->d_arena, (void **)&h->d_next, (void **)&h->d_first})
-                    if (*q) {
-                        hipFree(*q);
-                        *q = nullptr;
-                    }
-                e = hipSuccess;
-            }
+    return e;
+}
+
+// stage 6: the spoke arena of the hub-chain schedule (SgdArgs::arena): worth its memory when the spoke table is large -- random 512-B
+// rows over >= 2 GiB run at ~0.5 of the HBM peak (address-translation misses, DRAM page misses), sequential reads + random full-line
+// writes at ~0.7 (tools/micro/row_bias.hip: 4.10 vs 5.73 TB/s) -- and smaller tables gain nothing (5.58 vs 5.61).
+static hipError_t setup_arena(cmi_instance *h, int64_t n, bool dev_stream, const HostStream &hs, SpecArena &spec) {
+    if (!h->chain || !arena_kernel_ok(h)) return hipSuccess;
+    const int64_t spokes = h->chain_hub_item ? h->n_users : h->n_items;
+    const size_t table_bytes = (size_t)spokes * (size_t)h->k * esize(h), arena_bytes = (size_t)n * (size_t)h->k * esize(h);
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    // the speculative arena is already OUT of free_b: count it back, or the 0.6 / 0.3 limits below would apply to (free - arena) and an
+    // arena between 0.375 and 0.6 of the free memory -- north_star's 102 GB on 288 GB is within 1 % of that edge -- would be
+    // allocated, judged too large, freed again and the run would silently take the table form
+    if (spec.ptr && spec.bytes == arena_bytes) free_b += spec.bytes;
+    const bool forced = h->flags & CMI_FLAG_SPOKE_ARENA;
+    const bool large = table_bytes >= ((size_t)2 << 30) && (double)arena_bytes <= 0.6 * (double)free_b;
+    // In between (spoke tables of 256 MiB .. 2 GiB: BASELINE C5's share has a 1-GiB Q) the better form depends on the BOX: the same
+    // library measures the arena 9 % faster on some MI355X boxes of the pool and 4 % slower on others.  There
+    // the arena is built and the first training call times one epoch of each form at learning rate 0 (which leaves every parameter
+    // as it is) and keeps the faster one (arena_probe below).  CMI_ARENA_PROBE=1 forces the probe at any size (tests), =0 disables it.
+    const char *pe = getenv("CMI_ARENA_PROBE");
+    // (not under CMI_FLAG_STRICT unless asked for: the probe's rate-0 epochs turn a -0.0 parameter into +0.0, a bit-level drift the
+    // strict path promises not to have; strict instances in that range keep the table form)
+    const bool probe = !forced && !large && (pe ? atoi(pe) != 0 : (!h->strict && table_bytes >= ((size_t)256 << 20) && (double)arena_bytes <= 0.3 * (double)free_b));
+    h->arena_probe = false;
+    if (!forced && !large && !probe) return hipSuccess;
+    // next_pos[p] = stream position of the next tuple of the same spoke row (its tuples sit in ascending levels, hence ascending
+    // positions); the last one wraps to the first: that is where the row waits for the next epoch
+    // on the device out of the uploaded stream (sched_device.hip arena_positions_device: a stable sort of the positions by spoke
+    // row); the host walk (0.5 s for C3's 50 M tuples) only if that fails
+    const int32_t *d_spoke = h->chain_hub_item ? h->d_su : h->d_sj;
+    hipError_t e = hipMalloc((void **)&h->d_next, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_first, (size_t)spokes * 4);
+    if (e == hipSuccess && (hipError_t)arena_positions_device(h->stream, n, d_spoke, spokes, h->d_next, h->d_first) != hipSuccess) {
+        (void)hipGetLastError();
+        HostBuf<int32_t> nxt((size_t)n), first((size_t)spokes), back(dev_stream ? (size_t)n : 0);
+        if (dev_stream) { // the stream exists on the device only: the spoke ids come back for the host walk
+            e = hipMemcpyAsync(back.data(), d_spoke, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
+        if (e == hipSuccess) { // (a failed copy-back must not be walked over, nor its error overwritten: ADVICE r5)
+            const HostBuf<int32_t> &sp = dev_stream ? back : (h->chain_hub_item ? hs.su : hs.sj);
+            arena_positions(n, sp.data(), spokes, nxt.data(), first.data());
+            e = hipMemcpyAsync(h->d_next, nxt.data(), (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(h->d_first, first.data(), (size_t)spokes * 4, hipMemcpyHostToDevice, h->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // nxt / first are locals
     }
-    lap("arena");
-    if (e == hipSuccess && h->owner) {
-        const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
-        h->own_stride = owner_record_stride(h->model, h->k, h->n_conds, h->f64, h->owner_hub_item);
-        const int64_t rec_bytes = h->own_stride * 8;
-        if (((int64_t)n_spokes + h->n_owners) * rec_bytes >= ((int64_t)1 << 32) - 65536) {
-            free_ratings(h);
-            CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: owner schedule: the record table (%d records of %lld bytes) must stay below 4 GB",
-                     n_spokes, (long long)rec_bytes);
+    if (e == hipSuccess) {
+        h->d_arena = spec.take(arena_bytes); // allocated ahead of the schedule build (clean memory), if the sizes had announced it
+        if (!h->d_arena) e = hipMalloc(&h->d_arena, arena_bytes);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) {
+        h->arena_on = true;
+        h->arena_valid = false;
+        h->table_valid = true;
+        h->arena_which = h->chain_hub_item ? CMI_STATE_P : CMI_STATE_Q;
+        h->arena_probe = probe;
+        h->arena_probe_table = pe && atoi(pe) < 0; // (CMI_ARENA_PROBE=-1: tests force the "table wins" verdict)
+    } else if (!forced) { // not enough memory after all: run without
+        (void)hipGetLastError();
+        release_arena(h);
+        e = hipSuccess;
+    }
+    return e;
+}
+
+// stage 7: the owners' records in list order.  Every owner's list is followed by 2 x depth inert entries (OWN_NOP) on the owner's dummy
+// record behind the table: the kernel runs whole rounds of up to `depth` steps and reads entries depth + 1 places ahead, unchecked.
+static hipError_t pack_owner_records(cmi_instance *h, const RatingsIn &in, const OwnerSchedule &osch, const LevelSchedule &sch) {
+    const int64_t n = in.n;
+    const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
+    const int64_t rec_bytes = h->own_stride * 8;
+    const int pad = 2 * owner_depth();
+    const int ncw = owner_mask_words(h->model, h->n_conds);
+    const size_t rb = owner_rec_bytes(ncw);   // OwnerRecT<ncw>: {off, hub, want, flags, rating, mask[ncw]}
+    std::vector<uint64_t> recs(((size_t)n + (size_t)h->n_owners * (size_t)pad) * (rb / 8), 0);
+    auto put = [&](int64_t pos, uint32_t off, int32_t hub, uint32_t want, uint32_t flags, double rating, const uint64_t *mask) {
+        unsigned char *q = reinterpret_cast<unsigned char *>(recs.data()) + (size_t)pos * rb;
+        memcpy(q, &off, 4);
+        memcpy(q + 4, &hub, 4);
+        memcpy(q + 8, &want, 4);
+        memcpy(q + 12, &flags, 4);
+        if (h->f64) memcpy(q + 16, &rating, 8);
+        else {
+            const float rf = (float)rating;
+            memcpy(q + 16, &rf, 4);
         }
-        // every owner's list is followed by 2 x depth inert entries (OWN_NOP) on the owner's dummy record behind the table: the kernel
-        // runs whole rounds of up to `depth` steps and reads entries depth + 1 places ahead, unchecked
-        const int pad = 2 * owner_depth();
-        const int ncw = owner_mask_words(h->model, h->n_conds);
-        const size_t rb = owner_rec_bytes(ncw);   // OwnerRecT<ncw>: {off, hub, want, flags, rating, mask[ncw]}
-        std::vector<uint64_t> recs(((size_t)n + (size_t)h->n_owners * (size_t)pad) * (rb / 8), 0);
-        auto put = [&](int64_t pos, uint32_t off, int32_t hub, uint32_t want, uint32_t flags, double rating, const uint64_t *mask) {
-            unsigned char *q = reinterpret_cast<unsigned char *>(recs.data()) + (size_t)pos * rb;
-            memcpy(q, &off, 4);
-            memcpy(q + 4, &hub, 4);
-            memcpy(q + 8, &want, 4);
-            memcpy(q + 12, &flags, 4);
-            if (h->f64) memcpy(q + 16, &rating, 8);
-            else {
-                const float rf = (float)rating;
-                memcpy(q + 16, &rf, 4);
-            }
-            if (mask) memcpy(q + 24, mask, 8 * (size_t)ncw);
-        };
-        int64_t out = 0;
-        int32_t w = 0;
-        auto nop = [&](int32_t owner) {
-            put(out++, (uint32_t)(((int64_t)n_spokes + owner) * rec_bytes), 0, 0, OWN_HUB_FWD | OWN_SPK_FWD | OWN_NOP, 0.0, nullptr);
-        };
-        for (; w < h->n_owners && osch.own_off[(size_t)w + 1] == 0; ++w) // owners without tuples ahead of the first list
+        if (mask) memcpy(q + 24, mask, 8 * (size_t)ncw);
+    };
+    int64_t out = 0;
+    int32_t w = 0;
+    auto nop = [&](int32_t owner) {
+        put(out++, (uint32_t)(((int64_t)n_spokes + owner) * rec_bytes), 0, 0, OWN_HUB_FWD | OWN_SPK_FWD | OWN_NOP, 0.0, nullptr);
+    };
+    for (; w < h->n_owners && osch.own_off[(size_t)w + 1] == 0; ++w) // owners without tuples ahead of the first list
+        for (int i = 0; i < pad; ++i) nop(w);
+    for (int64_t s = 0; s < n; ++s) {
+        const int64_t t = sch.perm[(size_t)s];
+        uint64_t mask[6] = {0, 0, 0, 0, 0, 0};
+        if (!is_2d_model(h->model))
+            for (int32_t c = in.ctx_ptr[in.ctx[t]]; c < in.ctx_ptr[in.ctx[t] + 1]; ++c) mask[in.ctx_conds[c] >> 6] |= (uint64_t)1 << (in.ctx_conds[c] & 63);
+        put(out++, (uint32_t)((int64_t)(h->owner_hub_item ? in.u[t] : in.j[t]) * rec_bytes), h->owner_hub_item ? in.j[t] : in.u[t], osch.want[(size_t)s],
+            osch.flags[(size_t)s], in.r[t], mask);
+        while (w < h->n_owners && s + 1 == osch.own_off[(size_t)w + 1]) { // the end of owner w's list (and of empty owners after it)
             for (int i = 0; i < pad; ++i) nop(w);
-        for (int64_t s = 0; s < n; ++s) {
-            const int64_t t = sch.perm[(size_t)s];
-            uint64_t mask[6] = {0, 0, 0, 0, 0, 0};
-            if (contextual)
-                for (int32_t c = ctx_ptr[ctx[t]]; c < ctx_ptr[ctx[t] + 1]; ++c) mask[ctx_conds[c] >> 6] |= (uint64_t)1 << (ctx_conds[c] & 63);
-            put(out++, (uint32_t)((int64_t)(h->owner_hub_item ? u[t] : j[t]) * rec_bytes), h->owner_hub_item ? j[t] : u[t], osch.want[(size_t)s],
-                osch.flags[(size_t)s], r[t], mask);
-            while (w < h->n_owners && s + 1 == osch.own_off[(size_t)w + 1]) { // the end of owner w's list (and of empty owners after it)
-                for (int i = 0; i < pad; ++i) nop(w);
-                ++w;
-            }
+            ++w;
         }
-        for (; w < h->n_owners; ++w) // owners without tuples (n == 0 never gets here)
-            for (int i = 0; i < pad; ++i) nop(w);
-        e = upload((void **)&h->d_own_recs, recs, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_own_off, osch.own_off, h->stream);
-        if (e == hipSuccess) e = hipMalloc(&h->d_tagged, ((size_t)n_spokes + (size_t)h->n_owners) * (size_t)h->own_stride * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&h->d_flow_err, 16);
-        if (e == hipSuccess) e = hipMemsetAsync(h->d_flow_err, 0, 16, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // recs is a local
     }
-    if (e == hipSuccess && h->model == CMI_MODEL_SVDPP) {
-        // userItemsCache = train.rowColumnsCache (SVDPlusPlus.java:52): the items of every user in the 2-D train matrix, ascending
-        std::vector<int32_t> ptr((size_t)h->n_users + 1, 0), items((size_t)n);
-        for (int64_t t = 0; t < n; ++t) ptr[(size_t)u[t] + 1]++;
-        for (int32_t x = 0; x < h->n_users; ++x) ptr[(size_t)x + 1] += ptr[(size_t)x];
-        {
-            std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
-            for (int64_t t = 0; t < n; ++t) items[(size_t)cur[(size_t)u[t]]++] = j[t];
-        }
-        for (int32_t x = 0; x < h->n_users; ++x) std::sort(items.begin() + ptr[(size_t)x], items.begin() + ptr[(size_t)x + 1]);
-        e = upload((void **)&h->d_ui_ptr, ptr, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_ui_items, items, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // ptr/items are locals
+    for (; w < h->n_owners; ++w) // owners without tuples (n == 0 never gets here)
+        for (int i = 0; i < pad; ++i) nop(w);
+    hipError_t e = upload((void **)&h->d_own_recs, recs, h->stream);
+    if (e == hipSuccess) e = upload((void **)&h->d_own_off, osch.own_off, h->stream);
+    if (e == hipSuccess) e = hipMalloc(&h->d_tagged, ((size_t)n_spokes + (size_t)h->n_owners) * (size_t)h->own_stride * 8);
+    if (e == hipSuccess) e = hipMalloc((void **)&h->d_flow_err, 16);
+    if (e == hipSuccess) e = hipMemsetAsync(h->d_flow_err, 0, 16, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // recs is a local
+    return e;
+}
+
+// stage 8: userItemsCache = train.rowColumnsCache (SVDPlusPlus.java:52): the items of every user in the 2-D train matrix, ascending
+static hipError_t build_user_items(cmi_instance *h, const RatingsIn &in) {
+    const int64_t n = in.n;
+    std::vector<int32_t> ptr((size_t)h->n_users + 1, 0), items((size_t)n);
+    for (int64_t t = 0; t < n; ++t) ptr[(size_t)in.u[t] + 1]++;
+    for (int32_t x = 0; x < h->n_users; ++x) ptr[(size_t)x + 1] += ptr[(size_t)x];
+    {
+        std::vector<int32_t> cur(ptr.begin(), ptr.end() - 1);
+        for (int64_t t = 0; t < n; ++t) items[(size_t)cur[(size_t)in.u[t]]++] = in.j[t];
     }
-    if (e == hipSuccess && h->n_slots > 0) {
+    for (int32_t x = 0; x < h->n_users; ++x) std::sort(items.begin() + ptr[(size_t)x], items.begin() + ptr[(size_t)x + 1]);
+    hipError_t e = upload((void **)&h->d_ui_ptr, ptr, h->stream);
+    if (e == hipSuccess) e = upload((void **)&h->d_ui_items, items, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // ptr/items are locals
+    return e;
+}
+
+// stage 9: the loss slots, CAMF_C's block offsets and the narrow runs' level offsets on the device
+static hipError_t alloc_launch_buffers(cmi_instance *h) {
+    hipError_t e = hipSuccess;
+    if (h->n_slots > 0) {
         // zeroed: a launch shape that writes fewer slots than were reserved must not feed garbage into the loss
         e = hipMalloc((void **)&h->d_loss_part, (size_t)h->n_slots * sizeof(double));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_loss_part, 0, (size_t)h->n_slots * sizeof(double), h->stream);
     }
-    if (e == hipSuccess && !h->blk_off.empty()) {
-        e = hipMalloc((void **)&h->d_blk_off, h->blk_off.size() * sizeof(int32_t));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(h->d_blk_off, h->blk_off.data(), h->blk_off.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
-    }
-    if (e == hipSuccess && h->n_tail > 0) { // the tail launches read their level offsets from the device
-        e = hipMalloc((void **)&h->d_tail_off, h->level_off.size() * sizeof(int64_t));
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(h->d_tail_off, h->level_off.data(), h->level_off.size() * sizeof(int64_t), hipMemcpyHostToDevice,
-                               h->stream);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        free_ratings(h);
-        CMI_FAIL(h, CMI_E_HIP, "set_ratings: upload failed: %s", hipGetErrorString(e));
-    }
-    lap("rest");
+    if (e == hipSuccess && !h->blk_off.empty()) e = upload((void **)&h->d_blk_off, h->blk_off, h->stream);
+    if (e == hipSuccess && h->n_tail > 0) e = upload((void **)&h->d_tail_off, h->level_off, h->stream); // the tail launches read their level offsets from the device
+    return e;
+}
+
+// The stages of cmi_set_ratings, run once each in this order.  Their order constraints:
+//  - the speculative arena is allocated before anything this call frees (the schedule build's temporaries: SpecArena);
+//  - the ChainDeviceKeep of a device-built schedule is released after the device stream build and before the arena;
+//  - every host buffer an async copy reads is synchronised before it goes out of scope (the host stream lives to the end of the
+//    call, whose last step synchronises; the stages' own locals are synchronised inside them);
+//  - on any failure the exit goes through free_ratings (set_ratings_impl), which leaves have_ratings == false.
+// CMI_SETUP_TIMES=1: the wall time of every phase on stderr (tools/exp/setup_time.py reads these names).
+static int build_ratings(cmi_instance *h, const RatingsIn &in) {
+    const bool times = getenv("CMI_SETUP_TIMES") != nullptr;
+    auto T0 = std::chrono::steady_clock::now();
+    auto lap = [&](const char *w) {
+        if (!times) return;
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "set_ratings %s %.3f s\n", w, std::chrono::duration<double>(t - T0).count());
+        T0 = t;
+    };
+    const int64_t n = in.n;
+    int dmax = 0;
+    if (int rc = validate_ratings(h, in, dmax)) return rc;
+    lap("validate");
     h->n = n;
-    h->tuple_bytes = h->owner ? (ns + (int64_t)h->n_owners * 2 * owner_depth()) * (int64_t)owner_rec_bytes(owner_mask_words(h->model, h->n_conds))
-                              : ns * (8 + (int64_t)esize(h) + 4 * (int64_t)dmax + 0) + (h->chain ? 4 * (h->n_units + 1) : 0) + (h->arena_on ? 4 * ns : 0);
+    h->n_ctx = is_2d_model(h->model) ? 0 : in.n_ctx;
+    h->dmax = dmax;
+
+    bool chain_ok = false;
+    if (int rc = check_schedule_flags(h, dmax, chain_ok)) return rc;
+    SpecArena spec;
+    speculative_arena(h, n, chain_ok, spec);
+    lap("arena allocation");
+    LevelSchedule sch;
+    ChainSchedule csch;
+    OwnerSchedule osch;
+    ChainDeviceKeep keep; // device-built schedule: the tuple ids and the permutation stay on the device for the stream build
+    if (choose_schedule(h, in, chain_ok, csch, keep))
+        if (int rc = build_owner_lists(h, in, osch, sch)) return rc;
+    if (!h->owner) {
+        if (int rc = build_levels(h, in, dmax, csch, sch)) return rc;
+        level_slots(h, dmax, sch);
+    }
+    lap("schedule");
+    const bool dev_stream = h->chain && keep.d_perm != nullptr; // (the device-built schedule builds the stream on the device too)
+    HostStream hs;
+    if (!dev_stream) gather_stream(h, in, dmax, sch, hs);
+    lap("stream");
+    hipError_t e = upload_stream(h, in, dmax, dev_stream, hs, keep, csch);
+    lap("uploads");
+    if (e == hipSuccess) e = setup_arena(h, n, dev_stream, hs, spec);
+    lap("arena");
+    if (e == hipSuccess && h->owner) e = pack_owner_records(h, in, osch, sch);
+    if (e == hipSuccess && h->model == CMI_MODEL_SVDPP) e = build_user_items(h, in);
+    if (e == hipSuccess) e = alloc_launch_buffers(h);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) CMI_FAIL(h, CMI_E_HIP, "set_ratings: upload failed: %s", hipGetErrorString(e));
+    lap("rest");
+    h->tuple_bytes = h->owner ? (n + (int64_t)h->n_owners * 2 * owner_depth()) * (int64_t)owner_rec_bytes(owner_mask_words(h->model, h->n_conds))
+                              : n * (8 + (int64_t)esize(h) + 4 * (int64_t)dmax + 0) + (h->chain ? 4 * (h->n_units + 1) : 0) + (h->arena_on ? 4 * n : 0);
     h->have_ratings = true;
     return CMI_OK;
+}
+
+static int set_ratings_impl(cmi_instance *h, const RatingsIn &in) {
+    if (int rc = check_ratings_args(h, in)) return rc;
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
+    free_ratings(h);
+    const int rc = build_ratings(h, in);
+    if (rc != CMI_OK) free_ratings(h);
+    return rc;
+}
+
+// the exception barrier of the boundary: the schedule construction allocates O(tuples) host memory on the host pool's threads
+// (host_pool.hpp hands a range body's exception to the caller); nothing C++ may cross into a C / JNI / ctypes host
+extern "C" int cmi_set_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
+                               const double *r, int32_t n_ctx, const int32_t *ctx_ptr, const int32_t *ctx_conds) {
+    if (!h) return CMI_E_INVALID;
+    try {
+        return set_ratings_impl(h, RatingsIn{n, u, j, ctx, r, n_ctx, ctx_ptr, ctx_conds});
+    } catch (const std::exception &e) {
+        free_ratings(h);
+        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure: %s", e.what());
+    } catch (...) {
+        free_ratings(h);
+        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure (unknown exception)");
+    }
 }
 
 extern "C" int cmi_schedule_info(cmi_handle h, int64_t info[8]) {
@@ -1450,13 +1516,7 @@ static int arena_probe(cmi_instance *h) {
             hipGraphExecDestroy(h->graph_exec);
             h->graph_exec = nullptr;
         }
-        h->arena_on = h->arena_valid = false;
-        h->table_valid = true;
-        for (void **q : {(void **)&h->d_arena, (void **)&h->d_next, (void **)&h->d_first})
-            if (*q) {
-                hipFree(*q);
-                *q = nullptr;
-            }
+        release_arena(h);
     }
     return CMI_OK;
 }

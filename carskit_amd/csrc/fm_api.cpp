@@ -1,6 +1,5 @@
 // fm_api.cpp -- C ABI of the FM recommender (include/carskit_mi355x.h, cmi_fm_*).
 #include "../../include/carskit_mi355x.h"
-#include "env_knobs.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -56,7 +55,6 @@ struct cmi_fm_instance {
     FmOrderDev ord[3];   // [2] only: the context field (records sorted by feature, a wave per feature)
     FmCellsDev cell[2];  // users, items
     int atomic = 0;  // 0 (default): fm_cell_kernel, parking + a fixed walk, bit-reproducible; 1: CMI_FM_FLAG_RELAXED_SUMS, fm_cell_atomic_kernel (LDS atomics)
-    int h_split = 0; // CMI_FM_HSPLIT: id-range parts per group (0 = chosen from the geometry)
     int batch_cap = FMC_RCAP, slot_cap = FMC_SLOTS; // experiment / test knobs (CMI_FM_BATCH, CMI_FM_SLOTS): smaller batches and blocks on small data
     RankWorkspace rank_ws; // cmi_fm_eval_rankings' buffers, reused by the next evaluation
     ncclComm_t comm = nullptr; // cmi_fm_comm_init: ratings sharded by user over one process per GPU
@@ -149,7 +147,6 @@ extern "C" int cmi_fm_create(int k, int n_users, int n_items, int n_conds, int n
     // the reference's sweep is deterministic (FM.java:148-218): so is the default here; the relaxed (LDS-atomic) sums are an opt-in, and
     // an explicit CMI_FM_FLAG_DETERMINISTIC / CMI_FM_DETERMINISTIC=1 wins over the environment's opt-in
     h->atomic = ((flags & CMI_FM_FLAG_RELAXED_SUMS) || getenv("CMI_FM_RELAXED_SUMS")) && !(flags & CMI_FM_FLAG_DETERMINISTIC) && !getenv("CMI_FM_DETERMINISTIC") ? 1 : 0;
-    if (const char *v = cmi_exp_env("CMI_FM_HSPLIT")) h->h_split = std::max(0, std::min(atoi(v), 8));
     h->k = k;
     h->n_users = n_users;
     h->n_items = n_items;
@@ -285,7 +282,7 @@ struct FmCellsHost {
 // of the gathered field; the records of (block, sub-slice) are a CELL, cut into batches of <= batch_cap records in gathered-id order
 // (records with a context feature last).
 static void fm_build_cells(int64_t n, const int32_t *key, const int32_t *other, const int32_t *ctx, int count, int other_count, int other_base,
-                           int n_conds, int64_t slice_entries, int batch_cap, int slot_cap, int h_split, FmCellsHost &o, bool slot_in_word = false) {
+                           int n_conds, int64_t slice_entries, int batch_cap, int slot_cap, FmCellsHost &o, bool slot_in_word = false) {
     o.count = count;
     const bool times = getenv("CMI_SETUP_TIMES") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
@@ -306,12 +303,11 @@ static void fm_build_cells(int64_t n, const int32_t *key, const int32_t *other, 
     // refined below once the sub-slices are known; a coordinate's records spread evenly over sub-slices only if the gathered ids do)
     int64_t ng_min = std::max<int64_t>(1, (int64_t)std::ceil((double)count / (0.97 * (double)slot_cap)));
     int64_t H = 1, NG = ng_min;
-    if (h_split > 0) H = h_split;
-    else if (ng_min < 256) {
+    if (ng_min < 256) {
         while (H < 8 && ng_min * H * 2 <= 256 && n / (ng_min * H * 2) >= 2048) H *= 2; // fill the CUs, but keep blocks worth a launch
     }
     if (NG * H > 256) NG = (NG * H + 255) / 256 * 256 / H; // whole waves of 256 workgroups
-    else if (NG * H < 256 && h_split <= 0) NG = std::max<int64_t>(NG, std::min<int64_t>(256 / H, n / (2048 * H))); // small inputs: spread, blocks >= 2048 records
+    else if (NG * H < 256) NG = std::max<int64_t>(NG, std::min<int64_t>(256 / H, n / (2048 * H))); // small inputs: spread, blocks >= 2048 records
     NG = std::max<int64_t>(1, std::min<int64_t>(NG, count));
     const int64_t target = std::max<int64_t>(1, (n + NG - 1) / NG); // records per group
     // sub-slices: a cell should fill a batch: n / (NG * H * S) <= 0.93 * batch_cap; 17 bits of id per sub-slice at most
@@ -680,7 +676,7 @@ static int fm_set_ratings_impl(cmi_fm_handle h, int64_t n, const int32_t *u, con
         // the user cells
         std::vector<int32_t> ckey((size_t)n);
         auto item_cells = [&]() {
-            fm_build_cells(n, j, u, ctx, h->n_items, h->n_users, 0, h->n_conds, h->slice_entries, h->batch_cap, h->slot_cap, h->h_split, ci, h->atomic != 0);
+            fm_build_cells(n, j, u, ctx, h->n_items, h->n_users, 0, h->n_conds, h->slice_entries, h->batch_cap, h->slot_cap, ci, h->atomic != 0);
         };
         auto ctx_order = [&]() {
             // context features: only ratings whose context-combination id is < numConditions have one (FM.java:81-86)
@@ -712,7 +708,7 @@ static int fm_set_ratings_impl(cmi_fm_handle h, int64_t n, const int32_t *u, con
             hc = false;
         }
         try {
-            fm_build_cells(n, u, j, ctx, h->n_users, h->n_items, h->n_users, h->n_conds, h->slice_entries, h->batch_cap, h->slot_cap, h->h_split, cu, h->atomic != 0);
+            fm_build_cells(n, u, j, ctx, h->n_users, h->n_items, h->n_users, h->n_conds, h->slice_entries, h->batch_cap, h->slot_cap, cu, h->atomic != 0);
         } catch (...) {
             xu = std::current_exception();
         }

@@ -12,11 +12,10 @@
 //                   item_side = snapshot + bucket / W   (cmi_exchange_apply: the MEAN of the shards' moves)
 //     loss:         all-reduce (sum) of the fp64 epoch losses -> what isConverged()/updateLRate() steer by
 //
-// Shards that share a device (a group of N on ONE GPU: the form the tests run on a single-GPU box) or CMI_GROUP_NO_RCCL=1 use
+// Shards that share a device (a group of N on ONE GPU: the form the tests run on a single-GPU box) use
 // the in-process exchange instead: the buckets are summed in shard order on shard 0's stream and copied back (peer copies) --
 // the same arithmetic, no communicator.
 #include "../../include/carskit_mi355x.h"
-#include "env_knobs.hpp"
 
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -320,7 +319,7 @@ extern "C" int cmi_group_set_ratings(cmi_group_handle g, int64_t n, const int32_
     g->path_note = "in-process exchange (sums on shard 0's stream, peer copies)";
     // CMI_GROUP_TRY_RCCL=1 (test hook): attempt RCCL although shards share a device -- ncclCommInitAll refuses duplicate devices, which
     // drives the fallback below on a single-GPU box (tests/test_gpu_bench_group.py)
-    const bool try_rccl = (distinct || getenv("CMI_GROUP_TRY_RCCL")) && !cmi_exp_env("CMI_GROUP_NO_RCCL");
+    const bool try_rccl = distinct || getenv("CMI_GROUP_TRY_RCCL");
     if (!distinct && !try_rccl) g->path_note += ": shards share a device";
     if (try_rccl) {
         g->comm.assign((size_t)W, nullptr);

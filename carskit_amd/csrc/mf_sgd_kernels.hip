@@ -21,38 +21,12 @@
 // Built with -ffp-contract=off: the JVM never fuses a*b+c, and the strict fp64 path is bit-compared
 // with the CPU oracle.
 #include "mf_sgd_kernels.hpp"
-#include "env_knobs.hpp"
 #include "sgd_device.hpp"
 
 #include <cstdlib>
 #include <cstring>
 
 namespace cmi {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// Device-coherent 16-byte row traffic through raw buffer instructions with cache policy sc0|sc1 (aux 17):
-// compiler-tracked (its own s_waitcnt), unlike inline-asm loads whose destination registers the allocator may
-// copy before a hand-placed wait.  A raw buffer addresses base + 32-bit byte offset: the table must be < 4 GiB
-// (checked on the host; larger models use the level schedule).
-typedef unsigned int u32x4 __attribute__((__vector_size__(16)));
-#define CMI_CPOL_SC0_SC1 17
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t table_rsrc(const void *base) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, 0xffffffff, 0x00020000);
-}
-__device__ __forceinline__ f32x4 ld_row_coherent(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, CMI_CPOL_SC0_SC1));
-}
-__device__ __forceinline__ void st_row_coherent(__amdgpu_buffer_rsrc_t rs, uint32_t byte_off, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), rs, (int)byte_off, 0, CMI_CPOL_SC0_SC1);
-}
-__device__ __forceinline__ float ld_f32_coherent(const float *p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_f32_coherent(float *p, float v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 
 // ---------------------------------------------------------------------------------------------
 // fast path: fp32 state, K = 64*VPL, 16 lanes per tuple
@@ -83,7 +57,7 @@ __device__ __forceinline__ TupleIds load_tuple_ids(const SgdArgs<float> &a, int6
 // Returns the group's loss contribution (valid in lane 0 of the group).  GS = groups that work side by side (16 per
 // 256-thread workgroup of a level launch; 64 in the single 1024-thread workgroup of a narrow-run launch), so that
 // neighbouring groups read neighbouring tuples of the stream.
-template <int MODEL, int VPL, int TPG, bool RAGGED, bool COH, int GS, bool PRE = false>
+template <int MODEL, int VPL, int TPG, bool RAGGED, int GS, bool PRE = false>
 __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64_t begin, int count, int g0, int l16,
                                                   const TupleIds *pre = nullptr) {
     using M = Traits<MODEL>;
@@ -106,9 +80,6 @@ __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64
         cond[i] = t.cond;
     }
 
-    // COH (experiment CMI_LEVEL_COHERENT=1): all model traffic device-coherent (sc0 sc1: write-through stores, L2-bypassing
-    // loads), so a launch leaves no dirty lines in the XCD L2s for the end-of-kernel write-back
-    const __amdgpu_buffer_rsrc_t rsP = table_rsrc(a.P), rsQ = table_rsrc(a.Q);
     float4 *prow[TPG], *qrow[TPG];
     float4 p[TPG][VPL], q[TPG][VPL];
     float bu[TPG], bj[TPG], bic[TPG], buc[TPG];
@@ -123,37 +94,23 @@ __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64
 #pragma unroll
             for (int v = 0; v < VPL; ++v) {
                 p[i][v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!RAGGED || 4 * l16 + 64 * v < K) {
-                    if (COH) {
-                        const f32x4 t = ld_row_coherent(rsP, (uint32_t)(((size_t)uu[i] * K + 4 * l16 + 64 * v) * 4));
-                        p[i][v] = make_float4(t.x, t.y, t.z, t.w);
-                    } else {
-                        p[i][v] = prow[i][v * 16];
-                    }
-                }
+                if (!RAGGED || 4 * l16 + 64 * v < K) p[i][v] = prow[i][v * 16];
             }
 #pragma unroll
             for (int v = 0; v < VPL; ++v) {
                 q[i][v] = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (!RAGGED || 4 * l16 + 64 * v < K) {
-                    if (COH) {
-                        const f32x4 t = ld_row_coherent(rsQ, (uint32_t)(((size_t)jj[i] * K + 4 * l16 + 64 * v) * 4));
-                        q[i][v] = make_float4(t.x, t.y, t.z, t.w);
-                    } else {
-                        q[i][v] = qrow[i][v * 16];
-                    }
-                }
+                if (!RAGGED || 4 * l16 + 64 * v < K) q[i][v] = qrow[i][v * 16];
             }
-            if (M::has_bu) bu[i] = COH ? ld_f32_coherent(a.userBias + uu[i]) : a.userBias[uu[i]];
-            if (M::has_bj) bj[i] = COH ? ld_f32_coherent(a.itemBias + jj[i]) : a.itemBias[jj[i]];
+            if (M::has_bu) bu[i] = a.userBias[uu[i]];
+            if (M::has_bj) bj[i] = a.itemBias[jj[i]];
             if (cond[i] >= 0) {
                 if (M::has_ic) {
                     pic[i] = a.icBias + (size_t)jj[i] * a.n_conds + cond[i];
-                    bic[i] = COH ? ld_f32_coherent(pic[i]) : *pic[i];
+                    bic[i] = *pic[i];
                 }
                 if (M::has_uc) {
                     puc[i] = a.ucBias + (size_t)uu[i] * a.n_conds + cond[i];
-                    buc[i] = COH ? ld_f32_coherent(puc[i]) : *puc[i];
+                    buc[i] = *puc[i];
                 }
             }
         }
@@ -191,24 +148,17 @@ __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64
 
         // scalar biases: lane 0 of the group owns the store
         if (l16 == 0) {
-            if (COH) {
-                if (M::has_bu) st_f32_coherent(a.userBias + uu[i], bu[i] + lr * (e - regB * bu[i]));
-                if (M::has_bj) st_f32_coherent(a.itemBias + jj[i], bj[i] + lr * (e - regB * bj[i]));
-            } else {
-                if (M::has_bu) a.userBias[uu[i]] = bu[i] + lr * (e - regB * bu[i]);
-                if (M::has_bj) a.itemBias[jj[i]] = bj[i] + lr * (e - regB * bj[i]);
-            }
+            if (M::has_bu) a.userBias[uu[i]] = bu[i] + lr * (e - regB * bu[i]);
+            if (M::has_bj) a.itemBias[jj[i]] = bj[i] + lr * (e - regB * bj[i]);
         }
         float ctx_loss = 0.f;
         if (cond[i] >= 0) {
             if (M::has_ic) {
-                if (COH) st_f32_coherent(pic[i], bic[i] + lr * (e - regC * bic[i]));
-                else *pic[i] = bic[i] + lr * (e - regC * bic[i]);
+                *pic[i] = bic[i] + lr * (e - regC * bic[i]);
                 ctx_loss += bic[i] * bic[i];
             }
             if (M::has_uc) {
-                if (COH) st_f32_coherent(puc[i], buc[i] + lr * (e - regC * buc[i]));
-                else *puc[i] = buc[i] + lr * (e - regC * buc[i]);
+                *puc[i] = buc[i] + lr * (e - regC * buc[i]);
                 ctx_loss += buc[i] * buc[i];
             }
         }
@@ -224,16 +174,8 @@ __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64
             CMI_UPD(x) CMI_UPD(y) CMI_UPD(z) CMI_UPD(w)
 #undef CMI_UPD
             if (!RAGGED || 4 * l16 + 64 * v < K) {
-                if (COH) {
-                    f32x4 tp, tq;
-                    tp.x = pn.x, tp.y = pn.y, tp.z = pn.z, tp.w = pn.w;
-                    tq.x = qn.x, tq.y = qn.y, tq.z = qn.z, tq.w = qn.w;
-                    st_row_coherent(rsP, (uint32_t)(((size_t)uu[i] * K + 4 * l16 + 64 * v) * 4), tp);
-                    st_row_coherent(rsQ, (uint32_t)(((size_t)jj[i] * K + 4 * l16 + 64 * v) * 4), tq);
-                } else {
-                    prow[i][v * 16] = pn;
-                    qrow[i][v * 16] = qn;
-                }
+                prow[i][v * 16] = pn;
+                qrow[i][v * 16] = qn;
             }
         }
 
@@ -251,7 +193,7 @@ __device__ __forceinline__ double fast_tuples_f32(const SgdArgs<float> &a, int64
     return gloss;
 }
 
-template <int MODEL, int VPL, int TPG, bool RAGGED = false, bool COH = false>
+template <int MODEL, int VPL, int TPG, bool RAGGED = false>
 __global__ __launch_bounds__(256) void sgd_level_fast_f32(SgdArgs<float> a, int64_t begin, int count,
                                                           int64_t slot0) {
     __shared__ double s_loss[16];
@@ -259,7 +201,7 @@ __global__ __launch_bounds__(256) void sgd_level_fast_f32(SgdArgs<float> a, int6
     const int l16 = tid & 15;
     const int gib = tid >> 4;
     // tuple i of this group: g0 + 16*i (keeps the stream loads coalesced)
-    const double gloss = fast_tuples_f32<MODEL, VPL, TPG, RAGGED, COH, 16>(a, begin, count, blockIdx.x * (16 * TPG) + gib, l16);
+    const double gloss = fast_tuples_f32<MODEL, VPL, TPG, RAGGED, 16>(a, begin, count, blockIdx.x * (16 * TPG) + gib, l16);
     if (l16 == 0) s_loss[gib] = gloss;
     __syncthreads();
     if (tid == 0) {
@@ -596,8 +538,8 @@ __global__ __launch_bounds__(1024) void sgd_tail_fast_f32(SgdArgs<float> a, cons
         const TupleIds cur = next;
         const int64_t e2 = l + 1 < n_tail ? tail_off[l + 2] : e;
         if (l + 1 < n_tail) next = load_tuple_ids<Traits<MODEL>::has_ctx>(a, e, (int)(e2 - e), gib, l16);
-        gl += fast_tuples_f32<MODEL, VPL, 1, RAGGED, false, 64, true>(a, b, cnt, gib, l16, &cur);
-        for (int base = 64; base < cnt; base += 64) gl += fast_tuples_f32<MODEL, VPL, 1, RAGGED, false, 64>(a, b, cnt, base + gib, l16);
+        gl += fast_tuples_f32<MODEL, VPL, 1, RAGGED, 64, true>(a, b, cnt, gib, l16, &cur);
+        for (int base = 64; base < cnt; base += 64) gl += fast_tuples_f32<MODEL, VPL, 1, RAGGED, 64>(a, b, cnt, base + gib, l16);
         b = e;
         e = e2;
         __syncthreads();
@@ -1052,21 +994,9 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs<T> a, int64_t n) {
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
 
-static bool level_coherent() { // experiment: device-coherent model traffic in the level kernel (k = 128, tables < 4 GiB)
-    static const bool on = cmi_exp_env("CMI_LEVEL_COHERENT") != nullptr;
-    return on;
-}
-static int g_fast_tpg = -1;
-static int fast_tpg() { // tuples per 16-lane group (CMI_LEVEL_TPG overrides for experiments)
-    if (g_fast_tpg < 0) {
-        int v = 2;
-        if (const char *env = cmi_exp_env("CMI_LEVEL_TPG")) v = atoi(env);
-        g_fast_tpg = (v == 1 || v == 2 || v == 4) ? v : 2;
-    }
-    return g_fast_tpg;
-}
+constexpr int FAST_TPG = 2; // tuples per 16-lane group of a level launch
 
-int level_blocks_f32_fast(int, int count) { return (count + 16 * fast_tpg() - 1) / (16 * fast_tpg()); }
+int level_blocks_f32_fast(int, int count) { return (count + 16 * FAST_TPG - 1) / (16 * FAST_TPG); }
 int level_blocks_generic(int count) { return (count + 3) / 4; }
 
 bool has_fast_path(int k, int dmax, bool f64, const LaunchCfg &cfg) {
@@ -1084,7 +1014,6 @@ int small_lpt(int k, int dmax) {
 }
 bool has_small_path(int k, int dmax, bool f64, const LaunchCfg &cfg) {
     if (f64 || cfg.strict || cfg.model == CAMF_C) return false;
-    if (cmi_exp_env("CMI_NO_SMALL_K")) return false; // A/B experiments
     return k < 64 && dmax <= 16;
 }
 constexpr int SMALL_TPG = 2;
@@ -1115,57 +1044,38 @@ hipError_t launch_level_small_f32(const SgdArgs<float> &a, const LaunchCfg &cfg,
     return hipErrorInvalidValue;
 }
 
-template <int MODEL, int TPG>
-static hipError_t launch_fast_model_tpg(const SgdArgs<float> &a, int64_t begin, int count, int64_t slot0,
-                                        hipStream_t s) {
-    const dim3 grid((count + 16 * TPG - 1) / (16 * TPG)), block(256);
+template <int MODEL>
+static hipError_t launch_fast_model(const SgdArgs<float> &a, const LaunchCfg &, int64_t begin, int count,
+                                    int64_t slot0, hipStream_t s) {
+    constexpr int T = FAST_TPG;
+    const dim3 grid(level_blocks_f32_fast(a.k, count)), block(256);
     switch (a.k) {
-    case 64: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 1, TPG>), grid, block, 0, s, a, begin, count, slot0); break;
-    case 128:
-        if (level_coherent()) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, TPG, false, true>), grid, block, 0, s, a, begin, count, slot0);
-        else hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, TPG>), grid, block, 0, s, a, begin, count, slot0);
-        break;
-    case 256: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, TPG>), grid, block, 0, s, a, begin, count, slot0); break;
+    case 64: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 1, T>), grid, block, 0, s, a, begin, count, slot0); break;
+    case 128: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, T>), grid, block, 0, s, a, begin, count, slot0); break;
+    case 256: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, T>), grid, block, 0, s, a, begin, count, slot0); break;
     default: // ragged k (multiple of 4)
-        if (a.k < 128) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, TPG, true>), grid, block, 0, s, a, begin, count, slot0);
-        else if (a.k < 192) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 3, TPG, true>), grid, block, 0, s, a, begin, count, slot0);
-        else hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, TPG, true>), grid, block, 0, s, a, begin, count, slot0);
+        if (a.k < 128) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, T, true>), grid, block, 0, s, a, begin, count, slot0);
+        else if (a.k < 192) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 3, T, true>), grid, block, 0, s, a, begin, count, slot0);
+        else hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, T, true>), grid, block, 0, s, a, begin, count, slot0);
         break;
     }
     return hipGetLastError();
 }
 
 template <int MODEL>
-static hipError_t launch_fast_model(const SgdArgs<float> &a, const LaunchCfg &, int64_t begin, int count,
-                                    int64_t slot0, hipStream_t s) {
-    switch (fast_tpg()) {
-    case 1: return launch_fast_model_tpg<MODEL, 1>(a, begin, count, slot0, s);
-    case 4: return launch_fast_model_tpg<MODEL, 4>(a, begin, count, slot0, s);
-    default: return launch_fast_model_tpg<MODEL, 2>(a, begin, count, slot0, s);
-    }
-}
-
-template <int MODEL, int TPG>
-static void *fast_kernel_ptr(int k) {
+static void *fast_kernel_ptr_model(int k) {
+    constexpr int T = FAST_TPG;
     switch (k) {
-    case 64: return (void *)sgd_level_fast_f32<MODEL, 1, TPG>;
-    case 128: return level_coherent() ? (void *)sgd_level_fast_f32<MODEL, 2, TPG, false, true> : (void *)sgd_level_fast_f32<MODEL, 2, TPG>;
-    case 256: return (void *)sgd_level_fast_f32<MODEL, 4, TPG>;
+    case 64: return (void *)sgd_level_fast_f32<MODEL, 1, T>;
+    case 128: return (void *)sgd_level_fast_f32<MODEL, 2, T>;
+    case 256: return (void *)sgd_level_fast_f32<MODEL, 4, T>;
     }
     if (k > 64 && k < 256 && k % 4 == 0) {
-        if (k < 128) return (void *)sgd_level_fast_f32<MODEL, 2, TPG, true>;
-        if (k < 192) return (void *)sgd_level_fast_f32<MODEL, 3, TPG, true>;
-        return (void *)sgd_level_fast_f32<MODEL, 4, TPG, true>;
+        if (k < 128) return (void *)sgd_level_fast_f32<MODEL, 2, T, true>;
+        if (k < 192) return (void *)sgd_level_fast_f32<MODEL, 3, T, true>;
+        return (void *)sgd_level_fast_f32<MODEL, 4, T, true>;
     }
     return nullptr;
-}
-template <int MODEL>
-static void *fast_kernel_ptr_model(int k) {
-    switch (fast_tpg()) {
-    case 1: return fast_kernel_ptr<MODEL, 1>(k);
-    case 4: return fast_kernel_ptr<MODEL, 4>(k);
-    default: return fast_kernel_ptr<MODEL, 2>(k);
-    }
 }
 
 hipError_t launch_level_fast_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int64_t begin, int count,
@@ -1591,7 +1501,7 @@ static hipError_t launch_serial_model(const SgdArgs<T> &a, const LaunchCfg &cfg,
         hipLaunchKernelGGL((sgd_serial<T, MODEL, true>), dim3(1), dim3(64), 0, s, a, n, loss_out);
     else if (MODEL == CAMF_C && camfc_pipe_supported(a.k, a.n_conds, a.dmax))
         return launch_camfc_pipe<T>(a, n, loss_out, s);
-    else if (a.k <= 256 && lds <= 64 * 1024 && !cmi_exp_env("CMI_SERIAL_GENERIC")) {
+    else if (a.k <= 256 && lds <= 64 * 1024) {
         if (a.k == 64) hipLaunchKernelGGL((sgd_serial_fast<T, MODEL, 1, true>), dim3(1), dim3(64), lds, s, a, n, loss_out);
         else if (a.k == 128) hipLaunchKernelGGL((sgd_serial_fast<T, MODEL, 2, true>), dim3(1), dim3(64), lds, s, a, n, loss_out);
         else if (a.k == 256) hipLaunchKernelGGL((sgd_serial_fast<T, MODEL, 4, true>), dim3(1), dim3(64), lds, s, a, n, loss_out);

@@ -3,7 +3,6 @@
 // Host side: query / candidate / exclusion bookkeeping and the (tiny, per-query) metric formulas; device side:
 // rank_kernels.hip.  No CPU scoring path exists.
 #include <algorithm>
-#include "env_knobs.hpp"
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -615,10 +614,6 @@ void RankWorkspace::release() {
     Buf *dev[] = {&dA, &dB, &dS, &drc, &dcand, &dqu, &dqc, &dexptr, &dexcl, &dtop, &dscore, &dcount, &dB2, &dA2, &dS2, &dqg, &dqd, &dgu, &ddc, &dscr, &dSb, &dAb, &dcolc, &dM1, &dM1b, &dM2};
     if (sel_stream) (void)hipStreamDestroy(sel_stream);
     sel_stream = nullptr;
-    if (gemm_stream) (void)hipStreamDestroy(gemm_stream);
-    gemm_stream = nullptr;
-    if (ev_gs) (void)hipEventDestroy(ev_gs);
-    ev_gs = nullptr;
     for (std::vector<hipEvent_t> *v : {&evgemm, &evsel}) {
         for (hipEvent_t ev : *v) (void)hipEventDestroy(ev);
         v->clear();
@@ -890,27 +885,6 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
         need(ws.dAb, up128(bg) * a.kp1 * 4);
         need(ws.dSb, (size_t)bg * (size_t)nc * 4 + RANK_SLAB_SLACK);
         if (prune) need(ws.dM1b, (size_t)bg * nt64 * 4);
-        // experiment builds, CMI_RANK_SEL_CUS=N: the selection's stream may only use N compute units of every XCD (of 32) and the
-        // contraction runs on a stream of its own masked to the others, so that the two kernels overlap instead of taking turns
-        // (docs/history/r06.md 3 has the sweep)
-        const char *cus = cmi_exp_env("CMI_RANK_SEL_CUS");
-        if (e == hipSuccess && !ws.sel_stream && cus && atoi(cus) > 0) {
-            const int nsel = atoi(cus);
-            int n_cu = 0;
-            e = hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, 0);
-            uint32_t msel[16] = {}, mgemm[16] = {};
-            for (int c = 0; c < n_cu && c < 512; ++c) ((c / 8 < nsel) ? msel : mgemm)[c / 32] |= 1u << (c % 32); // bit c: XCD c % 8, slot c / 8
-            if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&ws.sel_stream, (uint32_t)((n_cu + 31) / 32), msel);
-            if (e == hipSuccess) e = hipExtStreamCreateWithCUMask(&ws.gemm_stream, (uint32_t)((n_cu + 31) / 32), mgemm);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&ws.ev_gs, hipEventDisableTiming);
-        }
-        // experiment builds, CMI_RANK_SEL_PRIO=high|low: the selection's stream at the device's highest / lowest stream priority (the
-        // instance's own stream, which carries the contraction, has the default one)
-        if (const char *pr = cmi_exp_env("CMI_RANK_SEL_PRIO")) {
-            int least = 0, greatest = 0;
-            if (e == hipSuccess && !ws.sel_stream) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-            if (e == hipSuccess && !ws.sel_stream) e = hipStreamCreateWithPriority(&ws.sel_stream, hipStreamNonBlocking, !strcmp(pr, "high") ? greatest : least);
-        }
         if (e == hipSuccess && !ws.sel_stream) e = hipStreamCreateWithFlags(&ws.sel_stream, hipStreamNonBlocking);
     }
     need(ws.dscr, std::max<size_t>(up128(bg), up128(n_dc)) * 4);
@@ -999,11 +973,6 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     hipStream_t sel = two ? ws.sel_stream : stream;
     // (the contraction of batch b + 1 made to wait for the selection of batch b -- the kernels never side by side, only the lists' copies
     // overlapped -- measured the same 6.3 ms as the overlapped form: docs/history/r06.md 3)
-    hipStream_t gs = two && ws.gemm_stream ? ws.gemm_stream : stream; // (the contraction's stream: the instance's own, except in the CU-split experiment)
-    if (gs != stream && e == hipSuccess) {
-        e = hipEventRecord(ws.ev_gs, stream); // behind the operands and the S2 contraction
-        if (e == hipSuccess) e = hipStreamWaitEvent(gs, ws.ev_gs, 0);
-    }
     for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
         const int64_t g0 = cuts[b];
         const int n = (int)(cuts[b + 1] - g0);
@@ -1011,15 +980,15 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
         float *dAx = (float *)((two && (b & 1)) ? ws.dAb.p : ws.dA.p), *dSx = (float *)((two && (b & 1)) ? ws.dSb.p : ws.dS.p);
         float *dMx = prune ? (float *)((two && (b & 1)) ? ws.dM1b.p : ws.dM1.p) : nullptr;
         // the slab of this parity is free once the selection of batch b - 2 has read it
-        if (two && b >= 2 && e == hipSuccess) e = hipStreamWaitEvent(gs, ev_at(ws.evsel, b - 2), 0);
+        if (two && b >= 2 && e == hipSuccess) e = hipStreamWaitEvent(stream, ev_at(ws.evsel, b - 2), 0);
         // (the builder leaves its per-row constant -- zero here -- in the scratch the contraction then reads as its row constant)
-        if (e == hipSuccess) e = rank_launch_split_users(a, (const int32_t *)ws.dgu.p + g0, n, dAx, (float *)ws.dscr.p, gs);
-        if (e == hipSuccess) e = ws.kernel_event(4 * b, gs);
-        if (e == hipSuccess) e = rank_launch_gemm<float>(dAx, a.B1, (const float *)ws.dscr.p, dSx, n, nc, a.kp1, gs, a.colc, dMx);
-        if (e == hipSuccess) e = ws.kernel_event(4 * b + 1, gs);
+        if (e == hipSuccess) e = rank_launch_split_users(a, (const int32_t *)ws.dgu.p + g0, n, dAx, (float *)ws.dscr.p, stream);
+        if (e == hipSuccess) e = ws.kernel_event(4 * b, stream);
+        if (e == hipSuccess) e = rank_launch_gemm<float>(dAx, a.B1, (const float *)ws.dscr.p, dSx, n, nc, a.kp1, stream, a.colc, dMx);
+        if (e == hipSuccess) e = ws.kernel_event(4 * b + 1, stream);
         if (two && e == hipSuccess) {
             hipEvent_t g = ev_at(ws.evgemm, b);
-            if (e == hipSuccess) e = hipEventRecord(g, gs);
+            if (e == hipSuccess) e = hipEventRecord(g, stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(sel, g, 0);
         }
         if (e == hipSuccess) e = ws.kernel_event(4 * b + 2, sel);
@@ -1308,7 +1277,7 @@ static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, 
         for (const Arr &a : arrs) hsh = (hsh ^ (a.bytes + (a.p ? 1 : 0))) * 0x100000001B3ull;
         key.hash = hsh;
     }
-    if (!(ws.plan_valid && ws.plan_key == key) || cmi_exp_env("CMI_RANK_NO_PLAN_CACHE")) {
+    if (!(ws.plan_valid && ws.plan_key == key)) {
         ws.plan_valid = false;
         rank_build_plan(h->n_users, h->n_items, RankTuples{n_train, tu, tj, tctx, tr}, RankTuples{n_test, su, sj, sctx, sr}, bin_thold,
                         num_ignore, plan);

@@ -14,7 +14,6 @@
 // Top-N: one wave64 per query row repeatedly extracts the row maximum (ties -> lowest candidate index, which
 // reproduces the reference's stable descending sort over its candidate iteration order).
 #include <hip/hip_runtime.h>
-#include "env_knobs.hpp"
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -771,9 +770,8 @@ template <typename T>
 hipError_t rank_launch_gemm(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp, hipStream_t s, const T *col_const, T *tile_max) {
     if (nq <= 0 || nc <= 0) return hipSuccess;
     const int nt64 = (nc + 63) / 64;
-    static const bool force_valu = cmi_exp_env("CMI_RANK_VALU") != nullptr; // A/B experiments only
     if constexpr (sizeof(T) == 4) {
-        if (!force_valu && kp % RG_BK == 0) {
+        if (kp % RG_BK == 0) {
             const int tiles_c = (nc + RG_BN - 1) / RG_BN, n_tiles = tiles_c * ((nq + RG_BM - 1) / RG_BM);
             hipLaunchKernelGGL(rank_gemm_mfma_f32, dim3(((n_tiles + 7) / 8) * 8), dim3(256), 0, s, (const float *)A,
                                (const float *)B, (const float *)row_const, (float *)S, nq, nc, kp, tiles_c, n_tiles, (const float *)col_const,

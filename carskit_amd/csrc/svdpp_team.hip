@@ -15,7 +15,6 @@
 // Per element the expressions are ext_serial_wave's; dots and the prediction are tree sums.  A user whose rows do not fit the LDS budget
 // (or whose ratings do not arrive as one run) is walked by wave 0 with ext_serial_wave's code.
 #include "mf_sgd_kernels.hpp"
-#include "env_knobs.hpp"
 #include "sgd_device.hpp"
 
 #include <cmath>
@@ -301,21 +300,10 @@ hipError_t launch_svdpp_team(const ExtArgs<T> &a, int64_t n, double *loss_out, h
     const size_t lds = fixed + rows * per_row + 16;
     // team size: 1024 threads measured fastest (measured on a stream of one-rating runs: 2.9 / 3.8 / 5.1 us per rating at k = 10 / 64 / 128 against 3.2 / 5.7 / 9.1 with
     // 256 threads) although a link is only ~375 instructions per wave: the wide parts (|N(u)| k element updates, one group per row) win more
-    // from 16 waves than the uniform part loses; CMI_SVDPP_THREADS=256|512 for A/B runs
-    const char *env = cmi_exp_env("CMI_SVDPP_THREADS");
-    int nt = env ? atoi(env) : 1024;
-    if (nt < a.k) nt = a.k <= 256 ? 256 : a.k <= 512 ? 512 : 1024;
-#define CMI_SVDPP_LAUNCH(NTV)                                                                                                             \
-    do {                                                                                                                                  \
-        auto fn = svdpp_team<T, NTV>;                                                                                                     \
-        if (lds > 64 * 1024)                                                                                                              \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);          \
-        hipLaunchKernelGGL(fn, dim3(1), dim3(NTV), lds, s, a, n, (int)rows, loss_out);                                                    \
-    } while (0)
-    if (nt <= 256) CMI_SVDPP_LAUNCH(256);
-    else if (nt <= 512) CMI_SVDPP_LAUNCH(512);
-    else CMI_SVDPP_LAUNCH(1024);
-#undef CMI_SVDPP_LAUNCH
+    // from 16 waves than the uniform part loses
+    auto fn = svdpp_team<T, 1024>;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(fn, dim3(1), dim3(1024), lds, s, a, n, (int)rows, loss_out);
     return hipGetLastError();
 }
 template hipError_t launch_svdpp_team<float>(const ExtArgs<float> &, int64_t, double *, hipStream_t);

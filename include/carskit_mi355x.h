@@ -332,7 +332,7 @@ int cmi_last_epoch_ms(cmi_handle h, float *ms);
  *     item_side = snapshot + (sum over shards of (item_side_shard - snapshot)) / n_shards        (the MEAN of the shards' moves)
  * through ncclReduceScatter + ncclAllGather over xGMI on the shards' own streams (librccl, one communicator per shard, grouped
  * calls), and the fp64 epoch losses are all-reduced, so cmi_group_train_epoch returns the GLOBAL loss and the unchanged host-side
- * isConverged()/updateLRate() keeps steering.  Shards that share a device (or CMI_GROUP_NO_RCCL=1) use an in-process exchange
+ * isConverged()/updateLRate() keeps steering.  Shards that share a device use an in-process exchange
  * (sum in shard order on shard 0's stream) instead -- same arithmetic.  n_shards = 1 is exactly the single-instance path.
  * With n_shards > 1 this is NOT the reference's sequential semantics (n_shards local SGD streams merged per epoch): accuracy is
  * reported as a band against the 1-GPU result.  CAMF_C / SVD++ / CAMF_*CS are serial chains: 1 shard only.

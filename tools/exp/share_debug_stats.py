@@ -11,16 +11,12 @@ from tests import util
 OWNER, F64 = capi.FLAG_SCHED_OWNER, capi.FLAG_STATE_F64
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 TEAM = None if len(sys.argv) < 3 or sys.argv[2] == "default" else sys.argv[2]   # CMI_OWNER_TEAM of the instance under test
-# optional (experiment builds): STATS_CUS_TEST / STATS_CUS_NEIGH = CMI_STREAM_CUS of the instance under test / of its neighbours (compute
-# unit masks, "m:r0,r1,..."), STATS_NEIGH_WAVES = CMI_OWNER_WAVES of the neighbours, STATS_REPS, STATS_DTYPES = "f32,f64"
+# optional: STATS_NEIGH_WAVES = CMI_OWNER_WAVES of the neighbours, STATS_REPS, STATS_DTYPES = "f32,f64"
 REPS = int(os.environ.get("STATS_REPS", "12"))
 DTYPES = os.environ.get("STATS_DTYPES", "f32,f64").split(",")
 def make(d, team, flags, neighbour=False):
     if team is None: os.environ.pop("CMI_OWNER_TEAM", None)
     else: os.environ["CMI_OWNER_TEAM"] = team
-    cus = os.environ.get("STATS_CUS_NEIGH" if neighbour else "STATS_CUS_TEST")
-    if cus: os.environ["CMI_STREAM_CUS"] = cus
-    else: os.environ.pop("CMI_STREAM_CUS", None)
     waves = os.environ.get("STATS_NEIGH_WAVES") if neighbour else None
     if waves: os.environ["CMI_OWNER_WAVES"] = waves
     else: os.environ.pop("CMI_OWNER_WAVES", None)
