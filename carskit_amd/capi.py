@@ -160,6 +160,15 @@ SYMBOLS = [
     ("cmi_fm_sweep", C.c_int, [_vp]),
     ("cmi_fm_train", C.c_int, [_vp, C.c_int]),
     ("cmi_fm_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_knn_measure", C.c_int, [C.c_char_p]),
+    ("cmi_knn_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_knn_destroy", C.c_int, [_vp]),
+    ("cmi_knn_last_error", C.c_char_p, [_vp]),
+    ("cmi_knn_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_knn_build", C.c_int, [_vp, C.c_int, C.c_int, _dbl, _dbl]),
+    ("cmi_knn_get_similarity", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
+    ("cmi_knn_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_knn_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -919,3 +928,73 @@ class FMInstance:
         lo, hi = bound if bound else (0.0, 0.0)
         self._chk(self.L.cmi_fm_predict_batch(self.h, len(u), _p(u), _p(j), _p(ctx), 1 if bound else 0, lo, hi, _p(out)))
         return out
+
+
+KNN_USER, KNN_ITEM = 0, 1
+SIM_PCC, SIM_COS, SIM_COS_BINARY, SIM_MSD, SIM_CPC, SIM_EXJACCARD = range(6)
+
+
+def knn_measure(name):
+    """the CMI_SIM_* id of a `similarity` value (case-insensitive; unknown names are pcc, as in the reference)"""
+    return lib().cmi_knn_measure(name.encode())
+
+
+class KNNInstance:
+    """The reference's ItemKNN (kind="item") or UserKNN (kind="user") on one GPU (a `cmi_knn_handle`)."""
+
+    def __init__(self, kind, n_users, n_items, device=0, flags=0):
+        self.L = lib()
+        k = {"user": KNN_USER, "item": KNN_ITEM}.get(kind, kind)
+        self.kind, self.n_users, self.n_items = k, n_users, n_items
+        self.n = n_items if k == KNN_ITEM else n_users
+        self.h = _vp()
+        rc = self.L.cmi_knn_create(k if isinstance(k, int) else -1, n_users, n_items, device, flags, C.byref(self.h))
+        if rc != OK:
+            self.h = None
+            raise CmiError(rc, self.L.cmi_knn_last_error(None).decode())
+
+    def _chk(self, rc):
+        if rc != OK:
+            raise CmiError(rc, self.L.cmi_knn_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.cmi_knn_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_ratings(self, u, i, r):
+        """the 2-D train matrix as cells (user, item, value)"""
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        i = np.ascontiguousarray(i, dtype=np.int32)
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        self._chk(self.L.cmi_knn_set_ratings(self.h, len(r), _p(u), _p(i), _p(r)))
+
+    def build(self, measure="pcc", shrinkage=-1, min_rate=1.0, max_rate=5.0):
+        m = knn_measure(measure) if isinstance(measure, str) else int(measure)
+        self._chk(self.L.cmi_knn_build(self.h, m, int(shrinkage), float(min_rate), float(max_rate)))
+
+    def similarity(self, row0=0, nrows=None):
+        """rows of the dense similarity matrix (NaN where unset)"""
+        nrows = self.n - row0 if nrows is None else nrows
+        out = np.empty((max(nrows, 0), self.n))
+        self._chk(self.L.cmi_knn_get_similarity(self.h, int(row0), int(nrows), _p(out)))
+        return out
+
+    def predict(self, u, j, knn, global_mean, bound=False, lo=1.0, hi=5.0):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_knn_predict_batch(self.h, len(u), _p(u), _p(j), int(knn), float(global_mean), 1 if bound else 0,
+                                               float(lo), float(hi), _p(out)))
+        return out
+
+    def last_build_ms(self):
+        ms = C.c_float()
+        self._chk(self.L.cmi_knn_last_build_ms(self.h, C.byref(ms)))
+        return ms.value

@@ -94,6 +94,13 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     FileConfiger cf(config);
     Conf conf(cf);
     conf.flags = flags;
+    {   // ItemKNN / UserKNN: rating prediction on one GPU; refused before any data or device work
+        const std::string a = lower(LineConfiger(cf.getString("recommender")).getMainParam());
+        if ((a == "itemknn" || a == "userknn") && conf.isRankingPred)
+            throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of the KNN models is not accelerated yet");
+        if ((a == "itemknn" || a == "userknn") && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": the KNN models run on one GPU");
+    }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
     const std::string ratingFile = cf.getPath("dataset.ratings");

@@ -154,6 +154,10 @@ struct Conf {
     // (Recommender.java:332-338: reachable only with Debug.OFF there; here the driver's --load-model flag)
     bool isSaveModel = false, loadModel = false;
     std::string workingPath;
+    // ItemKNN / UserKNN: num.neighbors, similarity, num.shrinkage (Recommender.java:244-246,426)
+    int knn = 20, knnShrinkage = 0;
+    bool knnShrinkageSet = false, knnShrinkagePresent = false;
+    std::string similarity = "PCC", knnShrinkageRaw;
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
         if (cf.contains("learn.rate")) {
@@ -194,6 +198,16 @@ struct Conf {
         if (cf.contains("ratings.setup")) binThold = cf.getParamOptions("ratings.setup").getFloat("-threshold", -1);
         evalStrategy = lower(cf.getString("eval.strategy", "ucu"));
         if (cf.contains("recommender")) numF = cf.getParamOptions("recommender").getInt("-f", 10);
+        knn = cf.getInt("num.neighbors", 20);
+        similarity = cf.getString("similarity", "PCC");
+        if (cf.contains("num.shrinkage")) { // Integer.parseInt: an optional sign and decimal digits only
+            knnShrinkagePresent = true;
+            knnShrinkageRaw = cf.getString("num.shrinkage");
+            const std::string &v = knnShrinkageRaw;
+            size_t p = (!v.empty() && (v[0] == '-' || v[0] == '+')) ? 1 : 0;
+            knnShrinkageSet = p < v.size() && v.find_first_not_of("0123456789", p) == std::string::npos;
+            if (knnShrinkageSet) knnShrinkage = (int)std::strtol(v.c_str(), nullptr, 10);
+        }
         if (cf.contains("FM")) {
             LineConfiger fm = cf.getParamOptions("FM");
             regLw = fm.getFloat("-lw", 0);
@@ -437,7 +451,7 @@ class IterativeRecommender {
     std::string modelPath() const {
         return conf_.workingPath + algoName + "/model" + (fold_ > 0 ? " fold [" + std::to_string(fold_) + "]" : "") + ".cmi";
     }
-    void saveModel() {
+    virtual void saveModel() {
         if (!h_) { // FM keeps its model behind a cmi_fm_handle, which has no persistence entry point
             if (log_) log_("--save-model: not available for " + algoName);
             return;
@@ -500,6 +514,23 @@ class IterativeRecommender {
             r2.push_back(sum / cnt);
             a = b;
         }
+    }
+
+    // Recommender.evalRatings (Recommender.java:504-594, numeric part) over bounded predictions of the test tuples, in their order;
+    // NaN predictions are skipped
+    Measures evalPredictions(const std::vector<double> &pred) const {
+        double sa = 0, ss = 0, sra = 0, srs = 0;
+        int64_t n = 0;
+        for (size_t t = 0; t < pred.size(); ++t) {
+            if (std::isnan(pred[t])) continue;
+            const double rp = std::floor(pred[t] / trainMatrix.min_rate + 0.5) * trainMatrix.min_rate;
+            const double e = std::fabs(testMatrix.r[t] - pred[t]), re = std::fabs(testMatrix.r[t] - rp);
+            sa += e, ss += e * e, sra += re, srs += re * re;
+            ++n;
+        }
+        const double mae = sa / (double)n;
+        return Measures{{"MAE", mae}, {"RMSE", std::sqrt(ss / (double)n)}, {"NMAE", mae / (trainMatrix.max_rate - trainMatrix.min_rate)},
+                        {"rMAE", sra / (double)n}, {"rRMSE", std::sqrt(srs / (double)n)}, {"MPE", 0.0}};
     }
 
     std::string algoName;
@@ -601,18 +632,7 @@ class FM : public IterativeRecommender {
         std::vector<double> pred((size_t)testMatrix.n());
         fmcheck(cmi_fm_predict_batch(fm_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(), 1,
                                      trainMatrix.min_rate, trainMatrix.max_rate, pred.data()), "cmi_fm_predict_batch");
-        double sa = 0, ss = 0, sra = 0, srs = 0;
-        int64_t n = 0;
-        for (size_t t = 0; t < pred.size(); ++t) {
-            if (std::isnan(pred[t])) continue;
-            const double rp = std::floor(pred[t] / trainMatrix.min_rate + 0.5) * trainMatrix.min_rate;
-            const double e = std::fabs(testMatrix.r[t] - pred[t]), re = std::fabs(testMatrix.r[t] - rp);
-            sa += e, ss += e * e, sra += re, srs += re * re;
-            ++n;
-        }
-        const double mae = sa / (double)n;
-        return Measures{{"MAE", mae}, {"RMSE", std::sqrt(ss / (double)n)}, {"NMAE", mae / (trainMatrix.max_rate - trainMatrix.min_rate)},
-                        {"rMAE", sra / (double)n}, {"rRMSE", std::sqrt(srs / (double)n)}, {"MPE", 0.0}};
+        return evalPredictions(pred);
     }
     double w0 = 0;
     std::vector<double> w, V;
@@ -622,6 +642,57 @@ class FM : public IterativeRecommender {
         if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_fm_last_error(fm_));
     }
     cmi_fm_handle fm_ = nullptr;
+};
+
+// src/carskit/alg/baseline/cf/{ItemKNN,UserKNN}.java: the similarity matrix of the 2-D train matrix (buildCorrs) and the
+// neighbourhood predict(u, j), rating prediction only; evaluation through the generic evalRatings recipe on bounded predictions.
+// num.neighbors (default 20) and similarity (default PCC) as Recommender.java:244-245 reads them; num.shrinkage as correlation() reads it
+// (Recommender.java:426: cf.getInt(key) = Integer.parseInt(value), so a missing or non-integer value fails the model there and here).
+class KNNRecommender : public IterativeRecommender {
+  public:
+    KNNRecommender(int kind, const char *name, const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log)
+        : IterativeRecommender(-1, name, false, tr, te, fold, c, log), kind_(kind) {}
+    ~KNNRecommender() override {
+        if (knn_) cmi_knn_destroy(knn_);
+    }
+    void initModel() override {}
+    void buildModel() override {
+        if (!conf_.knnShrinkageSet) // the reference: Integer.parseInt(null) -> "null", Integer.parseInt("x") -> For input string: "x"
+            throw std::runtime_error(!conf_.knnShrinkagePresent ? std::string("null (num.shrinkage is not set)")
+                                                                     : "For input string: \"" + conf_.knnShrinkageRaw + "\" (num.shrinkage)");
+        if (cmi_knn_create(kind_, trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &knn_) != CMI_OK)
+            throw std::runtime_error(std::string("cmi_knn_create: ") + cmi_knn_last_error(nullptr));
+        std::vector<int32_t> u2, j2;
+        std::vector<double> r2;
+        to2d(trainMatrix, u2, j2, r2);
+        kcheck(cmi_knn_set_ratings(knn_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), "cmi_knn_set_ratings");
+        kcheck(cmi_knn_build(knn_, cmi_knn_measure(conf_.similarity.c_str()), conf_.knnShrinkage, trainMatrix.min_rate,
+                             trainMatrix.max_rate), "cmi_knn_build");
+    }
+    Measures evalRatings() override { // Recommender.java:504-594 (numeric part); NaN predictions are skipped
+        std::vector<double> pred((size_t)testMatrix.n());
+        kcheck(cmi_knn_predict_batch(knn_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), conf_.knn, globalMean, 1,
+                                     trainMatrix.min_rate, trainMatrix.max_rate, pred.data()), "cmi_knn_predict_batch");
+        return evalPredictions(pred);
+    }
+    void saveModel() override {} // the reference's saveModel() of these two models is empty
+
+  private:
+    void kcheck(int rc, const char *what) {
+        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_knn_last_error(knn_));
+    }
+    int kind_;
+    cmi_knn_handle knn_ = nullptr;
+};
+class ItemKNN : public KNNRecommender {
+  public:
+    ItemKNN(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : KNNRecommender(CMI_KNN_ITEM, "ItemKNN", tr, te, fold, c, log) {}
+};
+class UserKNN : public KNNRecommender {
+  public:
+    UserKNN(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : KNNRecommender(CMI_KNN_USER, "UserKNN", tr, te, fold, c, log) {}
 };
 
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
@@ -639,7 +710,9 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "camf_ics") return std::unique_ptr<IterativeRecommender>(new CAMF_ICS(tr, te, fold, c, log));   // CARSKit.java:708
     if (n == "camf_lcs") return std::unique_ptr<IterativeRecommender>(new CAMF_LCS(tr, te, fold, c, log));   // CARSKit.java:710
     if (n == "camf_mcs") return std::unique_ptr<IterativeRecommender>(new CAMF_MCS(tr, te, fold, c, log));   // CARSKit.java:712
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm)");
+    if (n == "itemknn") return std::unique_ptr<IterativeRecommender>(new ItemKNN(tr, te, fold, c, log));
+    if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn)");
 }
 
 } // namespace carskit

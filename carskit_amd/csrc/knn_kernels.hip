@@ -1,0 +1,335 @@
+// knn_kernels.hip -- ItemKNN / UserKNN on gfx950: the similarity build (Recommender.buildCorrs + correlation + happy.coding.math.Sims)
+// and the neighbourhood prediction (ItemKNN.predict / UserKNN.predict).  Everything is fp64 with the reference's operation order:
+// every per-pair sum runs sequentially in one lane along the ascending contracted index (no lane-split reductions, no FMA:
+// -ffp-contract=off), and division / sqrt are the correctly rounded IEEE operations Java uses.
+#include "knn_kernels.hpp"
+#include "../../include/carskit_mi355x.h"
+
+namespace cmi {
+
+// ---- similarity build ----------------------------------------------------------------------------------------------------------
+// A workgroup owns an anchor row a and its partners b > a, one per lane (chunks of KNN_BUILD_BLOCK).  The anchor's vector is
+// scattered into LDS one tile of KNN_TILE contracted indices at a time (only tiles where the anchor has entries: no common entry lies
+// elsewhere); every lane walks its partner's entries of that tile in ascending order and probes the tile, so the common entries are
+// met in ascending order and the running sums stay in the lane's registers across tiles.  pcc sweeps the tiles twice (the means of
+// the common lists first, then the centred sums), as Sims.pcc does.  A tile entry is valid when its tag equals the current generation,
+// so a tile is never cleared.
+template <int M>
+__global__ __launch_bounds__(KNN_BUILD_BLOCK) void knn_build_kernel(KnnCsr R, int n, const double *norm2, int shrinkage, double median,
+                                                                    double *S) {
+    __shared__ double lv[KNN_TILE];
+    __shared__ int32_t tag[KNN_TILE];
+    __shared__ uint8_t okA[M == CMI_SIM_COS_BINARY ? KNN_TILE : 1];
+    __shared__ int32_t s_qb;
+    const int a = blockIdx.x;
+    const int a0 = R.ptr[a], a1 = R.ptr[a + 1];
+    if (a0 == a1 || a + 1 >= n) return; // Recommender.buildCorrs skips empty rows
+    for (int i = threadIdx.x; i < KNN_TILE; i += blockDim.x) tag[i] = -1;
+    int gen = 0;
+    constexpr int PASSES = M == CMI_SIM_PCC ? 2 : 1;
+    for (int c = a + 1; c < n; c += blockDim.x) {
+        const int b = c + (int)threadIdx.x;
+        const int b0 = b < n ? R.ptr[b] : 0, b1 = b < n ? R.ptr[b + 1] : 0;
+        const bool act = b0 < b1;
+        int k = 0;
+        double x1 = 0.0, x2 = 0.0, x3 = 0.0, mua = 0.0, mub = 0.0;
+        for (int pass = 0; pass < PASSES; ++pass) {
+            if (pass == 1) { // Stats.mean of the two common lists, then the centred sums start from zero
+                mua = x1 / (double)k;
+                mub = x2 / (double)k;
+                x1 = x2 = 0.0;
+            }
+            int cur = b0;
+            for (int qa = a0; qa < a1;) {
+                const int lo = R.idx[qa] / KNN_TILE * KNN_TILE, hi = lo + KNN_TILE;
+                __syncthreads(); // the previous tile's readers are done
+                if (threadIdx.x == 0) { // the anchor's entries of this tile: [qa, qb)
+                    int l = qa, r = a1;
+                    while (l < r) {
+                        const int m = (l + r) >> 1;
+                        if (R.idx[m] < hi) l = m + 1;
+                        else r = m;
+                    }
+                    s_qb = l;
+                }
+                __syncthreads();
+                const int qb = s_qb;
+                for (int q = qa + (int)threadIdx.x; q < qb; q += blockDim.x) {
+                    if (M != CMI_SIM_COS_BINARY && !R.ok[q]) continue; // correlation(): iv.contains(idx) misses this entry
+                    lv[R.idx[q] - lo] = R.val[q];
+                    tag[R.idx[q] - lo] = gen;
+                    if (M == CMI_SIM_COS_BINARY) okA[R.idx[q] - lo] = R.ok[q];
+                }
+                __syncthreads();
+                if (act) {
+                    int l = cur, r = b1; // skip the partner's entries below the tile
+                    while (l < r) {
+                        const int m = (l + r) >> 1;
+                        if (R.idx[m] < lo) l = m + 1;
+                        else r = m;
+                    }
+                    for (cur = l; cur < b1; ++cur) {
+                        const int x = R.idx[cur];
+                        if (x >= hi) break;
+                        if (tag[x - lo] != gen) continue;
+                        const double va = lv[x - lo], vb = R.val[cur]; // is.add(iv.get(idx)), js.add(jv.get(idx))
+                        if (M == CMI_SIM_PCC) {
+                            if (pass == 0) {
+                                x1 += va;
+                                x2 += vb;
+                                ++k;
+                            } else {
+                                const double da = va - mua, db = vb - mub;
+                                x1 += da * db;
+                                x2 += da * da;
+                                x3 += db * db;
+                            }
+                        } else if (M == CMI_SIM_MSD) {
+                            const double d = va - vb; // Math.pow(d, 2.0) == d * d
+                            x1 += d * d;
+                            ++k;
+                        } else if (M == CMI_SIM_CPC) {
+                            const double da = va - median, db = vb - median;
+                            x1 += da * db;
+                            x2 += da * da;
+                            x3 += db * db;
+                            ++k;
+                        } else if (M == CMI_SIM_COS_BINARY) {
+                            if (R.ok[cur]) x1 += va * vb; // iv.inner(jv): jv.contains(idx)
+                            k += okA[x - lo];             // n = is.size(): the entries iv.contains finds
+                        } else { // cos, exjaccard
+                            x1 += va * vb;
+                            x2 += va * va;
+                            x3 += vb * vb;
+                            ++k;
+                        }
+                    }
+                }
+                ++gen;
+                qa = qb;
+            }
+        }
+        if (!act) continue;
+        double sim;
+        if (M == CMI_SIM_PCC) sim = k < 2 ? __builtin_nan("") : x1 / (__dsqrt_rn(x2) * __dsqrt_rn(x3));
+        else if (M == CMI_SIM_COS || M == CMI_SIM_CPC) sim = k == 0 ? __builtin_nan("") : x1 / (__dsqrt_rn(x2) * __dsqrt_rn(x3));
+        else if (M == CMI_SIM_COS_BINARY) sim = x1 / (__dsqrt_rn(norm2[a]) * __dsqrt_rn(norm2[b]));
+        else if (M == CMI_SIM_MSD) {
+            sim = (double)k / x1;
+            if (__builtin_isinf(sim)) sim = 1.0;
+        } else sim = x1 / (x2 + x3 - x1); // exJaccard
+        if (__builtin_isnan(sim)) continue; // NaN is not stored
+        if (shrinkage > 0) sim *= (double)k / (double)(k + shrinkage);
+        S[(int64_t)a * n + b] = sim;
+        S[(int64_t)b * n + a] = sim;
+    }
+}
+
+hipError_t knn_launch_build(KnnCsr rows, int n, const double *norm2, int measure, int shrinkage, double median, double *S,
+                            hipStream_t s) {
+    if (n <= 1) return hipSuccess;
+    const dim3 g(n), b(KNN_BUILD_BLOCK);
+    switch (measure) {
+    case CMI_SIM_COS: knn_build_kernel<CMI_SIM_COS><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    case CMI_SIM_COS_BINARY: knn_build_kernel<CMI_SIM_COS_BINARY><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    case CMI_SIM_MSD: knn_build_kernel<CMI_SIM_MSD><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    case CMI_SIM_CPC: knn_build_kernel<CMI_SIM_CPC><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    case CMI_SIM_EXJACCARD: knn_build_kernel<CMI_SIM_EXJACCARD><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    default: knn_build_kernel<CMI_SIM_PCC><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
+    }
+    return hipGetLastError();
+}
+
+__global__ void knn_row_stats_kernel(KnnCsr R, int n, double *mean, double *norm2) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= n) return;
+    double s = 0.0, q = 0.0;
+    for (int e = R.ptr[v]; e < R.ptr[v + 1]; ++e) { // Stats.sum(data) / count; inner(v, v) -- both in index order
+        s += R.val[e];
+        if (R.ok[e]) q += R.val[e] * R.val[e]; // iv.inner(iv): iv.contains(idx)
+    }
+    const int c = R.ptr[v + 1] - R.ptr[v];
+    mean[v] = c > 0 ? s / (double)c : __builtin_nan("");
+    norm2[v] = q;
+}
+
+hipError_t knn_launch_row_stats(KnnCsr rows, int n, double *mean, double *norm2, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    knn_row_stats_kernel<<<(n + 255) / 256, 256, 0, s>>>(rows, n, mean, norm2);
+    return hipGetLastError();
+}
+
+// ---- prediction --------------------------------------------------------------------------------------------------------------
+// java.util.HashMap<Integer, Double> (JDK 8): bucket = (h ^ h >>> 16) & (cap - 1); a bin is a list in insertion order; a put that makes
+// a list of 9 nodes calls treeifyBin, which doubles a table of fewer than 64 slots and treeifies the bin otherwise; ++size > threshold
+// doubles the table.  Resizing keeps the relative order inside a bin, so as long as no bin is treeified the iteration order is
+// (bucket at the final capacity, insertion order).
+__device__ __forceinline__ uint32_t jhash(int32_t k) { return (uint32_t)k ^ ((uint32_t)k >> 16); }
+
+// the table's growth while keys kat(0..n-1) are put in that order; cap == 0: a new map (16 slots at the first put).  *tree: a bin
+// would be treeified (its order is not modelled).  Called by the whole wave; cnt: 64 ints of LDS.
+template <class K>
+__device__ void hm_grow(K kat, int n, int &cap, int &thr, int &tree, int32_t *cnt) {
+    const int lane = threadIdx.x;
+    __shared__ int32_t sh[3];
+    if (cap == 0) cap = 16, thr = 12;
+    if (lane == 0) { // tables below 64 slots: a serial walk with the bin counts (at most 48 puts)
+        int t = 0;
+        auto recount = [&](int upto) {
+            for (int b = 0; b < 64; ++b) cnt[b] = 0;
+            for (int s = 0; s < upto; ++s) ++cnt[jhash(kat(s)) & (cap - 1)];
+        };
+        if (cap < 64) recount(0);
+        while (t < n && cap < 64) {
+            const int b = jhash(kat(t)) & (cap - 1);
+            const bool grow = ++cnt[b] >= 9; // treeifyBin on a small table: resize()
+            ++t;
+            const int before = cap;
+            if (grow) cap <<= 1, thr <<= 1;
+            if (t > thr) cap <<= 1, thr <<= 1; // ++size > threshold
+            if (cap != before && cap < 64) recount(t);
+        }
+        sh[0] = t, sh[1] = cap, sh[2] = thr;
+    }
+    __syncthreads();
+    const int t0 = sh[0];
+    cap = sh[1], thr = sh[2];
+    __syncthreads();
+    // 64 slots and more: the capacity follows the size alone; a bin reaching 9 nodes is treeified.  Nine keys in one bucket of such a
+    // table share their low 6 hash bits, so a histogram mod 64 rules most maps out before the exact check.
+    int flag = 0;
+    if (t0 < n) {
+        if (lane < 64) cnt[lane] = 0;
+        __syncthreads();
+        for (int i = lane; i < n; i += 64) atomicAdd(&cnt[jhash(kat(i)) & 63], 1);
+        __syncthreads();
+        bool maybe = false;
+        for (int b = 0; b < 64; ++b) maybe |= cnt[b] >= 9;
+        __syncthreads();
+        if (maybe) {
+            for (int i = t0 + lane; i < n; i += 64) {
+                int ci = cap, ti = thr;
+                while (i > ti) ci <<= 1, ti <<= 1; // the table when key i is put (size i)
+                const uint32_t hi = jhash(kat(i));
+                int same = 0;
+                for (int s = 0; s < i; ++s) same += ((jhash(kat(s)) ^ hi) & (uint32_t)(ci - 1)) == 0;
+                flag |= same >= 8;
+            }
+        }
+        while (n > thr) cap <<= 1, thr <<= 1;
+    }
+    tree |= __any(flag) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(64) void knn_predict_kernel(KnnCsr L, const double *S, int n_ent, const double *mean, int64_t n,
+                                                         const int32_t *owner, const int32_t *target, int knn, double gm, int bound,
+                                                         double lo, double hi, double *out, int cap_entries, int32_t *s_key,
+                                                         double *s_sim, double *s_rate, int32_t *s_pos, int32_t *s_sel, int32_t *bad) {
+    __shared__ int32_t cnt[64];
+    const int lane = threadIdx.x;
+    int32_t *key = s_key + (size_t)blockIdx.x * cap_entries, *pos = s_pos + (size_t)blockIdx.x * cap_entries,
+            *sel = s_sel + (size_t)blockIdx.x * cap_entries;
+    double *sim = s_sim + (size_t)blockIdx.x * cap_entries, *rate = s_rate + (size_t)blockIdx.x * cap_entries;
+    for (int64_t t = blockIdx.x; t < n; t += gridDim.x) {
+        const int o = owner[t], g = target[t];
+        const double *Sg = S + (int64_t)g * n_ent;
+        // candidates in ascending id order: sim > 0 (NaN = unset fails) and a rating > 0
+        int m = 0;
+        for (int base = L.ptr[o]; base < L.ptr[o + 1]; base += 64) {
+            const int q = base + lane;
+            bool keep = false;
+            int e = 0;
+            double sv = 0.0, rv = 0.0;
+            if (q < L.ptr[o + 1]) {
+                e = L.idx[q];
+                rv = L.val[q];
+                sv = Sg[e];
+                keep = sv > 0.0 && rv > 0.0;
+            }
+            const uint64_t bal = __ballot(keep);
+            const int off = m + __popcll(bal & ((1ull << lane) - 1ull));
+            if (keep) key[off] = e, sim[off] = sv, rate[off] = rv;
+            m += __popcll(bal);
+        }
+        __syncthreads();
+        double pred = gm;
+        int tree = 0;
+        if (m > 0) {
+            int cap = 0, thr = 0;
+            hm_grow([&](int i) { return key[i]; }, m, cap, thr, tree, cnt);
+            const uint32_t mask1 = (uint32_t)(cap - 1);
+            for (int i = lane; i < m; i += 64) { // HashMap position: (bucket, insertion)
+                const uint32_t bi = jhash(key[i]) & mask1;
+                int p = 0;
+                for (int s = 0; s < m; ++s) {
+                    const uint32_t bs = jhash(key[s]) & mask1;
+                    p += bs < bi || (bs == bi && s < i);
+                }
+                pos[i] = p;
+            }
+            __syncthreads();
+            int len = m;
+            int32_t *ord = sel;
+            if (knn > 0 && knn < m) {
+                // Lists.sortMap(nns, true): a stable sort by value, descending, of the HashMap's entry list; the first knn survive
+                for (int i = lane; i < m; i += 64) {
+                    int r = 0;
+                    for (int s = 0; s < m; ++s) r += sim[s] > sim[i] || (sim[s] == sim[i] && pos[s] < pos[i]);
+                    if (r < knn) sel[r] = i;
+                }
+                __syncthreads();
+                // nns.clear() keeps the table; the survivors are put back in sorted order
+                hm_grow([&](int r) { return key[sel[r]]; }, knn, cap, thr, tree, cnt);
+                const uint32_t mask2 = (uint32_t)(cap - 1);
+                for (int r = lane; r < knn; r += 64) {
+                    const uint32_t br = jhash(key[sel[r]]) & mask2;
+                    int p = 0;
+                    for (int s = 0; s < knn; ++s) {
+                        const uint32_t bs = jhash(key[sel[s]]) & mask2;
+                        p += bs < br || (bs == br && s < r);
+                    }
+                    pos[p] = sel[r];
+                }
+                ord = pos;
+                len = knn;
+            } else {
+                for (int i = lane; i < m; i += 64) sel[pos[i]] = i;
+            }
+            __syncthreads();
+            if (lane == 0) { // the weighted sum in the final iteration order
+                double sum = 0.0, ws = 0.0;
+                for (int r = 0; r < len; ++r) {
+                    const int i = ord[r];
+                    sum += sim[i] * (rate[i] - mean[key[i]]);
+                    ws += fabs(sim[i]);
+                }
+                const double mg = mean[g];
+                pred = ws > 0.0 ? (__builtin_isnan(mg) ? gm : mg) + sum / ws : gm;
+            }
+        }
+        if (lane == 0) {
+            if (bound) {
+                if (pred > hi) pred = hi;
+                if (pred < lo) pred = lo;
+            }
+            if (tree) {
+                atomicAdd(bad, 1);
+                pred = __builtin_nan("");
+            }
+            out[t] = pred;
+        }
+        __syncthreads();
+    }
+}
+
+hipError_t knn_launch_predict(KnnCsr lists, const double *S, int n_ent, const double *mean, int64_t n, const int32_t *owner,
+                              const int32_t *target, int knn, double global_mean, int bound, double lo, double hi, double *out,
+                              int nwaves, int cap, int32_t *s_key, double *s_sim, double *s_rate, int32_t *s_pos, int32_t *s_sel,
+                              int32_t *bad, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    knn_predict_kernel<<<nwaves, 64, 0, s>>>(lists, S, n_ent, mean, n, owner, target, knn, global_mean, bound, lo, hi, out, cap, s_key,
+                                             s_sim, s_rate, s_pos, s_sel, bad);
+    return hipGetLastError();
+}
+
+} // namespace cmi

@@ -574,6 +574,45 @@ int cmi_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, int3
 int cmi_owner_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int hub, int n_owners, int depth,
                        int32_t *perm, int64_t *own_off, uint32_t *want, uint32_t *flags, int *hub_used);
 
+/* ---- ItemKNN / UserKNN (src/carskit/alg/baseline/cf/{ItemKNN,UserKNN}.java; knn_api.cpp, knn_kernels.hip) -------------------
+ * Rating prediction of the two memory-based baselines over the 2-D train matrix (DataDAO.toTraditionalSparseMatrix: a (user, item)
+ * cell holds the mean of its ratings over contexts).  cmi_knn_build computes Recommender.buildCorrs on the device -- every pair
+ * (a < b) of non-empty rows (UserKNN) or columns (ItemKNN), the reference's correlation() with its sums run sequentially in fp64 in
+ * ascending order of the contracted index -- into a dense n x n fp64 matrix; NaN marks an unset entry (the diagonal, pairs with an
+ * empty side, NaN similarities).  cmi_knn_predict_batch is the model's predict(u, j): candidates with sim > 0 and a rating, the knn cut
+ * by (similarity descending, java.util.HashMap position), the weighted sum in the final HashMap iteration order; bit-exact to the
+ * reference.  A tuple whose HashMap would treeify a bin (9 keys in one bucket of a table of 64 slots or more; its iteration order is
+ * not modelled) fails the call with CMI_E_UNSUPPORTED.  No CPU fallback: without a device cmi_knn_create returns CMI_E_NO_DEVICE. */
+#define CMI_KNN_USER 0
+#define CMI_KNN_ITEM 1
+#define CMI_SIM_PCC 0
+#define CMI_SIM_COS 1
+#define CMI_SIM_COS_BINARY 2
+#define CMI_SIM_MSD 3
+#define CMI_SIM_CPC 4
+#define CMI_SIM_EXJACCARD 5
+typedef struct cmi_knn_instance *cmi_knn_handle;
+/* the measure of a `similarity` value: case-insensitive, and any unknown name is CMI_SIM_PCC (Recommender.correlation's default:) */
+int cmi_knn_measure(const char *name);
+int cmi_knn_create(int kind, int n_users, int n_items, int device, unsigned flags, cmi_knn_handle *out);
+int cmi_knn_destroy(cmi_knn_handle h);
+const char *cmi_knn_last_error(cmi_knn_handle h);
+/* the 2-D train matrix as n cells; a duplicate (u, i) or an id out of range -> CMI_E_INVALID */
+int cmi_knn_set_ratings(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* shrinkage: num.shrinkage (applied when > 0); min_rate / max_rate give cpc's median.  The n x n matrix must fit in free device
+ * memory, else CMI_E_INVALID with the bytes needed (nothing is built) */
+int cmi_knn_build(cmi_knn_handle h, int measure, int shrinkage, double min_rate, double max_rate);
+/* rows [row0, row0 + nrows) of the similarity matrix, dense, NaN where unset */
+int cmi_knn_get_similarity(cmi_knn_handle h, int32_t row0, int32_t nrows, double *dst);
+/* predict(u, j) of n tuples; knn <= 0: every candidate; bound: clamp to [lo, hi] as Recommender.predict(u, j, c, true).  A tuple's
+ * candidate list (ItemKNN: the user's items, UserKNN: the item's users) may hold at most CMI_KNN_MAX_CANDIDATES entries: the wave that
+ * predicts it ranks the candidates by counting, O(m^2 / 64) steps per lane (2 000 tuples at the limit: 21 ms, tools/bench_knn.py);
+ * a longer list -> CMI_E_UNSUPPORTED, naming the tuple, before anything runs */
+#define CMI_KNN_MAX_CANDIDATES 16384
+int cmi_knn_predict_batch(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *j, int knn, double global_mean, int bound,
+                          double lo, double hi, double *out);
+int cmi_knn_last_build_ms(cmi_knn_handle h, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
