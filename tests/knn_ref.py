@@ -341,3 +341,104 @@ def eval_ratings(preds, truth, min_rate):
         ss += e * e
         n += 1
     return sa / n, math.sqrt(ss / n)
+
+
+# ---- the same prediction, vectorised -----------------------------------------------------------------------------------------------
+# predict() puts every candidate through JavaIntHashMap, whose put scans all keys: O(m^2) Python steps a tuple, unusable near the
+# 16 384-candidate limit.  predict_fast() restates it with numpy: the table's growth is a closed form of the size (plus a serial walk
+# while the table is below 64 slots, where treeifyBin resizes), the treeify test is "the number of earlier keys in key i's bin at the
+# capacity in force when i is put", and the iteration order is a sort by (bucket at the final capacity, insertion).  Only the weighted
+# sum stays a Python loop, so its rounding is predict()'s.
+
+def _jhash(keys):
+    k = np.asarray(keys, dtype=np.int64) & 0xFFFFFFFF
+    return k ^ (k >> 16)
+
+
+def _earlier_in_bin(b):
+    """per position i: how many positions s < i hold the same value b[s] == b[i]"""
+    if len(b) == 0:
+        return np.zeros(0, dtype=np.int64)
+    order = np.argsort(b, kind="stable")
+    sb = b[order]
+    start = np.r_[0, np.nonzero(sb[1:] != sb[:-1])[0] + 1]
+    first = np.repeat(start, np.diff(np.r_[start, len(sb)]))
+    occ = np.empty(len(b), dtype=np.int64)
+    occ[order] = np.arange(len(b)) - first
+    return occ
+
+
+def hashmap_grow(keys, cap=0, thr=0):
+    """JavaIntHashMap's (cap, thr) after putting the distinct `keys` in order into a table of (cap, thr) that holds no keys (cap 0: a
+    new map); raises Treeified as its put does"""
+    h = _jhash(keys)
+    n = len(h)
+    if cap == 0:
+        cap, thr = 16, 12
+    t = 0
+    while t < n and cap < 64:  # treeifyBin resizes a table below 64 slots: walk it
+        nodes = int(np.count_nonzero((h[:t] & (cap - 1)) == (h[t] & (cap - 1))))
+        t += 1
+        if nodes >= 8:
+            cap, thr = cap * 2, thr * 2
+        if t > thr:
+            cap, thr = cap * 2, thr * 2
+    # 64 slots and more: key i is put into the table of size i, which has doubled while i > thr
+    i = np.arange(t, n)
+    d = np.zeros(len(i), dtype=np.int64)
+    while True:
+        more = i > (thr << d)
+        if not more.any():
+            break
+        d += more
+    for dd in np.unique(d).tolist():
+        c = cap << dd
+        sel = i[d == dd]
+        hi = int(sel[-1]) + 1
+        occ = _earlier_in_bin(h[:hi] & (c - 1))
+        bad = sel[occ[sel] >= 8]
+        if len(bad):
+            raise Treeified(int(keys[int(bad[0])]))
+    while n > thr:
+        cap, thr = cap * 2, thr * 2
+    return cap, thr
+
+
+def _iteration_order(keys, cap):
+    return np.lexsort((np.arange(len(keys)), _jhash(keys) & (cap - 1)))
+
+
+def predict_fast(kind, S, means, lists, u, j, knn, global_mean, bound=False, lo=1.0, hi=5.0):
+    """predict() with the same contract and bits (raises Treeified for the same tuples).  lists[owner] may also be an (m, 2) array of
+    (id, rating) rows; S needs only S[target] (a row indexable by the candidate ids)."""
+    owner, target = (u, j) if kind == "item" else (j, u)
+    cells = np.asarray(lists[owner], dtype=np.float64).reshape(-1, 2)
+    ids = cells[:, 0].astype(np.int64)
+    rates = cells[:, 1]
+    sims = np.asarray(S[target], dtype=np.float64)[ids]
+    with np.errstate(invalid="ignore"):
+        keep = (sims > 0) & (rates > 0)
+    keys, sims, rates = ids[keep], sims[keep], rates[keep]
+    m = len(keys)
+    if m:
+        cap, thr = hashmap_grow(keys)
+        order = _iteration_order(keys, cap)
+        if 0 < knn < m:
+            srt = order[np.argsort(-sims[order], kind="stable")][:knn]  # Lists.sortMap(nns, true): stable, descending
+            cap, thr = hashmap_grow(keys[srt], cap, thr)  # clear() keeps the table
+            order = srt[_iteration_order(keys[srt], cap)]
+    if m == 0:
+        pred = global_mean
+    else:
+        s = ws = 0.0
+        for t in order.tolist():
+            sim = float(sims[t])
+            s += sim * (float(rates[t]) - float(means[int(keys[t])]))
+            ws += abs(sim)
+        pred = float(means[target]) + _div(s, ws) if ws > 0 else global_mean
+    if bound:
+        if pred > hi:
+            pred = hi
+        if pred < lo:
+            pred = lo
+    return pred

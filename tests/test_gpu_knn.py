@@ -1,6 +1,6 @@
 """ItemKNN / UserKNN on the GPU against the CPU restatement (tests/knn_ref.py), bit for bit: similarity matrices for every measure x
-shrinkage in {-1, 30} x kind on DePaul, one Frappe fold, a synthetic shape whose contracted dimension spans several LDS tiles and
-hand-made edge cases; predictions for knn in {0, 1, 20, more than any candidate count}; two handles built from two host threads;
+shrinkage in {-1, 30} x kind on DePaul, one Frappe fold, a synthetic shape whose contracted dimension spans several LDS tiles, one
+that adds several 256-partner chunks per anchor, and hand-made edge cases; predictions for knn in {0, 1, 20, more than any candidate count}; two handles built from two host threads;
 argument checks; and the driver's MAE / RMSE on DePaul (cv -k 5) against the restatement averaged over the same folds."""
 import json
 import math
@@ -77,6 +77,33 @@ def synth_multitile(seed=3, n_items=90, n_users=3 * 4096 + 500, cells=9000):
     return n_users, n_items, u, i, r
 
 
+def synth_chunks_by_tiles(seed=4, n_rows=640, n_ctr=3 * 4096 + 600):
+    """640 compared rows (3 chunks of 256 partners) over a contracted dimension of 4 tiles: by row mod 8, empty rows; rows only in the
+    first tile; rows only in the last tile; rows with entries in every tile; rows spread over all of it with half their entries in
+    the busy ranges, so pairs share entries in every tile"""
+    rng = np.random.default_rng(seed)
+    busy = [np.arange(t * 4096, t * 4096 + 300) for t in range(4)]
+    cells = []
+    for e in range(n_rows):
+        kind, cnt = e % 8, int(rng.integers(1, 60))
+        if kind == 0:
+            continue
+        if kind == 1:
+            c = rng.choice(busy[0], min(cnt, 300), replace=False)
+        elif kind == 2:
+            c = rng.choice(busy[3], min(cnt, 300), replace=False)
+        elif kind == 3:
+            c = np.concatenate([rng.choice(b, max(cnt // 4, 1), replace=False) for b in busy])
+        else:
+            c = np.concatenate([rng.choice(np.concatenate(busy), cnt // 2 + 1, replace=False), rng.integers(0, n_ctr, cnt // 2)])
+        for x in np.unique(c).tolist():
+            cells.append((e, x, float(rng.integers(1, 6)) / float(rng.integers(1, 3))))
+    ent = np.array([c[0] for c in cells], np.int32)
+    ctr = np.array([c[1] for c in cells], np.int32)
+    r = np.array([c[2] for c in cells])
+    return n_rows, n_ctr, ent, ctr, r
+
+
 def handmade():
     """constant common values, single common entry, no overlap, identical vectors, anti-correlation, +-Infinity (cos / cpc), a user and
     an item with no ratings"""
@@ -144,6 +171,27 @@ def test_similarity_frappe_fold(tmp_path):
 def test_similarity_multitile_synthetic():
     nu, ni, u, i, r = synth_multitile()
     check_sims(nu, ni, u, i, r)
+
+
+def test_similarity_partner_chunks_by_tiles():
+    """several 256-partner chunks of one anchor, each sweeping several 4 096-index tiles (twice for pcc), with empty partners between:
+    the per-chunk tile generations; both kinds (the matrix and its transpose); the CPU restates a subsample of anchors that holds the
+    first and last rows, empty rows and rows of every pattern"""
+    n, n_ctr, ent, ctr, r = synth_chunks_by_tiles()
+    anchors = sorted({0, 1, 2, 3, 4, 8, 11, 255, 256, 257, 511, 512, n - 9, n - 3, n - 2, n - 1} |
+                     set(np.random.default_rng(1).integers(0, n, 24).tolist()))
+    assert any(a % 8 == 0 for a in anchors) and {a % 8 for a in anchors} >= set(range(8))
+    for kind in ("item", "user"):
+        nu, ni, u, i = (n_ctr, n, ctr, ent) if kind == "item" else (n, n_ctr, ent, ctr)
+        rows = knn_ref.rows_of(u, i, r, kind, nu, ni)
+        assert len(rows) == n and any(row and row[0][0] < 4096 and row[-1][0] >= 3 * 4096 for row in rows)
+        for m in knn_ref.MEASURES:
+            for shr in (-1, 30):
+                want = knn_ref.build_corrs(rows, n_ctr, m, shr, anchors=anchors)
+                got = gpu_sim(kind, nu, ni, u, i, r, m, shr)
+                for a in anchors:
+                    assert same_bits(got[a, a + 1:], want[a, a + 1:]), (kind, m, shr, a)
+                assert same_bits(got, got.T)
 
 
 def test_similarity_handmade():

@@ -1,0 +1,428 @@
+"""ItemKNN / UserKNN prediction on the GPU past 64 candidates, bit for bit against knn_ref.predict_fast (itself pinned to predict() and
+its JavaIntHashMap by tests/test_knn_ref.py): long candidate lists up to the 16 384 limit, the limit itself, HashMap bins crowded on
+purpose (jhash(k) = k below 65 536, so a bucket is id mod capacity and ids pick them), refusals of tuples that would treeify a bin,
+mixed batches, the grid-stride loop with scratch reuse, ties at the cut, filtered candidates and ids above 65 536.
+
+Every case is a rating matrix in "entity space": entities are the compared rows (items for ItemKNN, users for UserKNN), and owners
+and two helper columns are the other side.  An owner's entities are its candidate list.  The two helpers rate every candidate and
+every target, and nothing else rates a target, so S[target, e] is cos over the two helper entries.  The helper values set the
+similarity and its sign.  An entity without helper entries has no similarity (NaN).  S comes from the GPU build (checked bit for bit
+elsewhere) through h.similarity(target, 1)."""
+import time
+
+import numpy as np
+import pytest
+
+from carskit_amd import capi
+from tests import knn_ref
+
+pytestmark = pytest.mark.gpu
+
+LIMIT = 16384  # CMI_KNN_MAX_CANDIDATES
+
+
+def same_bits(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
+
+
+class Case:
+    """a rating matrix built owner by owner (see the module docstring), its GPU handle, and predict_fast over it"""
+
+    def __init__(self, kind, n_ent, seed=0):
+        self.kind, self.n_ent = kind, n_ent
+        self.rng = np.random.default_rng(seed)
+        self.owners = []   # per owner: (entity ids, ratings)
+        self.helper = {}   # entity -> (value of helper 0, value of helper 1)
+
+    def owner(self, ents, rates=None, auto_help=True):
+        """a new owner whose list is `ents` (distinct); auto_help: random positive helper values for those that have none yet"""
+        ents = np.asarray(ents, dtype=np.int64)
+        assert len(np.unique(ents)) == len(ents) and (len(ents) == 0 or (ents.min() >= 0 and ents.max() < self.n_ent))
+        if rates is None:
+            rates = self.rng.integers(1, 6, len(ents)).astype(np.float64)
+        for e in ents.tolist():
+            if auto_help and e not in self.helper:
+                self.helper[e] = tuple(self.rng.uniform(0.5, 5.0, 2).tolist())
+        self.owners.append((ents, np.asarray(rates, dtype=np.float64)))
+        return len(self.owners) - 1
+
+    def help(self, ents, a, b):
+        for e in np.asarray(ents).tolist():
+            self.helper[e] = (a, b)
+
+    def target(self, e, a=1.0, b=1.0):
+        assert all(e not in set(o[0].tolist()) for o in self.owners)
+        self.helper[e] = (a, b)
+        return e
+
+    def finish(self, measure="cos"):
+        k = len(self.owners)
+        self.empty_owner = k + 2  # a column with no cells
+        self.n_ctr = k + 3
+        ent = [o[0] for o in self.owners] + [np.array(sorted(self.helper), np.int64)] * 2
+        ctr = [np.full(len(o[0]), c, np.int64) for c, o in enumerate(self.owners)] + [np.full(len(self.helper), k + h, np.int64)
+                                                                                         for h in (0, 1)]
+        val = [o[1] for o in self.owners] + [np.array([self.helper[e][h] for e in sorted(self.helper)]) for h in (0, 1)]
+        ent, ctr, val = np.concatenate(ent), np.concatenate(ctr), np.concatenate(val)
+        if self.kind == "item":
+            nu, ni, u, i = self.n_ctr, self.n_ent, ctr, ent
+        else:
+            nu, ni, u, i = self.n_ent, self.n_ctr, ent, ctr
+        t0 = time.time()
+        self.h = capi.KNNInstance(self.kind, nu, ni)
+        self.h.set_ratings(u.astype(np.int32), i.astype(np.int32), val)
+        self.h.build(measure, -1)
+        self.build_s = time.time() - t0
+        # the owners' lists (ascending entity) and the entity means (a sequential sum in column order / count)
+        order = np.lexsort((ent, ctr))
+        self.lptr = np.searchsorted(ctr[order], np.arange(self.n_ctr + 1))
+        self.lcells = np.column_stack((ent[order], val[order])).astype(np.float64)
+        self.means = np.full(self.n_ent, np.nan)
+        order = np.lexsort((ctr, ent))
+        cur, s, c = -1, 0.0, 0
+        for e, v in zip(ent[order].tolist(), val[order].tolist()):
+            if e != cur:
+                if c:
+                    self.means[cur] = s / c
+                cur, s, c = e, 0.0, 0
+            s += v
+            c += 1
+        if c:
+            self.means[cur] = s / c
+        self.rows, self.memo = {}, {}
+        return self
+
+    def __getitem__(self, owner):  # knn_ref's lists[owner]
+        return self.lcells[self.lptr[owner]:self.lptr[owner + 1]]
+
+    def srow(self, t):
+        if t not in self.rows:
+            self.rows[t] = self.h.similarity(t, 1)[0]
+        return self.rows[t]
+
+    def uj(self, owners, targets):
+        o, t = np.asarray(owners, np.int32), np.asarray(targets, np.int32)
+        return (o, t) if self.kind == "item" else (t, o)
+
+    def want(self, o, t, knn, gm, bound, lo=1.0, hi=5.0):
+        """predict_fast for (owner, target), or None if that tuple would treeify a bin"""
+        key = (o, t, knn, gm, bound, lo, hi)
+        if key not in self.memo:
+            u, j = (o, t) if self.kind == "item" else (t, o)
+            S = {t: self.srow(t)}
+            try:
+                self.memo[key] = knn_ref.predict_fast(self.kind, S, self.means, self, u, j, knn, gm, bound, lo, hi)
+            except knn_ref.Treeified:
+                self.memo[key] = None
+        return self.memo[key]
+
+    def candidates(self, o, t):
+        c = self[o]
+        s = self.srow(t)[c[:, 0].astype(np.int64)]
+        return int(np.count_nonzero((s > 0) & (c[:, 1] > 0)))
+
+    def check(self, owners, targets, knns, gm=3.25, lo=1.0, hi=5.0):
+        """the GPU's predictions equal predict_fast's bit for bit, bound on and off (no tuple may be refused)"""
+        u, j = self.uj(owners, targets)
+        for knn in knns:
+            for bound in (False, True):
+                want = [self.want(o, t, knn, gm, bound, lo, hi) for o, t in zip(list(owners), list(targets))]
+                assert None not in want, "a tuple of this batch would treeify a bin"
+                got = self.h.predict(u, j, knn, gm, bound, lo, hi)
+                bad = np.nonzero(~((got == np.array(want)) | (np.isnan(got) & np.isnan(want))))[0]
+                assert same_bits(got, want), (self.kind, knn, bound, bad[:5], got[bad[:5]], np.array(want)[bad[:5]])
+
+    def refused(self, owners, targets, knn, gm=3.25):
+        """the call fails with CMI_E_UNSUPPORTED, and its count equals the tuples predict_fast flags; returns that count"""
+        n_bad = sum(self.want(o, t, knn, gm, False) is None for o, t in zip(list(owners), list(targets)))
+        assert n_bad > 0
+        u, j = self.uj(owners, targets)
+        for bound in (False, True):
+            with pytest.raises(capi.CmiError) as e:
+                self.h.predict(u, j, knn, gm, bound)
+            assert e.value.code == capi.E_UNSUPPORTED, str(e.value)
+            assert ("%d tuple(s) would treeify" % n_bad) in str(e.value), (n_bad, str(e.value))
+        return n_bad
+
+    def close(self):
+        self.h.close()
+
+
+def grown(ids):
+    """(capacity, threshold) of a HashMap after putting `ids` in order"""
+    return knn_ref.hashmap_grow(np.asarray(ids, np.int64))
+
+
+def spaced_ids(start, count, avoid_mod=64, avoid=()):
+    """`count` ascending consecutive ids from `start`, skipping those whose residue mod `avoid_mod` is in `avoid`"""
+    out, k = [], start
+    while len(out) < count:
+        if k % avoid_mod not in avoid:
+            out.append(k)
+        k += 1
+    return out
+
+
+# ---- long lists, the candidate limit and the grid-stride loop ----------------------------------------------------------------------
+LENGTHS = (63, 64, 65, 127, 128, 129, 1000, 4097, LIMIT)
+
+
+@pytest.fixture(scope="module", params=["item", "user"])
+def long_case(request):
+    n_ids = LIMIT + 16
+    c = Case(request.param, n_ids + 8, seed=11)
+    c.by_len = {m: c.owner(np.sort(c.rng.choice(n_ids, size=m, replace=False))) for m in LENGTHS}
+    c.over = c.owner(np.sort(c.rng.choice(n_ids, size=LIMIT + 1, replace=False)))
+    c.targets = [c.target(n_ids + q, *c.rng.uniform(0.5, 5.0, 2).tolist()) for q in range(3)]
+    c.finish()
+    yield c
+    c.close()
+
+
+def test_long_lists_bit_exact(long_case):
+    """m in {63, 64, 65, 127, 128, 129, 1 000, 4 097, 16 384}: ballots, hm_grow's >= 64-slot phase and the rank / position / selection
+    loops past lane 63; knn inside, at and past every length"""
+    c = long_case
+    owners = [c.by_len[m] for m in LENGTHS for _ in c.targets]
+    targets = [t for _ in LENGTHS for t in c.targets]
+    for o, t in zip(owners, targets):  # every list entry is a candidate
+        assert c.candidates(o, t) == len(c[o])
+    c.check(owners, targets, (0, 1, 2, 20, 63, 64, 65, 128, 999, 4096, LIMIT - 1, LIMIT, 10 ** 6))
+
+
+def test_candidate_limit_refused_before_launch(long_case):
+    c = long_case
+    owners = [c.by_len[63]] * 5 + [c.over] + [c.by_len[LIMIT]] * 2
+    u, j = c.uj(owners, [c.targets[0]] * len(owners))
+    with pytest.raises(capi.CmiError) as e:
+        c.h.predict(u, j, 20, 3.25)
+    assert e.value.code == capi.E_UNSUPPORTED
+    assert "tuple 5 has %d candidates" % (LIMIT + 1) in str(e.value), str(e.value)
+    c.check([c.by_len[LIMIT]], [c.targets[0]], (20,))  # the handle still works
+
+
+def test_grid_stride_and_scratch_reuse(long_case):
+    """12 288 tuples with a 16 384-entry list among them: nwaves = min(n, 8192, 2^30 / (32 * 16 384)) = 2 048, so wave w runs tuples
+    w, w + 2 048, ...  Along each wave's sequence the lengths go long / short / empty / mid / short / long, so scratch left by a longer
+    tuple would show in the next one.  Then 9 000 tuples of short lists (n > 8 192 waves)."""
+    c = long_case
+    waves = 2048
+    pattern = [c.by_len[LIMIT], c.by_len[63], c.empty_owner, c.by_len[4097], c.by_len[129], c.by_len[LIMIT]]
+    owners = [pattern[t // waves] for t in range(len(pattern) * waves)]
+    targets = [c.targets[(t + t // waves) % 3] for t in range(len(owners))]
+    c.check(owners, targets, (0, 20, 100, 10 ** 6))
+    short = [c.by_len[63], c.by_len[64], c.empty_owner, c.by_len[65], c.by_len[127], c.by_len[128]]
+    owners = [short[t % len(short)] for t in range(9000)]
+    targets = [c.targets[(t // 7) % 3] for t in range(9000)]
+    c.check(owners, targets, (0, 20, 64))
+
+
+# ---- HashMap bins crowded on purpose -------------------------------------------------------------------------------------------------
+class Ids:
+    """hands out id blocks aligned to 512 (so residues mod 16 .. 512 are the ones chosen)"""
+
+    def __init__(self):
+        self.next = 0
+
+    def block(self, ids):
+        base = (self.next + 511) // 512 * 512
+        out = [base + k for k in ids]
+        self.next = max(out) + 1
+        return out
+
+
+@pytest.fixture(scope="module", params=["item", "user"])
+def bucket_case(request):
+    ids = Ids()
+    lists, helpers = {}, {}
+    # small tables: 9 ids = 3 (mod 16) make treeifyBin resize 16 -> 32, then 9 ids = 7 (mod 32) resize 32 -> 64, then fillers
+    lists["small"] = ids.block([3 + 16 * k for k in range(9)] + [7 + 32 * k for k in range(10, 19)] + list(range(1000, 1040)))
+    # 8 ids sharing their low 7 bits, arriving in a 128-slot table after 60 fillers (m = 68: 128 slots at the end): accepted
+    fill = spaced_ids(0, 60, 64, (5,))
+    lists["eight"] = ids.block(fill + [128 + 5 + 128 * k for k in range(8)])
+    lists["nine"] = ids.block(fill + [128 + 5 + 128 * k for k in range(9)])           # a 9th: refused
+    # 16 ids = 5 (mod 64) that the growth to 128 slots split 8 / 8 before the 9th arrives: the histogram prefilter passes them to the
+    # exact check, which must accept
+    lists["split"] = ids.block(fill + [128 + 5 + 64 * k for k in range(16)])
+    # 9 ids = 5 (mod 64), alternately 5 and 69 (mod 128), put while the table has 64 slots (after 26 fillers); 30 fillers more take
+    # it to 128 slots, where the bin would hold 5 and 4: refused all the same
+    lists["at64"] = ids.block(spaced_ids(0, 26, 64, (5,)) + [64 + 5 + 64 * k for k in range(9)] +
+                              spaced_ids(1024, 30, 64, (5,)))
+    # a treeify only in the re-put after the cut: 9 (or 8) survivors = 21 (mod 512) are the first puts (a small table: treeifyBin
+    # resizes), 200 fillers take the table to 512 slots, and the cut to knn re-puts the survivors -- the largest similarities -- into
+    # that table, all in bucket 21
+    surv9 = [21 + 512 * k for k in range(9)]
+    lists["reput9"] = ids.block(surv9 + spaced_ids(5000, 200, 64, (21,)))
+    lists["reput8"] = ids.block(surv9[:8] + spaced_ids(5000, 201, 64, (21,)))
+    helpers["reput9"] = lists["reput9"][:9]
+    helpers["reput8"] = lists["reput8"][:8]
+    # ties: 150 random ids whose helper values take 4 values (cos gives few distinct similarities)
+    rng = np.random.default_rng(5)
+    lists["ties"] = ids.block(sorted(rng.choice(4000, 150, replace=False).tolist()))
+    # filtered candidates: positive, negative, zero and unset (NaN) similarities, and ratings <= 0; an owner with none positive
+    lists["filtered"] = ids.block(list(range(0, 400, 2)))
+    lists["none"] = ids.block(list(range(0, 40)))
+    n_ent = ids.next + 8
+    c = Case(request.param, n_ent, seed=7)
+    c.lists = lists
+    c.o = {}
+    for name, L in lists.items():
+        if name.startswith("reput"):
+            c.help(L[:len(helpers[name])], 3.0, 3.0)            # cos = 1 (or its neighbour) against the target's (1, 1)
+            for e in L[len(helpers[name]):]:
+                c.help([e], 1.0, float(2 + e % 4))             # strictly smaller
+        elif name == "ties":
+            for e in L:
+                c.help([e], 1.0, float(1 + e % 4))
+        elif name in ("filtered", "none"):
+            rates = np.ones(len(L))
+            for q, e in enumerate(L):
+                kind = q % 6 if name == "filtered" else 1 + q % 4
+                if kind == 0 or kind == 5:
+                    c.help([e], 1.0 + q % 3, 2.0)               # positive
+                elif kind == 1:
+                    c.help([e], -1.0, -2.0)                     # negative
+                elif kind == 2:
+                    c.help([e], 1.0, -1.0)                      # exactly 0 against (1, 1)
+                elif kind == 3:
+                    pass                                        # no helper entry: unset (NaN)
+                else:
+                    c.help([e], 2.0, 1.0)
+                    rates[q] = 0.0 if q % 2 else -1.0           # a candidate whose rating is not > 0
+            c.o[name] = c.owner(L, rates=rates, auto_help=False)
+            continue
+        c.o[name] = c.owner(L)
+    c.t = c.target(n_ent - 1, 1.0, 1.0)
+    c.t2 = c.target(n_ent - 2, 2.0, 0.7)
+    c.t_empty = n_ent - 3   # no cells at all
+    c.finish()
+    yield c
+    c.close()
+
+
+def test_small_table_treeify_resizes(bucket_case):
+    c = bucket_case
+    L = c.lists["small"]
+    assert grown(L[:8]) == (16, 12) and grown(L[:9]) == (32, 24)      # the 9th of bin 3: treeifyBin resizes to 32 slots
+    assert grown(L[:17]) == (32, 24) and grown(L[:18]) == (64, 48)    # the 9th of bin 7 (of 32): resizes to 64
+    c.check([c.o["small"]] * 2, [c.t, c.t2], (0, 1, 5, 9, 17, 30, 10 ** 6))
+
+
+def test_eight_in_a_128_slot_bin_accepted(bucket_case):
+    c = bucket_case
+    L = np.array(c.lists["eight"])
+    assert grown(L) == (128, 96)
+    assert np.bincount(L % 128).max() == 8
+    c.check([c.o["eight"]] * 2, [c.t, c.t2], (0, 1, 8, 40, 67, 10 ** 6))
+
+
+def test_ninth_in_a_128_slot_bin_refused(bucket_case):
+    c = bucket_case
+    with pytest.raises(knn_ref.Treeified):
+        grown(c.lists["nine"])
+    assert c.refused([c.o["nine"]], [c.t], 0) == 1
+    assert c.refused([c.o["nine"]], [c.t2], 10 ** 6) == 1
+
+
+def test_bin_split_by_growth_before_the_ninth_accepted(bucket_case):
+    """the false-positive trap: 16 ids share their low 6 bits (the mod-64 prefilter fires) but sit 8 / 8 in the 128-slot table"""
+    c = bucket_case
+    L = np.array(c.lists["split"])
+    assert np.bincount(L % 64).max() == 16 and grown(L) == (128, 96)
+    c.check([c.o["split"]] * 2, [c.t, c.t2], (0, 1, 9, 16, 70, 10 ** 6))
+
+
+def test_nine_at_an_intermediate_capacity_refused(bucket_case):
+    """9 nodes in a bin of the 64-slot table; the table later grows to 128 slots, where that bin would hold only 5"""
+    c = bucket_case
+    L = np.array(c.lists["at64"])
+    assert grown(L[:26])[0] == 64 and len(L) > 48 and np.bincount(L % 128).max() == 5
+    with pytest.raises(knn_ref.Treeified):
+        grown(L)
+    assert c.refused([c.o["at64"]], [c.t], 0) == 1
+
+
+def test_treeify_only_in_the_reput_after_the_cut(bucket_case):
+    """the first fill grows cleanly to 512 slots; the cut keeps those 512 slots and re-puts the survivors, all in one bucket"""
+    c = bucket_case
+    for name, k in (("reput8", 8), ("reput9", 9)):
+        L = np.array(c.lists[name])
+        assert grown(L) == (512, 384)  # the first fill raises nothing
+        top = np.argsort(-c.srow(c.t)[L], kind="stable")[:k]
+        assert sorted(top.tolist()) == list(range(k))          # the survivors are the k smallest ids
+        assert len(set((L[:k] % 512).tolist())) == 1
+    c.check([c.o["reput8"], c.o["reput9"]], [c.t, c.t], (0, 10 ** 6))  # no cut: nothing treeifies
+    c.check([c.o["reput8"]], [c.t], (8, 9, 10))
+    assert c.refused([c.o["reput9"]], [c.t], 9) == 1
+    assert c.refused([c.o["reput9"]], [c.t], 10) == 1
+    c.check([c.o["reput9"]], [c.t], (8,))  # 8 of the 9 in bucket 21
+
+
+def test_mixed_batch_refusal_count_and_recovery(bucket_case):
+    c = bucket_case
+    good = [c.o["small"], c.o["eight"], c.o["split"], c.o["ties"], c.o["filtered"], c.o["reput8"], c.o["none"], c.empty_owner]
+    owners = good[:3] + [c.o["nine"]] + good[3:5] + [c.o["at64"], c.o["reput9"]] + good[5:] + [c.o["nine"]]
+    targets = [c.t] * len(owners)
+    assert c.refused(owners, targets, 9) == 4
+    keep = [q for q, o in enumerate(owners) if c.want(o, targets[q], 9, 3.25, False) is not None]
+    assert len(keep) == len(owners) - 4
+    c.check([owners[q] for q in keep], [targets[q] for q in keep], (9,))
+
+
+def test_ties_at_the_cut(bucket_case):
+    c = bucket_case
+    o = c.o["ties"]
+    s = c.srow(c.t)[np.array(c.lists["ties"])]
+    assert len(np.unique(s)) <= 4 and c.candidates(o, c.t) == 150
+    c.check([o, o], [c.t, c.t2], (1, 2, 37, 63, 64, 65, 66, 100, 149, 150))
+
+
+def test_filtered_candidates_and_empty_rows(bucket_case):
+    c = bucket_case
+    s = c.srow(c.t)[np.array(c.lists["filtered"])]
+    assert (s < 0).any() and (s == 0).any() and np.isnan(s).any() and c.candidates(c.o["filtered"], c.t) > 64
+    assert c.candidates(c.o["none"], c.t) == 0
+    owners = [c.o["filtered"], c.o["none"], c.empty_owner, c.o["filtered"], c.o["ties"]]
+    targets = [c.t, c.t, c.t, c.t_empty, c.t_empty]
+    for gm, lo, hi in ((3.25, 1.0, 5.0), (5.5, 1.0, 5.0), (0.5, 1.0, 5.0)):
+        c.check(owners, targets, (0, 1, 20, 64, 65), gm, lo, hi)
+        u, j = c.uj(owners[1:], targets[1:])
+        assert same_bits(c.h.predict(u, j, 20, gm), [gm] * 4)                        # exactly the global mean
+        assert same_bits(c.h.predict(u, j, 20, gm, True, lo, hi), [min(max(gm, lo), hi)] * 4)
+
+
+# ---- ids above 65 536: jhash's k ^ k >>> 16 ------------------------------------------------------------------------------------------
+HIGH_USERS = 65536 + 1024
+
+
+def test_userknn_ids_above_65536():
+    """UserKNN with 66 560 users (a 35 GB similarity matrix), where jhash(k) = k ^ 1 for the upper ids: 5 ids = 5 (mod 64) below 65 536
+    and 4 ids = 4 (mod 64) above share one bin (refused); 5 + 4 ids whose raw ids share a bin but whose hashes do not (accepted);
+    150 ids across both halves at several knn.  Measured on one MI355X: about 1 s, nearly all of it the build (the 35 GB fill included)."""
+    need = HIGH_USERS * HIGH_USERS * 8
+    import torch
+    free, _ = torch.cuda.mem_get_info()
+    if free < need + (4 << 30):
+        pytest.skip("the %d x %d similarity matrix needs %.1f GB of device memory and %.1f GB are free" %
+                    (HIGH_USERS, HIGH_USERS, need / 1e9, free / 1e9))
+    t0 = time.time()
+    c = Case("user", HIGH_USERS, seed=3)
+    fill = spaced_ids(100, 40, 64, (4, 5))
+    same_bin = fill + [5 + 64 * k for k in range(1, 6)] + [65536 + 4 + 64 * k for k in range(4)]
+    raw_bin = fill + [5 + 64 * k for k in range(1, 6)] + [65536 + 5 + 64 * k for k in range(4)]
+    rng = np.random.default_rng(9)
+    both = sorted(rng.choice(4000, 75, replace=False).tolist() + (65536 + rng.choice(900, 75, replace=False)).tolist())
+    o_same, o_raw, o_both = c.owner(sorted(same_bin)), c.owner(sorted(raw_bin)), c.owner(both)
+    t1, t2 = c.target(HIGH_USERS - 1), c.target(HIGH_USERS - 2, 2.0, 0.5)
+    c.finish()
+    try:
+        with pytest.raises(knn_ref.Treeified):
+            grown(sorted(same_bin))
+        assert grown(sorted(raw_bin)) == (128, 96)
+        c.check([o_both, o_both], [t1, t2], (0, 1, 7, 50, 149, 10 ** 6))
+        c.check([o_raw, o_raw], [t1, t2], (0, 1, 7, 48, 10 ** 6))
+        assert c.refused([o_same], [t1], 0) == 1
+    finally:
+        c.close()
+    print("ids above 65536: %.1f s (build %.1f s)" % (time.time() - t0, c.build_s))
