@@ -72,6 +72,54 @@ __device__ T ext_predict_seq(const ExtArgs<T> &a, T gm, int uu, int jj, const in
 
 constexpr int EXT_MAX_DIMS = 16;
 
+// CAMF_MCS's condition-position chain (CAMF_MCS.java:86-150) for one tuple: sets e, adds its loss terms, stores the moved
+// positions when `store`, returns the factor loop's scale 1 - dist.  The positions are T in memory, but the chain runs in double
+// for every T: the widened positions, diff, dist, the dist == 0 -> lowbound substitution, the update on the T-rounded lr, regC
+// and on e * dot formed in double, and both clips; only the stored positions round to T.  With T = float and the chain in T,
+// lowbound = 1e-100 rounds to 0: a clipped position is stored as exactly 0, upbound - lowbound rounds to upbound, two paired
+// conditions parked on one bound give dist == 0, the substituted dist is 0 again and ((e*dot)*diff)/dist is 0/0 = NaN, which
+// then spreads through every row the chain touches.  For T = double these are the reference's operations in its order.
+template <typename T>
+__device__ __forceinline__ T mcs_chain(const ExtArgs<T> &a, const int32_t *conds, T dot, T rr, T lr, T regC, bool store, T &e,
+                                       double &loss) {
+    const double lrd = lr, regCd = regC;
+    int i1[EXT_MAX_DIMS], i2[EXT_MAX_DIMS];
+    double val[EXT_MAX_DIMS];
+    int nupd = 0;
+    double dist = 0.0;
+    for (int i = 0; i < a.dmax && conds[i] >= 0 && i < a.n_empty; ++i) {
+        const int c1 = conds[i], c2 = a.empty_conds[i];
+        const double pos1 = a.cv[c1], pos2 = a.cv[c2];
+        const double diff = pos1 - pos2;
+        dist += diff * diff;
+        if (c1 != c2) {
+            i1[nupd] = c1, i2[nupd] = c2, val[nupd] = diff;
+            ++nupd;
+        }
+        loss += (regCd * pos1) * pos1 + (regCd * pos2) * pos2;
+    }
+    dist = sqrt(dist);
+    const T pred = dot * (T)(1.0 - dist);
+    e = rr - pred;
+    loss += (double)(e * e);
+    const double ed = (double)e * (double)dot;
+    for (int q = 0; q < nupd; ++q) {
+        const double pos1 = a.cv[i1[q]], pos2 = a.cv[i2[q]];
+        if (dist == 0.0) dist = a.lowbound; // sticks for the rest of the tuple (CAMF_MCS.java:121-122)
+        double p1 = pos1 + lrd * ((ed * val[q]) / dist - regCd * pos1);
+        double p2 = pos2 - lrd * ((ed * val[q]) / dist + regCd * pos2);
+        p1 = p1 < 0.0 ? a.lowbound : p1;
+        p1 = p1 > a.upbound ? a.upbound - a.lowbound : p1;
+        p2 = p2 < 0.0 ? a.lowbound : p2;
+        p2 = p2 > a.upbound ? a.upbound - a.lowbound : p2;
+        if (store) {
+            a.cv[i1[q]] = (T)p1;
+            a.cv[i2[q]] = (T)p2;
+        }
+    }
+    return (T)(1.0 - dist);
+}
+
 template <typename T, int MODEL>
 __global__ __launch_bounds__(64) void ext_serial_strict(ExtArgs<T> a, int64_t n, double *loss_out) {
     if (threadIdx.x != 0) return;
@@ -120,35 +168,7 @@ __global__ __launch_bounds__(64) void ext_serial_strict(ExtArgs<T> a, int64_t n,
         T pred = dot, scale;
         T e;
         if (MODEL == CAMF_MCS) {
-            T dist = 0;
-            for (int i = 0; i < a.dmax && conds[i] >= 0 && i < a.n_empty; ++i) {
-                const int c1 = conds[i], c2 = a.empty_conds[i];
-                const T pos1 = a.cv[c1], pos2 = a.cv[c2];
-                const T diff = pos1 - pos2;
-                dist += diff * diff;
-                if (c1 != c2) {
-                    i1[nupd] = c1, i2[nupd] = c2, val[nupd] = diff;
-                    ++nupd;
-                }
-                loss += (double)((regC * pos1) * pos1 + (regC * pos2) * pos2);
-            }
-            dist = (T)sqrt((double)dist);
-            pred *= (T)1 - dist;
-            e = rr - pred;
-            loss += (double)(e * e);
-            for (int q = 0; q < nupd; ++q) {
-                const T pos1 = a.cv[i1[q]], pos2 = a.cv[i2[q]];
-                if (dist == (T)0) dist = (T)a.lowbound; // sticks for the rest of the tuple (CAMF_MCS.java:121-122)
-                T p1 = pos1 + lr * (((e * dot) * val[q]) / dist - regC * pos1);
-                T p2 = pos2 - lr * (((e * dot) * val[q]) / dist + regC * pos2);
-                p1 = p1 < (T)0 ? (T)a.lowbound : p1;
-                p1 = p1 > (T)a.upbound ? (T)a.upbound - (T)a.lowbound : p1;
-                p2 = p2 < (T)0 ? (T)a.lowbound : p2;
-                p2 = p2 > (T)a.upbound ? (T)a.upbound - (T)a.lowbound : p2;
-                a.cv[i1[q]] = p1;
-                a.cv[i2[q]] = p2;
-            }
-            scale = (T)1 - dist;
+            scale = mcs_chain(a, conds, dot, rr, lr, regC, true, e, loss);
         } else {
             T simc = 1;
             for (int i = 0; i < a.dmax && conds[i] >= 0 && i < a.n_empty; ++i) {
@@ -254,37 +274,7 @@ __global__ __launch_bounds__(64) void ext_serial_wave(ExtArgs<T> a, int64_t n, d
         int nupd = 0;
         T pred = dot;
         if (MODEL == CAMF_MCS) {
-            T dist = 0;
-            for (int i = 0; i < a.dmax && conds[i] >= 0 && i < a.n_empty; ++i) {
-                const int c1 = conds[i], c2 = a.empty_conds[i];
-                const T pos1 = a.cv[c1], pos2 = a.cv[c2];
-                const T diff = pos1 - pos2;
-                dist += diff * diff;
-                if (c1 != c2) {
-                    i1[nupd] = c1, i2[nupd] = c2, val[nupd] = diff;
-                    ++nupd;
-                }
-                loss += (double)((regC * pos1) * pos1 + (regC * pos2) * pos2);
-            }
-            dist = (T)sqrt((double)dist);
-            pred *= (T)1 - dist;
-            e = rr - pred;
-            loss += (double)(e * e);
-            for (int q = 0; q < nupd; ++q) {
-                const T pos1 = a.cv[i1[q]], pos2 = a.cv[i2[q]];
-                if (dist == (T)0) dist = (T)a.lowbound;
-                T p1 = pos1 + lr * (((e * dot) * val[q]) / dist - regC * pos1);
-                T p2 = pos2 - lr * (((e * dot) * val[q]) / dist + regC * pos2);
-                p1 = p1 < (T)0 ? (T)a.lowbound : p1;
-                p1 = p1 > (T)a.upbound ? (T)a.upbound - (T)a.lowbound : p1;
-                p2 = p2 < (T)0 ? (T)a.lowbound : p2;
-                p2 = p2 > (T)a.upbound ? (T)a.upbound - (T)a.lowbound : p2;
-                if (lane == 0) {
-                    a.cv[i1[q]] = p1;
-                    a.cv[i2[q]] = p2;
-                }
-            }
-            scale = (T)1 - dist;
+            scale = mcs_chain(a, conds, dot, rr, lr, regC, lane == 0, e, loss);
         } else {
             T simc = 1;
             for (int i = 0; i < a.dmax && conds[i] >= 0 && i < a.n_empty; ++i) {
