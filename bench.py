@@ -4,16 +4,21 @@
 A "step" is one epoch of buildModel(): one pass of the fused gather-dot-AXPY update over every training
 tuple, through the C ABI (libcarskit_mi355x.so), with tuples and model already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|northstar|c5|small] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|northstar|c5|small] [--dump-outputs DIR] [--full]
 
 N>1 is launched by the driver through torch.distributed.run (one rank per GPU): tuples are sharded by
 user (each rank owns its own users and their ratings: weak scaling, per-GPU work fixed), the item-side
 state (Q, icBias) is replicated and the mean of the ranks' per-epoch moves is applied after a reduce-scatter +
-all-gather of one flat bucket over RCCL (carskit_amd/dist.py).  Prints ONE JSON line on rank 0:
-the BASELINE metric at fp32 state (`value`, `roofline`, `cpu_baseline`), plus -- at N=1 -- a secondary `f64` object (the same
-workload with the model kept in fp64, the reference's own precision), the part's measured ceilings (`roofline.peak_measured`) and a
-`northstar` object: the shape BASELINE.json's north_star target sentence names (10 M users x 1 M items x 64 conditions, 200 M
-ratings) timed the same way in the same run.
+all-gather of one flat bucket over RCCL (carskit_amd/dist.py).  Prints ONE JSON line on rank 0: the BASELINE metric at fp32
+state (`value`, `roofline` from the timed epochs' own HIP events).
+
+A plain run does only what that line needs: set up, warm up, time the K steps, dump the outputs, print.  --full adds, after the
+timed steps and the dump, every measurement that takes runs of its own: `cpu_baseline`; at N=1 a secondary `f64` object (the same
+workload with the model kept in fp64, the reference's own precision), the part's measured ceilings (`roofline.peak_measured`), two
+models side by side (`two_folds`), a `northstar` object (the shape BASELINE.json's north_star target sentence names: 10 M users x
+1 M items x 64 conditions, 200 M ratings, timed the same way in the same run), the C5 / C4 / evalRankings objects and the box's
+clocks; with --workload c4 the relaxed-sums form and the per-kernel roofline, with rank the one-stream kernel roofline, with
+frappe / depaul one fold alone.
 
 roofline.frac = HBM bytes the loaded SCHEDULE has to move (cmi_schedule_traffic: hub row / bias / context-bias row once per unit of
 the hub-chain schedule, spoke row + tuple stream + scalar-bias sectors per tuple) / kernel time / 8 TB/s.  SURVEY 8(d)'s no-reuse
@@ -291,8 +296,8 @@ def secondary_workload(name, steps, warmup, device, flags, regs, lr, calibrate=T
 def bench_fm(args):
     """--workload c4: one GPU's share of BASELINE configs[3] (FM k=64, 5 M users x 500 K items x 64 conditions, 200 M ratings over
     8 GPUs -> 625 K users / 25 M ratings per GPU).  A step = one ALS sweep (FM.java:148-218: 1 + 3 + 3k coordinate phases).  `value` is
-    the DEFAULT form (fixed-order sums: two runs are bit-identical, like the reference's sweep); `relaxed_sums` beside it is the opt-in
-    LDS-atomic form (CMI_FM_FLAG_RELAXED_SUMS)."""
+    the DEFAULT form (fixed-order sums: two runs are bit-identical, like the reference's sweep); with --full, `relaxed_sums` beside it is the
+    opt-in LDS-atomic form (CMI_FM_FLAG_RELAXED_SUMS) and `roofline` prices the dominant kernel, timed in runs of its own."""
     k, n_users, n_items, n = 64, 625_000, 500_000, 25_000_000
     data = synth.generate_fast(n_users, n_items, 4, 16, n)
     p = data.n_users + data.n_items + data.n_conds
@@ -322,16 +327,27 @@ def bench_fm(args):
         if flags == 0 and args.dump_outputs:          # the default form's model after the last sweep
             w0, w, V = g.get_model()
             dump_outputs(args.dump_outputs, {"w0": np.float64(w0), "w": w, "V": V})
-        # the dominant kernel: the launch of a factor's user / item phase (65 + 65 of the ~390 launches of a sweep, 85 % of its time), timed
-        # with HIP events on the instance's stream (in its non-updating form: it only writes scratch)
-        ku, ki = g.time_reduce(4 + 3 * (k // 2) + 0, 10) * 1e-3, g.time_reduce(4 + 3 * (k // 2) + 1, 10) * 1e-3
-        lay = g.layout()
+        ku = ki = lay = None
+        if args.full:
+            # the dominant kernel: the launch of a factor's user / item phase (65 + 65 of the ~390 launches of a sweep, 85 % of its time),
+            # timed with HIP events on the instance's stream (in its non-updating form: it only writes scratch)
+            ku, ki = g.time_reduce(4 + 3 * (k // 2) + 0, 10) * 1e-3, g.time_reduce(4 + 3 * (k // 2) + 1, 10) * 1e-3
+            lay = g.layout()
         g.close()
         return dt, ku, ki, lay, setup_s, model_s
 
     dt, ku, ki, lay, setup_s, model_s = timed(0)
-    rdt, rku, rki, rlay, _, _ = timed(capi.FM_FLAG_RELAXED_SUMS)
     phases = 4 + 3 * k
+    config = {"workload": "c4 share: FM k=%d, %d users x %d items x %d conditions, %d ratings (one GPU of BASELINE configs[3])"
+                          % (k, data.n_users, data.n_items, data.n_conds, data.n), "phases_per_sweep": phases,
+              "form": "default: fixed-order sums, bit-reproducible (fm_cell_kernel)",
+              "setup_s": setup_s, "set_model_and_init_s": model_s}
+    out = {"metric": "FM ALS rating-sweeps/sec, k=%d" % k, "value": data.n / dt, "unit": "rating-sweeps/s", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+           "data": "synthetic", "config": config}
+    if not args.full:
+        return out
+    rdt, rku, rki, rlay, _, _ = timed(capi.FM_FLAG_RELAXED_SUMS)
     # Bytes = what THIS implementation has to move per launch (cmi_fm_layout: 12-byte records streamed once, the coordinates' table entries
     # and sums, one L2 fill of every table slice per XCD) -- not the reference algorithm's errors[] + Q traffic, which it never generates.
     bytes_launch = 0.5 * (lay["bytes_reduce_user"] + lay["bytes_reduce_item"])
@@ -351,33 +367,26 @@ def bench_fm(args):
         except Exception:
             continue
     ref_bytes = 16 * (3 + 3 * k) + 16 * 3 * k
-    out = {"metric": "FM ALS rating-sweeps/sec, k=%d" % k, "value": data.n / dt, "unit": "rating-sweeps/s", "n_gpus": 1, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-           "data": "synthetic",
-           "config": {"workload": "c4 share: FM k=%d, %d users x %d items x %d conditions, %d ratings (one GPU of BASELINE configs[3])"
-                                  % (k, data.n_users, data.n_items, data.n_conds, data.n), "phases_per_sweep": phases,
-                      "form": "default: fixed-order sums, bit-reproducible (fm_cell_kernel)",
-                      "setup_s": setup_s, "set_model_and_init_s": model_s},
-           "relaxed_sums": {"form": "CMI_FM_FLAG_RELAXED_SUMS: LDS-atomic sums, last bits vary run to run (fm_cell_atomic_kernel)",
-                            "value": data.n / rdt, "unit": "rating-sweeps/s", "ms_per_step": rdt * 1e3,
-                            "kernel_us": {"user_field": rku * 1e6, "item_field": rki * 1e6},
-                            "frac": rbytes_launch / rkern / 1e9 / HBM_PEAK_GBS},
-           "roofline": {"bound": "hbm", "achieved": bytes_launch / kern / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                        "frac": bytes_launch / kern / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
-                        "traffic_GBps": traffic / kern / 1e9 if traffic else None, "traffic_over_model": traffic / bytes_launch if traffic else None,
-                        "kernel": "fm_cell_kernel<0|1> (one factor's user / item phase, the default fixed-order form; fm_cell_atomic_kernel under "
-                                  "CMI_FM_FLAG_RELAXED_SUMS: see relaxed_sums)",
-                        "kernel_us": {"user_field": ku * 1e6, "item_field": ki * 1e6}, "bytes_per_launch": bytes_launch,
-                        "bytes_per_rating_phase": bytes_launch / data.n,
-                        "bytes_model": "this implementation's own traffic per launch (cmi_fm_layout): records 12 B x %d, "
-                                       "coordinate entries + sums, table-slice fills; the reference ALGORITHM's errors[] + Q traffic would be %d B per "
-                                       "rating-sweep (never generated here)" % (data.n, ref_bytes),
-                        "whole_sweep_GBps": sweep_bytes / dt / 1e9, "whole_sweep_frac": sweep_bytes / dt / 1e9 / HBM_PEAK_GBS,
-                        "limiter": "the memory pattern: 2.3 M stream lines from HBM + 8.3 M gather lines from L2 per launch (3 lanes per line) "
-                                   "against ~400 outstanding lines per CU: time ~ sum(lines x latency) / (256 x 400), which also gives the "
-                                   "stream-only (59 us) and lone-gather (119 us) microbenchmarks (tools/micro/gather16.hip; DESIGN.md 5); the "
-                                   "fixed-order form adds the parking of a batch's products in LDS and its walk (+ ~11 %)",
-                        "layout": lay, "avg_phase_us": dt * 1e6 / phases}}
+    out["relaxed_sums"] = {"form": "CMI_FM_FLAG_RELAXED_SUMS: LDS-atomic sums, last bits vary run to run (fm_cell_atomic_kernel)",
+                           "value": data.n / rdt, "unit": "rating-sweeps/s", "ms_per_step": rdt * 1e3,
+                           "kernel_us": {"user_field": rku * 1e6, "item_field": rki * 1e6},
+                           "frac": rbytes_launch / rkern / 1e9 / HBM_PEAK_GBS}
+    out["roofline"] = {"bound": "hbm", "achieved": bytes_launch / kern / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": bytes_launch / kern / 1e9 / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": tsrc,
+                       "traffic_GBps": traffic / kern / 1e9 if traffic else None, "traffic_over_model": traffic / bytes_launch if traffic else None,
+                       "kernel": "fm_cell_kernel<0|1> (one factor's user / item phase, the default fixed-order form; fm_cell_atomic_kernel under "
+                                 "CMI_FM_FLAG_RELAXED_SUMS: see relaxed_sums)",
+                       "kernel_us": {"user_field": ku * 1e6, "item_field": ki * 1e6}, "bytes_per_launch": bytes_launch,
+                       "bytes_per_rating_phase": bytes_launch / data.n,
+                       "bytes_model": "this implementation's own traffic per launch (cmi_fm_layout): records 12 B x %d, "
+                                      "coordinate entries + sums, table-slice fills; the reference ALGORITHM's errors[] + Q traffic would be %d B per "
+                                      "rating-sweep (never generated here)" % (data.n, ref_bytes),
+                       "whole_sweep_GBps": sweep_bytes / dt / 1e9, "whole_sweep_frac": sweep_bytes / dt / 1e9 / HBM_PEAK_GBS,
+                       "limiter": "the memory pattern: 2.3 M stream lines from HBM + 8.3 M gather lines from L2 per launch (3 lanes per line) "
+                                  "against ~400 outstanding lines per CU: time ~ sum(lines x latency) / (256 x 400), which also gives the "
+                                  "stream-only (59 us) and lone-gather (119 us) microbenchmarks (tools/micro/gather16.hip; DESIGN.md 5); the "
+                                  "fixed-order form adds the parking of a batch's products in LDS and its walk (+ ~11 %)",
+                       "layout": lay, "avg_phase_us": dt * 1e6 / phases}
     return out
 
 
@@ -385,9 +394,10 @@ def bench_frappe(args):
     """--workload frappe: BASELINE configs[1]'s data set the way the reference runs it -- `cv -k F -p on`, F recommender instances side by
     side (CARSKit.java:395-412: one Java thread per fold) -- on ONE GPU: F instances of --model (default CAMF_C, k=64) on F streams, each
     training on the tuples outside its fold of the real Frappe file (tests/golden/frappe_compact.csv.gz through the product's DataTransformer
-    + DataDAO; rating = 1 + log10(count), the scale the tests train on).  value = aggregate updates/s of the F concurrent folds; cpu_baseline
-    = the C restatement on the same folds, one core and F threads.  These models are ONE dependent chain per instance (every rating updates
-    parameters every other rating reads): the bound is the chain's latency, not HBM -- the roofline object says so."""
+    + DataDAO; rating = 1 + log10(count), the scale the tests train on).  value = aggregate updates/s of the F concurrent folds; with --full,
+    cpu_baseline = the C restatement on the same folds, one core and F threads, and config gets one fold timed alone.  These models are ONE
+    dependent chain per instance (every rating updates parameters every other rating reads): the bound is the chain's latency, not HBM --
+    the roofline object says so."""
     import gzip
     import math
     import tempfile
@@ -454,11 +464,6 @@ def bench_frappe(args):
         dump_outputs(args.dump_outputs, outs)
     one_ms = float(np.mean([i.last_epoch_ms() for i, _, _, _ in folds]))
     total = sum(tr.n for _, tr, _, _ in folds)
-    # one instance alone (no neighbours): what a fold costs when the GPU has nothing else to do
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        folds[0][0].train_epoch(lr)
-    alone = (time.perf_counter() - t0) / args.steps
     bpu = algorithmic_bytes("CAMF_C", k, 8, 4)
     out = {"metric": "SGD rating-updates/sec, %s k=%d, %d concurrent folds" % (model, k, F), "value": total * args.steps / el, "unit": "rating-updates/s",
            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
@@ -468,7 +473,6 @@ def bench_frappe(args):
                                   "concurrently on one GPU, each on the tuples outside its fold (%d per fold)"
                                   % (args.workload, model, k, "DePaulMovie" if depaul else "Frappe", d.n_users, d.n_items, d.n_conds, d.n, F, folds[0][1].n),
                       "concurrent_folds": F, "schedule": folds[0][0].schedule_info()["kind"],
-                      "one_fold_alone_ms_per_epoch": alone * 1e3, "one_fold_alone_updates_per_s": folds[0][1].n / alone,
                       "fold_epoch_ms_while_concurrent": one_ms},
            "roofline": {"bound": "hbm", "achieved": total * args.steps * bpu / el / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": total * args.steps * bpu / el / 1e9 / HBM_PEAK_GBS, "traffic": None,
@@ -476,7 +480,14 @@ def bench_frappe(args):
                         "limiter": "latency of ONE dependent chain per instance (every rating updates parameters every other rating reads: "
                                    "CAMF_C's condBias, the similarity models' shared tables); the whole model is a few MB and cache-resident, "
                                    "HBM is idle -- the fraction is reported for form, the comparison that matters is cpu_baseline"}}
-    if not args.no_cpu_baseline:
+    if args.full:
+        # one instance alone (no neighbours): what a fold costs when the GPU has nothing else to do
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            folds[0][0].train_epoch(lr)
+        alone = (time.perf_counter() - t0) / args.steps
+        out["config"].update(one_fold_alone_ms_per_epoch=alone * 1e3, one_fold_alone_updates_per_s=folds[0][1].n / alone)
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, k, d, None, 0.0, regs, lr, 0, fold_sets=[(tr, st, gm) for _, tr, st, gm in folds], sim=sim)
         out["vs_cpu_folds"] = out["value"] / out["cpu_baseline"]["five_fold"]["value"]
     for i, _, _, _ in folds:
@@ -626,21 +637,22 @@ def bench_rank(args):
     nq = res["n_queries"]
     if args.dump_outputs:           # the measures of the last evaluation
         dump_outputs(args.dump_outputs, {m: np.float64(v) for m, v in res.items()})
-    # the two kernels ON THEIR OWN: in the timed evaluations the selection of batch b runs beside the contraction of batch b + 1 (two
-    # streams), so their HIP-event times overlap and stretch each other; the roofline prices the contraction alone (one stream)
-    overlapped = dict(kern)
-    os.environ["CMI_RANK_ONE_STREAM"] = "1"
-    try:
-        one_dev = []
-        for _ in range(3):
-            inst.eval_rankings(tr, te, bin_thold=2.5, num_recs=10)
-            one_dev.append(inst.last_rank_ms()[0])
-            kern = inst.last_rank_kernel_ms()
-    finally:
-        del os.environ["CMI_RANK_ONE_STREAM"]
+    if args.full:
+        # the two kernels ON THEIR OWN: in the timed evaluations the selection of batch b runs beside the contraction of batch b + 1 (two
+        # streams), so their HIP-event times overlap and stretch each other; the roofline prices the contraction alone (one stream)
+        overlapped = dict(kern)
+        os.environ["CMI_RANK_ONE_STREAM"] = "1"
+        try:
+            one_dev = []
+            for _ in range(3):
+                inst.eval_rankings(tr, te, bin_thold=2.5, num_recs=10)
+                one_dev.append(inst.last_rank_ms()[0])
+                kern = inst.last_rank_kernel_ms()
+        finally:
+            del os.environ["CMI_RANK_ONE_STREAM"]
     n_cand = int(len(np.unique(train.j)))
     # value = queries / WALL time of the whole cmi_eval_rankings call (plan + uploads + scoring + lists back + measures), timed
-    # around the C-ABI call on the host; the roofline object prices the device scoring loop (HIP events) against the f32 MFMA peak
+    # around the C-ABI call on the host; the roofline object (--full) prices the device scoring loop (HIP events) against the f32 MFMA peak
     out = {"metric": "evalRankings queries/sec, %s k=%d" % (model, k), "value": nq / wall, "unit": "queries/s", "n_gpus": 1,
            "steps": args.steps, "warmup": args.warmup, "ms_per_step": wall * 1e3, "higher_is_better": True, "scaling": "weak",
            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -650,13 +662,14 @@ def bench_rank(args):
                       "host_ms_breakdown_last_step": inst.last_rank_host_ms(),
                       "note": "value = queries / host wall clock of the whole call: the plan (candidates, queries, exclusions; host threads), "
                               "uploads, the device scoring loop, and the per-query measures computed batch by batch behind the device"},
-           "roofline": rank_roofline(nq, n_cand, dev, flops, kern),
            "AUC10": res["AUC10"]}
-    out["roofline"]["kernel_ms_while_overlapped"] = overlapped
-    out["roofline"]["device_ms_one_stream"] = float(np.mean(one_dev[1:]))
-    out["roofline"]["timing"] = ("contraction and selection timed on ONE stream (CMI_RANK_ONE_STREAM=1, HIP events around their launches, summed over the "
-                                 "batches of an evaluation); the timed evaluations overlap them on two streams (kernel_ms_while_overlapped)")
-    if not args.no_cpu_baseline:
+    if args.full:
+        out["roofline"] = rank_roofline(nq, n_cand, dev, flops, kern)
+        out["roofline"]["kernel_ms_while_overlapped"] = overlapped
+        out["roofline"]["device_ms_one_stream"] = float(np.mean(one_dev[1:]))
+        out["roofline"]["timing"] = ("contraction and selection timed on ONE stream (CMI_RANK_ONE_STREAM=1, HIP events around their launches, summed over "
+                                     "the batches of an evaluation); the timed evaluations overlap them on two streams (kernel_ms_while_overlapped)")
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(model, k, train, state, float(train.r.mean()), (1e-4, 1e-4, 1e-4, 1e-3), 0.0, 0, rank_queries=(test, 200))
     inst.close()
     return out
@@ -691,6 +704,10 @@ def main():
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS) + ["c4", "rank", "frappe", "depaul"],
                     help="c3 (default) / northstar / c5 / small: the SGD hot path; c4: one GPU's share of the FM configuration (ALS sweep); "
                          "rank: evalRankings (top-N scoring on the f32 matrix cores)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement: CPU baseline, fp64 leg, HBM calibration, two "
+                         "models side by side, north_star shape, C5 / C4 / evalRankings objects, box clocks, per-kernel rooflines "
+                         "(~1.5 min for the default workload); the --no-* options below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-tuples", type=int, default=20_000_000)
     ap.add_argument("--no-f64", action="store_true", help="skip the secondary fp64-state measurement")
@@ -942,10 +959,12 @@ def main():
                                          "bytes_per_epoch_all_ranks": total_sched_bytes}
         for o in extra:
             o.close()
-        if world == 1 and not args.no_calibration:
+        # --full: what the headline figure does not need, each part in runs of its own after the timed steps and the dump
+        full = world == 1 and args.full
+        if full and not args.no_calibration:
             inst.synchronize()
             with_measured(out["roofline"], local_rank)
-        if world == 1 and args.folds == 1 and args.workload == "c3" and not args.no_extras and not args.item_zipf and trainer is None:
+        if full and args.folds == 1 and args.workload == "c3" and not args.no_extras and not args.item_zipf and trainer is None:
             # secondary line: TWO independent models of the same workload side by side on this GPU (two instances, two streams, two host
             # threads: the reference's `cv -p on`, CARSKit.java:395-412).  The second model fills the first one's level boundaries
             # (285 dependent launches per epoch, each with its pipeline ramp and drain): what a lone model's order-exact schedule leaves idle
@@ -973,7 +992,7 @@ def main():
                 other.close()
             except Exception as e:
                 out["two_folds"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_f64 and args.folds == 1:
+        if full and not args.no_f64 and args.folds == 1:
             # secondary line: the same workload with the model kept in fp64 on the GPU (the reference's precision)
             try:
                 inst.close()
@@ -989,12 +1008,12 @@ def main():
                 with_measured(out["f64"]["roofline"], local_rank, not args.no_calibration)
             except Exception as e:
                 out["f64"] = {"value": None, "error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(model, k, data, state, gm, regs, lr, args.cpu_tuples)
             except Exception as e:  # the oracle is only the reported baseline, never the product path
                 out["cpu_baseline"] = {"value": None, "error": repr(e)}
-        if world == 1 and args.folds == 1 and args.workload == "c3" and not args.no_northstar and not args.item_zipf:
+        if full and args.folds == 1 and args.workload == "c3" and not args.no_northstar and not args.item_zipf:
             # the shape the north_star target sentence is quoted on, driver-timed in the same run
             try:
                 inst.close()
@@ -1023,7 +1042,7 @@ def main():
                         raise
                     except Exception as e:
                         out[key] = {"value": None, "error": repr(e)}
-        if world == 1:
+        if full:
             out["box"] = box_state()     # read right after the timed work, clocks still up
             # the driver's record keeps `config`, `roofline` and `cpu_baseline` and drops every other key of the line: the secondary
             # workloads timed in this same run travel as five numbers each inside config; the full objects stay at
@@ -1042,6 +1061,7 @@ def main():
                                                  "traffic_over_model": None}
             if sec:
                 out["config"]["secondary"] = sec
+        if world == 1:
             out["roofline"]["note"] = ("frac = schedule-model bytes (what this schedule has to move: hub rows once per unit, spoke rows once per tuple) "
                                        "/ HIP-event kernel time / 8 TB/s; SURVEY 8(d)'s zero-reuse bytes_per_update_algorithmic exceed what the "
                                        "schedule moves (hub rows stay on chip for ~4.5 tuples), so frac_algorithmic may exceed 1 without any "

@@ -4,10 +4,10 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 O=gpurun_out/r06_folds.jsonl; : > $O
 for m in CAMF_C CAMF_CI BiasedMF CAMF_CU CAMF_CUCI; do
   for f in 1 5; do
-    timeout 600 python bench.py --workload frappe --model $m --folds $f --steps 10 --warmup 2 2>/dev/null | tail -1 >> $O
+    timeout 600 python bench.py --full --workload frappe --model $m --folds $f --steps 10 --warmup 2 2>/dev/null | tail -1 >> $O
   done
 done
-timeout 600 python bench.py --workload depaul --folds 5 --steps 10 --warmup 2 2>/dev/null | tail -1 >> $O
+timeout 600 python bench.py --full --workload depaul --folds 5 --steps 10 --warmup 2 2>/dev/null | tail -1 >> $O
 python - <<'PY'
 import json
 for l in open("gpurun_out/r06_folds.jsonl"):

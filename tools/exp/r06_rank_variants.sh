@@ -6,7 +6,7 @@ O=gpurun_out/r06_rank_var; mkdir -p $O
 for r in 1 2; do
   for v in ${VARS:-base}; do
     lib=carskit_amd/lib/var/lib$v.so; [ $v = base ] && lib=carskit_amd/lib/libcarskit_mi355x.so
-    CMI_LIB_PATH=$PWD/$lib python bench.py --workload rank --steps 8 --warmup 2 > $O/${v}_$r.json 2> $O/${v}_$r.err
+    CMI_LIB_PATH=$PWD/$lib python bench.py --full --workload rank --steps 8 --warmup 2 > $O/${v}_$r.json 2> $O/${v}_$r.err
   done
 done
 python - <<'P'

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/rank_sel
 mkdir -p $out
-args=(--workload rank --steps 3 --warmup 1 --no-cpu-baseline)
+args=(--workload rank --steps 3 --warmup 1 --full --no-cpu-baseline)
 for form in tile slab; do
   [ $form = slab ] && export CMI_RANK_NO_TILE=1
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/${form}_stats -o s -- python bench.py "${args[@]}" > $out/${form}_stats.log 2>&1

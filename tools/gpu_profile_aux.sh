@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 for wl in c4 rank; do
   out=$PWD/gpurun_out/prof_${tag}_${wl}
   mkdir -p $out
-  args=(--workload $wl --steps 3 --warmup 1)
+  args=(--workload $wl --steps 3 --warmup 1 --full)
   python bench.py "${args[@]}" > $out/bench.json 2> $out/bench.err
   timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o stats -- python bench.py "${args[@]}" --no-cpu-baseline > $out/stats.log 2>&1
   if [ $wl = rank ]; then
