@@ -646,19 +646,13 @@ bool has_chain_path(int model, int k, int dmax, int n_conds, bool f64, bool stri
 }
 
 size_t chain_lds_bytes(int model, int n_conds, int dmax, bool f64, bool hub_is_item) {
-    const bool has_ic = model == CAMF_CI || model == CAMF_CUCI, has_uc = model == CAMF_CU || model == CAMF_CUCI;
-    const bool hc = hub_is_item ? has_ic : has_uc;
-    const bool has_ctx = model != BIASEDMF && model != PMF;
-    return 16 * chain_group_lds(hc ? n_conds : 0, has_ctx ? dmax : 0, f64 ? 8 : 4);
+    const ModelParams mp = model_params(model);
+    const bool hc = hub_is_item ? mp.has_ic : mp.has_uc;
+    return 16 * chain_group_lds(hc ? n_conds : 0, mp.has_ctx ? dmax : 0, f64 ? 8 : 4);
 }
 
-// lanes per unit of the small-k kernel (as small_lpt in mf_sgd_kernels.hip): LPT >= dmax and 4 * LPT >= k
-static int chain_small_lpt(int k, int dmax) {
-    if (k <= 16 && dmax <= 4) return 4;
-    if (k <= 32 && dmax <= 8) return 8;
-    return 16;
-}
-int chain_groups_per_block(int k, int dmax, bool f64) { return (!f64 && k < 64) ? 256 / chain_small_lpt(k, dmax) : 16; }
+// the small-k kernel has a unit per small_lpt lanes
+int chain_groups_per_block(int k, int dmax, bool f64) { return (!f64 && k < 64) ? 256 / small_lpt(k, dmax) : 16; }
 int chain_level_blocks(int k, int dmax, bool f64, int count) {
     const int g = chain_groups_per_block(k, dmax, f64);
     return (count + g - 1) / g;
@@ -692,18 +686,6 @@ static void *chain_kernel_k(int k, bool hub_is_item) {
     return nullptr;
 }
 
-template <typename T>
-static void *chain_kernel_ptr(int model, int k, bool hub_is_item) {
-    switch (model) {
-    case BIASEDMF: return chain_kernel_k<T, BIASEDMF>(k, hub_is_item);
-    case PMF: return chain_kernel_k<T, PMF>(k, hub_is_item);
-    case CAMF_CI: return chain_kernel_k<T, CAMF_CI>(k, hub_is_item);
-    case CAMF_CU: return chain_kernel_k<T, CAMF_CU>(k, hub_is_item);
-    case CAMF_CUCI: return chain_kernel_k<T, CAMF_CUCI>(k, hub_is_item);
-    }
-    return nullptr;
-}
-
 template <int MODEL, int LPT>
 static void *chain_small_hub(bool hub_is_item) {
     return hub_is_item ? (void *)sgd_chain_small<MODEL, LPT, true> : (void *)sgd_chain_small<MODEL, LPT, false>;
@@ -716,16 +698,6 @@ static void *chain_small_lpt_ptr(int lpt, bool hub_is_item) {
     default: return chain_small_hub<MODEL, 16>(hub_is_item);
     }
 }
-static void *chain_small_ptr(int model, int lpt, bool hub_is_item) {
-    switch (model) {
-    case BIASEDMF: return chain_small_lpt_ptr<BIASEDMF>(lpt, hub_is_item);
-    case PMF: return chain_small_lpt_ptr<PMF>(lpt, hub_is_item);
-    case CAMF_CI: return chain_small_lpt_ptr<CAMF_CI>(lpt, hub_is_item);
-    case CAMF_CU: return chain_small_lpt_ptr<CAMF_CU>(lpt, hub_is_item);
-    case CAMF_CUCI: return chain_small_lpt_ptr<CAMF_CUCI>(lpt, hub_is_item);
-    }
-    return nullptr;
-}
 
 template <typename T>
 hipError_t launch_chain_level(const SgdArgs<T> &a, const LaunchCfg &cfg, bool hub_is_item, const int32_t *unit_off, int64_t ubegin,
@@ -733,7 +705,10 @@ hipError_t launch_chain_level(const SgdArgs<T> &a, const LaunchCfg &cfg, bool hu
     if (count <= 0) return hipSuccess;
     const bool f64 = sizeof(T) == 8;
     const int groups = chain_groups_per_block(a.k, a.dmax, f64);
-    void *fn = (!f64 && a.k < 64) ? chain_small_ptr(cfg.model, 256 / groups, hub_is_item) : chain_kernel_ptr<T>(cfg.model, a.k, hub_is_item);
+    void *fn = dispatch_model<ModelSet::PARALLEL>(cfg.model, (void *)nullptr, [&](auto m) {
+        constexpr int MODEL = decltype(m)::value;
+        return (!f64 && a.k < 64) ? chain_small_lpt_ptr<MODEL>(256 / groups, hub_is_item) : chain_kernel_k<T, MODEL>(a.k, hub_is_item);
+    });
     if (!fn) return hipErrorInvalidValue;
     SgdArgs<T> args = a;
     void *params[] = {&args, &unit_off, &ubegin, &count, &slot0};

@@ -117,9 +117,9 @@ static void free_ratings(cmi_instance *h) {
                    (void **)&h->d_sr, (void **)&h->d_loss_part, (void **)&h->d_flow_err, (void **)&h->d_tail_off, (void **)&h->d_blk_off,
                    (void **)&h->d_unit_off, (void **)&h->d_ui_ptr, (void **)&h->d_ui_items, (void **)&h->d_own_recs, (void **)&h->d_own_off,
                    (void **)&h->d_tagged});
-    h->owner = false;
+    h->sched = Sched::NONE;
+    h->level_kernel = LevelKernel::GENERIC;
     h->owner_stalled = false;
-    h->chain = false;
     h->n_units = 0;
     h->blk_off.clear();
     h->n_launches = h->n_tail = 0;
@@ -191,10 +191,8 @@ extern "C" int cmi_create(int model, int k, int n_users, int n_items, int n_cond
     h->device = device;
     h->flags = flags;
     h->f64 = flags & CMI_FLAG_STATE_F64;
-    h->serial = flags & CMI_FLAG_SCHED_SERIAL;
     h->strict = flags & CMI_FLAG_STRICT;
     h->use_graph = !(flags & CMI_FLAG_NO_GRAPH);
-    h->want_owner = flags & CMI_FLAG_SCHED_OWNER;
     const char *step = "";
     hipError_t e = hipSuccess;
 #define TRY(x)                                                                                          \
@@ -520,7 +518,6 @@ static bool try_chain(cmi_instance *h, int64_t n, const int32_t *u, const int32_
         free_keep(keep);
         return false;
     }
-    h->chain = true;
     h->chain_hub_item = csch.hub_is_item != 0;
     h->n_units = csch.n_units();
     return true;
@@ -625,17 +622,14 @@ static int validate_ratings(cmi_instance *h, const RatingsIn &in, int &dmax) {
     return CMI_OK;
 }
 
-// stage 2a: the level launch forms, and the schedule flags checked against the kernels that exist.  chain_ok = a hub-chain kernel
-// exists and no flag rules it out
+// stage 2a: the schedule flags checked against the kernels that exist.  chain_ok = a hub-chain kernel exists and no flag rules it out
 static int check_schedule_flags(cmi_instance *h, int dmax, bool &chain_ok) {
-    const LaunchCfg cfg{h->model, h->strict};
-    h->fast = !h->serial && has_fast_path(h->k, dmax, h->f64, cfg);
-    h->small = !h->serial && !h->fast && has_small_path(h->k, dmax, h->f64, cfg);
-    chain_ok = !h->serial && !h->want_owner && !(h->flags & CMI_FLAG_NO_CHAIN) && has_chain_path(h->model, h->k, dmax, h->n_conds, h->f64, h->strict);
+    const bool serial = h->flags & CMI_FLAG_SCHED_SERIAL, owner = h->flags & CMI_FLAG_SCHED_OWNER;
+    chain_ok = !serial && !owner && !(h->flags & CMI_FLAG_NO_CHAIN) && has_chain_path(h->model, h->k, dmax, h->n_conds, h->f64, h->strict);
     if ((h->flags & CMI_FLAG_SCHED_CHAIN) && !chain_ok)
         CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: CMI_FLAG_SCHED_CHAIN: no hub-chain kernel for model %d, k=%d, %s state%s (or another "
                  "schedule flag is set)", h->model, h->k, h->f64 ? "fp64" : "fp32", h->strict ? ", strict" : "");
-    if (h->want_owner && (h->serial || !has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict)))
+    if (owner && (serial || !has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict)))
         CMI_FAIL(h, CMI_E_UNSUPPORTED, "set_ratings: CMI_FLAG_SCHED_OWNER: no owner kernel for model %d, k=%d, %d conditions, %s state%s (or "
                  "another schedule flag is set)", h->model, h->k, h->n_conds, h->f64 ? "fp64" : "fp32", h->strict ? ", strict" : "");
     return CMI_OK;
@@ -691,21 +685,44 @@ static bool owner_pays_off(int model, int k, int n_conds, bool f64, int32_t n_us
     return est_levels >= 2.0 * est_owner;
 }
 
-// stage 2b: which schedule runs -- serial when asked for, the hub-chain levels when they are wide (try_chain sets h->chain), the owner
-// epoch when forced or when the cost model picks it, the plain levels otherwise -- and the note when a slower one runs than the data
-// calls for.  Returns whether the owner epoch runs.
-static bool choose_schedule(cmi_instance *h, const RatingsIn &in, bool chain_ok, ChainSchedule &csch, ChainDeviceKeep &keep) {
+// CAMF_C's conflict-free CRS blocks (consecutive tuples sharing no user and no item, <= 64 -- see sgd_camfc_blocks) into h->blk_off
+// when its kernel takes this configuration and the blocks are long enough to beat the serial wave
+static bool camfc_blocks(cmi_instance *h, const RatingsIn &in, int dmax) {
+    const int64_t n = in.n;
+    h->blk_off.clear();
+    if (h->model != CMI_MODEL_CAMF_C || h->strict || h->k > 256 || dmax > 16 || n <= 0 || n >= ((int64_t)1 << 31) ||
+        camfc_blocks_lds(h->n_conds, dmax, esize(h)) > 64 * 1024 || getenv("CMI_NO_CAMFC_BLOCKS"))
+        return false;
+    std::vector<int32_t> off;
+    build_conflict_free_blocks(n, in.u, in.j, h->n_users, h->n_items, 64, off);
+    // shorter runs: the serial wave is faster -- the pipelined one (camfc_pipe.hip, 0.55-0.63 us per tuple at any run length)
+    // breaks even with the block kernel (about 1.3 us per block + 0.28 us per tuple) near 5 tuples per block, the one-ahead
+    // wave near 3 (tests/tools/bench_camfc_paths.py)
+    const double min_run = camfc_pipe_supported(h->k, h->n_conds, dmax) ? 5.0 : 3.0;
+    if ((double)n / (double)(off.size() - 1) < min_run) return false;
+    h->blk_off.swap(off);
+    return true;
+}
+
+// stage 2b: which schedule runs -- serial when asked for (CAMF_C's blocks when they pay), the hub-chain levels when they are wide
+// (try_chain), the owner epoch when forced or when the cost model picks it, the plain levels otherwise -- and the note when a slower
+// one runs than the data calls for
+static Sched choose_schedule(cmi_instance *h, const RatingsIn &in, int dmax, bool chain_ok, ChainSchedule &csch, ChainDeviceKeep &keep) {
     const int64_t n = in.n;
     h->sched_note.clear();
-    if (chain_ok && n > 0 && try_chain(h, n, in.u, in.j, csch, keep)) return false;
-    if (h->want_owner) return true;
-    if (h->serial) return false;
+    if (h->flags & CMI_FLAG_SCHED_SERIAL) {
+        if (is_ext_model(h->model)) return Sched::EXT_SERIAL;
+        return camfc_blocks(h, in, dmax) ? Sched::CAMFC_BLOCKS : Sched::SERIAL;
+    }
+    if (chain_ok && n > 0 && try_chain(h, n, in.u, in.j, csch, keep)) return Sched::CHAIN;
+    if (h->flags & CMI_FLAG_SCHED_OWNER) return Sched::OWNER;
     const bool owner_kernel = has_owner_path(h->model, h->k, h->n_conds, h->f64, h->strict);
     if (n >= ((int64_t)1 << 16) && !owner_kernel && !(h->flags & CMI_FLAG_NO_OWNER))
         h->sched_note = "narrow dependency levels on a large data set (heavy-tailed degrees?) and no owner kernel for this configuration "
                         "(limits: <= 384 conditions, k <= 256 (fp64: 128)): the level walk runs -- order-exact, roughly 10x slower on such data";
-    if (n < ((int64_t)1 << 16) || !owner_kernel || (h->flags & (CMI_FLAG_SCHED_CHAIN | CMI_FLAG_NO_OWNER))) return false;
-    return owner_pays_off(h->model, h->k, h->n_conds, h->f64, h->n_users, h->n_items, n, in.u, in.j, h->sched_note);
+    if (n < ((int64_t)1 << 16) || !owner_kernel || (h->flags & (CMI_FLAG_SCHED_CHAIN | CMI_FLAG_NO_OWNER))) return Sched::LEVELS;
+    return owner_pays_off(h->model, h->k, h->n_conds, h->f64, h->n_users, h->n_items, n, in.u, in.j, h->sched_note) ? Sched::OWNER
+                                                                                                                     : Sched::LEVELS;
 }
 
 // stage 3: the owners' lists and the teams.  The owners must all be resident: as many as the device holds wavefronts of the kernel
@@ -773,7 +790,6 @@ static int build_owner_lists(cmi_instance *h, const RatingsIn &in, OwnerSchedule
         }
         h->n_team = t;
     }
-    h->owner = true;
     h->owner_hub_item = osch.hub_is_item != 0;
     h->n_owners = waves;
     const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
@@ -791,25 +807,16 @@ static int build_owner_lists(cmi_instance *h, const RatingsIn &in, OwnerSchedule
     return CMI_OK;
 }
 
-// stage 4a: the levels of the serial, hub-chain and plain forms (the serial form: one level in input order, and CAMF_C's
-// conflict-free CRS blocks -- consecutive tuples sharing no user and no item, <= 64 -- see sgd_camfc_blocks)
-static int build_levels(cmi_instance *h, const RatingsIn &in, int dmax, ChainSchedule &csch, LevelSchedule &sch) {
+// whether the epoch walks the tuples in input order (the serial forms: no schedule permutation)
+static bool in_input_order(Sched s) { return s == Sched::SERIAL || s == Sched::CAMFC_BLOCKS || s == Sched::EXT_SERIAL; }
+
+// stage 4a: the levels of the serial, hub-chain and plain forms (the serial forms: one level in input order)
+static int build_levels(cmi_instance *h, const RatingsIn &in, ChainSchedule &csch, LevelSchedule &sch) {
     const int64_t n = in.n;
-    if (h->serial) {
+    if (in_input_order(h->sched)) {
         sch.level_off = {0, n};
         sch.max_level = n;
-        h->blk_off.clear();
-        if (h->model == CMI_MODEL_CAMF_C && !h->strict && h->k <= 256 && dmax <= 16 && n > 0 && n < ((int64_t)1 << 31) &&
-            camfc_blocks_lds(h->n_conds, dmax, esize(h)) <= 64 * 1024 && !getenv("CMI_NO_CAMFC_BLOCKS")) {
-            std::vector<int32_t> off;
-            build_conflict_free_blocks(n, in.u, in.j, h->n_users, h->n_items, 64, off);
-            // shorter runs: the serial wave is faster -- the pipelined one (camfc_pipe.hip, 0.55-0.63 us per tuple at any run length)
-            // breaks even with the block kernel (about 1.3 us per block + 0.28 us per tuple) near 5 tuples per block, the one-ahead
-            // wave near 3 (tests/tools/bench_camfc_paths.py)
-            const double min_run = camfc_pipe_supported(h->k, h->n_conds, dmax) ? 5.0 : 3.0;
-            if ((double)n / (double)(off.size() - 1) >= min_run) h->blk_off.swap(off);
-        }
-    } else if (h->chain) {
+    } else if (h->sched == Sched::CHAIN) {
         // hub-chain levels: level_off indexes UNITS; sch.perm carries the stream order
         sch.perm.swap(csch.perm);
         sch.level_off = csch.level_off;
@@ -836,15 +843,13 @@ static void level_slots(cmi_instance *h, int dmax, const LevelSchedule &sch) {
     h->sched_levels = n_levels;
     h->tail_len.assign((size_t)n_levels, 0);
     h->n_launches = 0;
-    if (!h->serial && !h->chain) build_narrow_runs(h->level_off, 256, 16, h->tail_len);
+    if (h->sched == Sched::LEVELS) build_narrow_runs(h->level_off, 256, 16, h->tail_len);
     h->slot_off.assign((size_t)n_levels + 1, 0);
     for (int64_t l = 0; l < n_levels; ++l) {
         const int cnt = (int)(h->level_off[(size_t)l + 1] - h->level_off[(size_t)l]);
-        int blocks = h->serial ? 0
-                     : h->chain ? chain_level_blocks(h->k, dmax, h->f64, cnt)
-                     : h->fast ? level_blocks_f32_fast(h->k, cnt)
-                     : h->small ? level_blocks_small(h->k, dmax, cnt)
-                                : level_blocks_generic(cnt);
+        int blocks = h->sched == Sched::CHAIN    ? chain_level_blocks(h->k, dmax, h->f64, cnt)
+                     : h->sched == Sched::LEVELS ? level_blocks(h->level_kernel, h->k, dmax, cnt)
+                                                 : 0;
         if (h->tail_len[(size_t)l] > 0) blocks = 1;       // a narrow run owns one loss slot ...
         else if (h->tail_len[(size_t)l] < 0) blocks = 0;  // ... at its first level
         if (h->tail_len[(size_t)l] >= 0) ++h->n_launches;
@@ -868,9 +873,10 @@ static void gather_stream(const cmi_instance *h, const RatingsIn &in, int dmax, 
     hs.sconds = HostBuf<int32_t>((size_t)ns * (size_t)dmax);
     hs.sr32 = HostBuf<float>(h->f64 ? 0 : (size_t)ns);
     hs.sr64 = HostBuf<double>(h->f64 ? (size_t)ns : 0);
+    const bool in_order = in_input_order(h->sched);
     parallel_ranges(ns, host_threads(ns), [&](int, int64_t s0, int64_t s1) {
         for (int64_t s = s0; s < s1; ++s) {
-            if (!h->serial && s + 16 < s1) {
+            if (!in_order && s + 16 < s1) {
                 const int64_t tp = sch.perm[(size_t)s + 16];
                 if (tp >= 0) {
                     __builtin_prefetch(&u[tp]);
@@ -879,7 +885,7 @@ static void gather_stream(const cmi_instance *h, const RatingsIn &in, int dmax, 
                     if (dmax > 0) __builtin_prefetch(&ctx[tp]);
                 }
             }
-            const int64_t t = h->serial ? s : sch.perm[(size_t)s];
+            const int64_t t = in_order ? s : sch.perm[(size_t)s];
             int32_t *row = dmax > 0 ? &hs.sconds[(size_t)s * (size_t)dmax] : nullptr;
             if (t < 0) { // padding slot
                 hs.su[(size_t)s] = -1;
@@ -932,7 +938,7 @@ static hipError_t upload_stream(cmi_instance *h, const RatingsIn &in, int dmax, 
                                                 h->f64, h->d_su, h->d_sj, h->d_sconds, h->d_sr);
     }
     free_keep(keep);
-    if (e == hipSuccess && h->chain) e = upload((void **)&h->d_unit_off, csch.unit_off, h->stream);
+    if (e == hipSuccess && h->sched == Sched::CHAIN) e = upload((void **)&h->d_unit_off, csch.unit_off, h->stream);
     return e;
 }
 
@@ -940,7 +946,7 @@ static hipError_t upload_stream(cmi_instance *h, const RatingsIn &in, int dmax, 
 // rows over >= 2 GiB run at ~0.5 of the HBM peak (address-translation misses, DRAM page misses), sequential reads + random full-line
 // writes at ~0.7 (tools/micro/row_bias.hip: 4.10 vs 5.73 TB/s) -- and smaller tables gain nothing (5.58 vs 5.61).
 static hipError_t setup_arena(cmi_instance *h, int64_t n, bool dev_stream, const HostStream &hs, SpecArena &spec) {
-    if (!h->chain || !arena_kernel_ok(h)) return hipSuccess;
+    if (h->sched != Sched::CHAIN || !arena_kernel_ok(h)) return hipSuccess;
     const int64_t spokes = h->chain_hub_item ? h->n_users : h->n_items;
     const size_t table_bytes = (size_t)spokes * (size_t)h->k * esize(h), arena_bytes = (size_t)n * (size_t)h->k * esize(h);
     size_t free_b = 0, total_b = 0;
@@ -1081,7 +1087,7 @@ static hipError_t alloc_launch_buffers(cmi_instance *h) {
         e = hipMalloc((void **)&h->d_loss_part, (size_t)h->n_slots * sizeof(double));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_loss_part, 0, (size_t)h->n_slots * sizeof(double), h->stream);
     }
-    if (e == hipSuccess && !h->blk_off.empty()) e = upload((void **)&h->d_blk_off, h->blk_off, h->stream);
+    if (e == hipSuccess && h->sched == Sched::CAMFC_BLOCKS) e = upload((void **)&h->d_blk_off, h->blk_off, h->stream);
     if (e == hipSuccess && h->n_tail > 0) e = upload((void **)&h->d_tail_off, h->level_off, h->stream); // the tail launches read their level offsets from the device
     return e;
 }
@@ -1119,14 +1125,16 @@ static int build_ratings(cmi_instance *h, const RatingsIn &in) {
     ChainSchedule csch;
     OwnerSchedule osch;
     ChainDeviceKeep keep; // device-built schedule: the tuple ids and the permutation stay on the device for the stream build
-    if (choose_schedule(h, in, chain_ok, csch, keep))
+    h->sched = choose_schedule(h, in, dmax, chain_ok, csch, keep);
+    if (h->sched == Sched::LEVELS) h->level_kernel = level_kernel(h->k, dmax, h->f64, LaunchCfg{h->model, h->strict});
+    if (h->sched == Sched::OWNER) {
         if (int rc = build_owner_lists(h, in, osch, sch)) return rc;
-    if (!h->owner) {
-        if (int rc = build_levels(h, in, dmax, csch, sch)) return rc;
+    } else {
+        if (int rc = build_levels(h, in, csch, sch)) return rc;
         level_slots(h, dmax, sch);
     }
     lap("schedule");
-    const bool dev_stream = h->chain && keep.d_perm != nullptr; // (the device-built schedule builds the stream on the device too)
+    const bool dev_stream = h->sched == Sched::CHAIN && keep.d_perm != nullptr; // (the device-built schedule builds the stream on the device too)
     HostStream hs;
     if (!dev_stream) gather_stream(h, in, dmax, sch, hs);
     lap("stream");
@@ -1134,14 +1142,17 @@ static int build_ratings(cmi_instance *h, const RatingsIn &in) {
     lap("uploads");
     if (e == hipSuccess) e = setup_arena(h, n, dev_stream, hs, spec);
     lap("arena");
-    if (e == hipSuccess && h->owner) e = pack_owner_records(h, in, osch, sch);
+    if (e == hipSuccess && h->sched == Sched::OWNER) e = pack_owner_records(h, in, osch, sch);
     if (e == hipSuccess && h->model == CMI_MODEL_SVDPP) e = build_user_items(h, in);
     if (e == hipSuccess) e = alloc_launch_buffers(h);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) CMI_FAIL(h, CMI_E_HIP, "set_ratings: upload failed: %s", hipGetErrorString(e));
     lap("rest");
-    h->tuple_bytes = h->owner ? (n + (int64_t)h->n_owners * 2 * owner_depth()) * (int64_t)owner_rec_bytes(owner_mask_words(h->model, h->n_conds))
-                              : n * (8 + (int64_t)esize(h) + 4 * (int64_t)dmax + 0) + (h->chain ? 4 * (h->n_units + 1) : 0) + (h->arena_on ? 4 * n : 0);
+    if (h->sched == Sched::OWNER)
+        h->tuple_bytes = (n + (int64_t)h->n_owners * 2 * owner_depth()) * (int64_t)owner_rec_bytes(owner_mask_words(h->model, h->n_conds));
+    else
+        h->tuple_bytes = n * (8 + (int64_t)esize(h) + 4 * (int64_t)dmax) + (h->sched == Sched::CHAIN ? 4 * (h->n_units + 1) : 0) +
+                         (h->arena_on ? 4 * n : 0);
     h->have_ratings = true;
     return CMI_OK;
 }
@@ -1183,8 +1194,15 @@ extern "C" int cmi_schedule_info(cmi_handle h, int64_t info[8]) {
     for (int w = 0; w < CMI_STATE_COUNT; ++w) sb += h->state_count[w] * (int64_t)esize(h);
     info[4] = sb;
     info[5] = h->tuple_bytes;
-    info[6] = h->owner ? (h->owner_hub_item ? 6 : 7) : (h->serial ? 1 : (h->chain ? (h->chain_hub_item ? 4 : 5) : 0));
-    info[7] = h->owner ? ((int64_t)h->n_owners | ((int64_t)h->n_team << 32)) : (h->chain ? h->n_units : (h->d_blk_off ? (int64_t)h->blk_off.size() - 1 : 0));
+    info[6] = info[7] = 0; // plain levels
+    switch (h->sched) {
+    case Sched::SERIAL:
+    case Sched::EXT_SERIAL: info[6] = 1; break;
+    case Sched::CAMFC_BLOCKS: info[6] = 1; info[7] = (int64_t)h->blk_off.size() - 1; break;
+    case Sched::CHAIN: info[6] = h->chain_hub_item ? 4 : 5; info[7] = h->n_units; break;
+    case Sched::OWNER: info[6] = h->owner_hub_item ? 6 : 7; info[7] = (int64_t)h->n_owners | ((int64_t)h->n_team << 32); break;
+    default: break;
+    }
     return CMI_OK;
 }
 
@@ -1209,7 +1227,7 @@ extern "C" int cmi_schedule_traffic(cmi_handle h, int64_t out[4]) {
     const int64_t ctx_row_sect = 2 * row_sectors * SECT, ctx_row_own = 2 * NC * e;                 // the whole row, coalesced
     const int64_t S = (bu ? 1 : 0) + (bj ? 1 : 0), T = (uc ? 1 : 0) + (ic ? 1 : 0) + (cb ? 1 : 0);
     out[2] = n * (12 + e + 4 * D + 2 * row + 2 * e * S + 2 * e * D * T);
-    if (h->chain) {
+    if (h->sched == Sched::CHAIN) {
         const bool hi = h->chain_hub_item;
         const bool hub_b = hi ? bj : bu, spk_b = hi ? bu : bj, hub_c = hi ? ic : uc, spk_c = hi ? uc : ic;
         const int64_t unit_sect = row + (hub_b ? 2 * SECT : 0) + (hub_c ? ctx_row_sect : 0) + 4;
@@ -1265,7 +1283,7 @@ static SgdArgs<T> make_args(cmi_instance *h) {
 // Debug builds only (make TRACE=1; tools/exp/owner_trace.py): owner epochs from now on record every tuple's inputs and outputs (12 rows of
 // 64 doubles per list position, owner_kernels.hip CMI_TR_ROWS); the dump writes the most recent epoch's trace to a file and stops tracing.
 extern "C" int cmi_debug_owner_trace(cmi_handle h) {
-    if (!h || !h->owner) return CMI_E_INVALID;
+    if (!h || h->sched != Sched::OWNER) return CMI_E_INVALID;
     if (hipSetDevice(h->device) != hipSuccess) return CMI_E_HIP;
     if (!h->d_trace) {
         h->trace_doubles = ((size_t)h->n + (size_t)h->n_owners * 2 * (size_t)owner_depth()) * 12 * 64;
@@ -1339,99 +1357,72 @@ static ExtArgs<T> make_ext_args(cmi_instance *h) {
     return a;
 }
 
-// enqueue every level of one epoch + the loss reduction on h->stream
+// The owner epoch is a persistent launch whose workgroups wait for each other: every one of them has to be resident.  Two of them in
+// flight at once (two folds of `cv -p on` on one GPU, each on its own stream) could each hold part of the compute units and wait forever
+// for the rest, so the gate (OwnerDeviceLock) admits owner epochs of this process only while their workgroups fit the device together,
+// and keeps another PROCESS's epochs away through an advisory file lock; it is held from the launch until the stream has drained
+// (cmi_train_epoch_async is synchronous for this schedule).  Should a foreign persistent kernel hold compute units anyway, the waits are
+// bounded, the first one to expire ends every other wait early (owner_spin_expired) and the epoch is reported as failed right here --
+// also on the cmi_train_epoch_async path, which never calls cmi_last_loss.
+template <typename T>
+static hipError_t enqueue_owner_epoch(cmi_instance *h) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 1;
+    OwnerDeviceLock guard(h->device, h->n_team + (h->n_owners - h->n_team + 3) / 4, cus);
+    if (!guard.ok) {
+        h->owner_busy = true;
+        h->owner_busy_why = guard.why;
+        return hipErrorNotReady;
+    }
+    const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
+    // the epoch's tag base: an odd multiple of the sequence number mod 2^32 -- two epochs' tags of one row differ by far more than a
+    // row has updates, so a record copy from an earlier epoch cannot carry the tag a tuple of this epoch waits for
+    const uint32_t tag0 = (uint32_t)(++h->owner_epoch_seq) * 0x9E3779B1u;
+    // the strict form is fp64 only: has_owner_path refuses strict fp32 state, so an fp32 owner epoch is never strict
+    const bool strict = sizeof(T) == 8 && h->strict;
+    hipError_t e = launch_owner_epoch<T>(make_args<T>(h), h->model, h->owner_hub_item, strict, h->d_own_recs, h->d_own_off, h->n_owners,
+                                         h->n_team, h->d_tagged, h->own_stride, n_spokes, h->d_flow_err, tag0, h->stream);
+    if (e == hipSuccess) e = launch_reduce_loss(h->d_loss_part, h->n_slots, h->d_scratch, h->d_loss, h->stream);
+    int32_t stalled = 0;
+    if (e == hipSuccess) e = hipMemcpyAsync(&stalled, h->d_flow_err, 4, hipMemcpyDeviceToHost, h->stream); // (the instance's stream, not the legacy one)
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess && stalled) {
+        h->owner_stalled = true;
+        e = hipErrorLaunchFailure;
+    }
+    return e;
+}
+
+// enqueue one epoch of the chosen schedule (+ the loss reduction) on h->stream
+template <typename T>
 static hipError_t enqueue_levels(cmi_instance *h) {
-    LaunchCfg cfg{h->model, h->strict};
-    hipError_t e = hipSuccess;
+    const LaunchCfg cfg{h->model, h->strict};
+    switch (h->sched) {
+    case Sched::EXT_SERIAL: return launch_ext_serial<T>(make_ext_args<T>(h), h->model, h->strict, h->n, h->d_loss, h->stream);
+    case Sched::SERIAL: return launch_serial<T>(make_args<T>(h), cfg, h->n, h->d_loss, h->stream);
+    case Sched::CAMFC_BLOCKS: return launch_camfc_blocks<T>(make_args<T>(h), h->d_blk_off, (int)h->blk_off.size() - 1, h->d_loss, h->stream);
+    case Sched::OWNER: return enqueue_owner_epoch<T>(h);
+    case Sched::CHAIN:
+    case Sched::LEVELS: break;
+    default: return hipErrorInvalidValue;
+    }
+    const SgdArgs<T> a = make_args<T>(h);
     const int64_t n_levels = (int64_t)h->level_off.size() - 1;
-    if (is_ext_model(h->model)) {
-        if (h->f64) return launch_ext_serial<double>(make_ext_args<double>(h), h->model, h->strict, h->n, h->d_loss, h->stream);
-        return launch_ext_serial<float>(make_ext_args<float>(h), h->model, h->strict, h->n, h->d_loss, h->stream);
-    }
-    if (h->serial) {
-        if (h->d_blk_off) { // CAMF_C over conflict-free blocks
-            const int nb = (int)h->blk_off.size() - 1;
-            if (h->f64) return launch_camfc_blocks<double>(make_args<double>(h), h->d_blk_off, nb, h->d_loss, h->stream);
-            return launch_camfc_blocks<float>(make_args<float>(h), h->d_blk_off, nb, h->d_loss, h->stream);
-        }
-        if (h->f64) return launch_serial<double>(make_args<double>(h), cfg, h->n, h->d_loss, h->stream);
-        return launch_serial<float>(make_args<float>(h), cfg, h->n, h->d_loss, h->stream);
-    }
-    if (h->owner) {
-        // The owner epoch is a persistent launch whose workgroups wait for each other: every one of them has to be resident.  Two of
-        // them in flight at once (two folds of `cv -p on` on one GPU, each on its own stream) could each hold part of the compute units
-        // and wait forever for the rest, so the gate (OwnerDeviceLock) admits owner epochs of this process only while their workgroups
-        // fit the device together, and keeps another PROCESS's epochs away through an advisory file lock; it is held from the launch
-        // until the stream has drained (cmi_train_epoch_async is synchronous for this schedule).  Should a foreign persistent kernel
-        // hold compute units anyway, the waits are bounded, the first one to expire ends every other wait early (owner_spin_expired)
-        // and the epoch is reported as failed right here -- also on the cmi_train_epoch_async path, which never calls cmi_last_loss.
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || cus < 1) cus = 1;
-        OwnerDeviceLock guard(h->device, h->n_team + (h->n_owners - h->n_team + 3) / 4, cus);
-        if (!guard.ok) {
-            h->owner_busy = true;
-            h->owner_busy_why = guard.why;
-            return hipErrorNotReady;
-        }
-        const int32_t n_spokes = h->owner_hub_item ? h->n_users : h->n_items;
-        // the epoch's tag base: an odd multiple of the sequence number mod 2^32 -- two epochs' tags of one row differ by far more than a
-        // row has updates, so a record copy from an earlier epoch cannot carry the tag a tuple of this epoch waits for
-        const uint32_t tag0 = (uint32_t)(++h->owner_epoch_seq) * 0x9E3779B1u;
-        e = h->f64 ? launch_owner_epoch<double>(make_args<double>(h), h->model, h->owner_hub_item, h->strict, h->d_own_recs, h->d_own_off, h->n_owners, h->n_team, h->d_tagged,
-                                                h->own_stride, n_spokes, h->d_flow_err, tag0, h->stream)
-                   : launch_owner_epoch<float>(make_args<float>(h), h->model, h->owner_hub_item, false, h->d_own_recs, h->d_own_off, h->n_owners, h->n_team, h->d_tagged,
-                                               h->own_stride, n_spokes, h->d_flow_err, tag0, h->stream);
-        if (e == hipSuccess) e = launch_reduce_loss(h->d_loss_part, h->n_slots, h->d_scratch, h->d_loss, h->stream);
-        int32_t stalled = 0;
-        if (e == hipSuccess) e = hipMemcpyAsync(&stalled, h->d_flow_err, 4, hipMemcpyDeviceToHost, h->stream); // (the instance's stream, not the legacy one)
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e == hipSuccess) {
-            if (stalled) {
-                h->owner_stalled = true;
-                e = hipErrorLaunchFailure;
-            }
-        }
-        return e;
-    }
-    if (h->chain) {
-        for (int64_t l = 0; l < n_levels && e == hipSuccess; ++l) {
-            const int64_t b = h->level_off[(size_t)l];
-            const int cnt = (int)(h->level_off[(size_t)l + 1] - b);
-            e = h->f64 ? launch_chain_level<double>(make_args<double>(h), cfg, h->chain_hub_item, h->d_unit_off, b, cnt, h->slot_off[(size_t)l], h->stream)
-                       : launch_chain_level<float>(make_args<float>(h), cfg, h->chain_hub_item, h->d_unit_off, b, cnt, h->slot_off[(size_t)l], h->stream);
-        }
-    } else if (h->f64) {
-        const SgdArgs<double> a = make_args<double>(h);
-        for (int64_t l = 0; l < n_levels && e == hipSuccess; ++l) {
-            const int32_t run = h->tail_len.empty() ? 0 : h->tail_len[(size_t)l];
-            if (run > 0) {
-                e = launch_tail<double>(a, cfg, h->d_tail_off + l, run, h->slot_off[(size_t)l], h->stream);
-                l += run - 1;
-                continue;
-            }
-            e = launch_level_generic<double>(a, cfg, h->level_off[(size_t)l],
-                                             (int)(h->level_off[(size_t)l + 1] - h->level_off[(size_t)l]),
-                                             h->slot_off[(size_t)l], h->stream);
-        }
-    } else {
-        const SgdArgs<float> a = make_args<float>(h);
-        for (int64_t l = 0; l < n_levels && e == hipSuccess; ++l) {
-            const int32_t run = h->tail_len.empty() ? 0 : h->tail_len[(size_t)l];
-            if (run > 0) {
-                e = launch_tail_f32(a, cfg, h->fast ? 1 : (h->small ? 2 : 0), h->d_tail_off + l, run, h->slot_off[(size_t)l], h->stream);
-                l += run - 1;
-                continue;
-            }
-            const int64_t b = h->level_off[(size_t)l];
-            const int cnt = (int)(h->level_off[(size_t)l + 1] - b);
-            e = h->fast    ? launch_level_fast_f32(a, cfg, b, cnt, h->slot_off[(size_t)l], h->stream)
-                : h->small ? launch_level_small_f32(a, cfg, b, cnt, h->slot_off[(size_t)l], h->stream)
-                           : launch_level_generic<float>(a, cfg, b, cnt, h->slot_off[(size_t)l], h->stream);
-        }
+    hipError_t e = hipSuccess;
+    for (int64_t l = 0; l < n_levels && e == hipSuccess; ++l) {
+        const int64_t b = h->level_off[(size_t)l], slot = h->slot_off[(size_t)l];
+        const int cnt = (int)(h->level_off[(size_t)l + 1] - b);
+        const int32_t run = h->tail_len[(size_t)l];
+        if (h->sched == Sched::CHAIN) e = launch_chain_level<T>(a, cfg, h->chain_hub_item, h->d_unit_off, b, cnt, slot, h->stream);
+        else if (run > 0) {
+            e = launch_narrow_run<T>(a, cfg, h->level_kernel, h->d_tail_off + l, run, slot, h->stream);
+            l += run - 1;
+        } else e = launch_level<T>(a, cfg, h->level_kernel, b, cnt, slot, h->stream);
     }
     if (e == hipSuccess) e = launch_reduce_loss(h->d_loss_part, h->n_slots, h->d_scratch, h->d_loss, h->stream);
     return e;
 }
+static hipError_t enqueue_levels(cmi_instance *h) { return h->f64 ? enqueue_levels<double>(h) : enqueue_levels<float>(h); }
 
 static int arena_probe(cmi_instance *h);
 
@@ -1448,7 +1439,7 @@ static int enqueue_epoch(cmi_instance *h, double lrate, bool probing = false) {
         return CMI_OK;
     }
     // a graph of several hundred thousand kernel nodes is neither instantiable in reasonable time nor useful
-    const bool graph = h->use_graph && !h->serial && !h->owner && (h->n_tail > 0 ? h->n_launches : (int64_t)h->level_off.size() - 1) <= 65536;
+    const bool graph = h->use_graph && (h->sched == Sched::LEVELS || h->sched == Sched::CHAIN) && (h->n_tail > 0 ? h->n_launches : (int64_t)h->level_off.size() - 1) <= 65536;
     if (graph && !h->graph_exec) {
         hipGraph_t g = nullptr;
         CMI_HIP(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -1531,13 +1522,14 @@ extern "C" int cmi_last_loss(cmi_handle h, double *loss_out) {
     CMI_HIP(h, hipSetDevice(h->device));
     CMI_HIP(h, hipMemcpyAsync(h->h_loss, h->d_loss, sizeof(double), hipMemcpyDeviceToHost, h->stream));
     int32_t flow_stat[4] = {0, 0, 0, 0};
-    if (h->owner) CMI_HIP(h, hipMemcpyAsync(flow_stat, h->d_flow_err, 16, hipMemcpyDeviceToHost, h->stream));
+    const bool owner = h->sched == Sched::OWNER;
+    if (owner) CMI_HIP(h, hipMemcpyAsync(flow_stat, h->d_flow_err, 16, hipMemcpyDeviceToHost, h->stream));
     CMI_HIP(h, hipStreamSynchronize(h->stream));
     const int32_t flow_err = flow_stat[0];
-    if (h->owner && h->n_team > 0 && getenv("CMI_OWNER_STATS"))
+    if (owner && h->n_team > 0 && getenv("CMI_OWNER_STATS"))
         fprintf(stderr, "[cmi] owner teams: %d; cumulative, busiest owner: compute wave found the ring empty %d times, loader found it full %d times\n",
                 h->n_team, flow_stat[1], flow_stat[2]);
-    else if (h->owner && getenv("CMI_OWNER_STATS"))
+    else if (owner && getenv("CMI_OWNER_STATS"))
         fprintf(stderr, "[cmi] owner: cumulative -- busiest owner (%lld tuples per epoch) found %d records not ready and polled %d times; all owners: %d "
                 "records not ready (of %lld tuples per epoch)\n", (long long)h->max_level, flow_stat[1], flow_stat[2], flow_stat[3], (long long)h->n);
     if (flow_err) CMI_FAIL(h, CMI_E_HIP, "owner epoch stalled: a tuple waited past its bound for a predecessor (model state is invalid)");

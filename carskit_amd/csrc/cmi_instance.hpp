@@ -12,11 +12,25 @@
 
 #include "mf_sgd_kernels.hpp"
 
+// The epoch form cmi_set_ratings chose (the caller's request stays in cmi_instance::flags, CMI_FLAG_SCHED_*)
+enum class Sched {
+    NONE,         // no ratings
+    LEVELS,       // plain dependency levels and their narrow runs, with cmi_instance::level_kernel
+    SERIAL,       // one wave walks the tuples in input order
+    CAMFC_BLOCKS, // CAMF_C over conflict-free CRS blocks (blk_off)
+    EXT_SERIAL,   // SVD++ / CAMF_ICS / LCS / MCS: their serial kernels (ext_kernels.hip)
+    CHAIN,        // hub-chain levels: level_off holds UNIT indices, d_unit_off the units
+    OWNER,        // the owner (dataflow) epoch: one persistent launch
+};
+
 struct cmi_instance {
     int model = 0, k = 0, n_users = 0, n_items = 0, n_conds = 0, device = 0;
     unsigned flags = 0;
-    bool f64 = false, serial = false, strict = false, use_graph = true, fast = false, small = false;
-    bool chain = false, chain_hub_item = true; // hub-chain level schedule: level_off holds UNIT indices, d_unit_off the units
+    bool f64 = false, strict = false, use_graph = true;
+    // set once by cmi_set_ratings (build_ratings), reset by free_ratings
+    Sched sched = Sched::NONE;
+    cmi::LevelKernel level_kernel = cmi::LevelKernel::GENERIC;
+    bool chain_hub_item = true;
     int32_t *d_unit_off = nullptr;
     int64_t n_units = 0;
     // spoke arena of the hub-chain schedule (SgdArgs::arena): one slot per tuple, in schedule order.  While arena_valid the live value of
@@ -29,7 +43,7 @@ struct cmi_instance {
     void *d_arena = nullptr;
     int32_t *d_next = nullptr, *d_first = nullptr;
     // owner (dataflow) schedule: one persistent launch, d_own_recs = the owners' lists, d_tagged = the spoke side's tagged records
-    bool want_owner = false, owner = false, owner_hub_item = true;
+    bool owner_hub_item = true;
     uint32_t owner_epoch_seq = 0; // owner epochs launched so far (the epoch's tag base derives from it)
     bool owner_busy = false; // the last owner epoch was not launched: the device's owner-epoch lock could not be taken (CMI_E_BUSY)
     const char *owner_busy_why = "";
@@ -61,7 +75,7 @@ struct cmi_instance {
     int64_t n_launches = 0, n_tail = 0; // launches per epoch; levels that live inside narrow runs
     std::vector<int32_t> tail_len;      // per level: >0 = a narrow run of that many levels starts here (one launch), -1 = inside one
     int64_t *d_tail_off = nullptr;
-    std::vector<int32_t> blk_off; // CAMF_C: conflict-free CRS blocks (empty: the serial wave is used)
+    std::vector<int32_t> blk_off; // Sched::CAMFC_BLOCKS: the conflict-free CRS blocks
     int32_t *d_blk_off = nullptr;
     int64_t n_slots = 0, max_level = 0, tuple_bytes = 0, sched_levels = 0;
     double *d_loss_part = nullptr, *d_scratch = nullptr, *d_loss = nullptr;

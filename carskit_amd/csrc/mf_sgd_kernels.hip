@@ -9,12 +9,17 @@
 // ~10k flop against ~16k bytes.  HBM-bound, no dense contraction -> no MFMA; the work is coalesced
 // 16-byte-per-lane row traffic, DPP row reductions for the dot, and keeping enough tuples in flight.
 //
-// Three kernel families:
-//   sgd_level_fast_f32  fp32 state, k in {64,128,256}: 16 lanes per tuple (4 tuples per wave64), each lane
+// Kernel families:
+//   sgd_level_fast_f32  fp32 state, 64 <= k <= 256: 16 lanes per tuple (4 tuples per wave64), each lane
 //                       owns k/16 factors as float4s -> every row load/store instruction moves whole 256-B
 //                       segments; the dot is reduced inside a DPP row (row_ror 8/4/2/1, pure VALU).
+//   sgd_level_small_f32 fp32 state, k < 64: 4 / 8 / 16 lanes per tuple, the sum inside the lane group.
 //   sgd_level_generic   any k / fp64 state / strict order: one wave64 per tuple, lane-strided factors.
-//   sgd_serial          one wave64 walks every tuple in the reference's order (exact for all models).
+//   sgd_tail_*          a narrow run of levels in one workgroup, with the arithmetic of the level kernel it replaces.
+//   sgd_camfc_blocks    CAMF_C over conflict-free CRS blocks (below); sgd_serial / sgd_serial_fast: one wave64 walks
+//                       every tuple in the reference's order (exact for all models).
+// The hub-chain levels (chain_kernels.hip), the owner epoch (owner_kernels.hip) and CAMF_C's pipelined wave
+// (camfc_pipe.hip) live in their own files.
 // A "level" is a set of tuples that share no user and no item; their updates commute exactly, so
 // running levels back-to-back reproduces the reference's sequential result (see level_schedule.cpp).
 //
@@ -994,199 +999,117 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs<T> a, int64_t n) {
 // host-side launchers
 // ---------------------------------------------------------------------------------------------
 
-constexpr int FAST_TPG = 2; // tuples per 16-lane group of a level launch
+constexpr int FAST_TPG = 2;  // tuples per 16-lane group of a level launch
+constexpr int SMALL_TPG = 2; // tuples per lane group of a small-k level launch
 
-int level_blocks_f32_fast(int, int count) { return (count + 16 * FAST_TPG - 1) / (16 * FAST_TPG); }
-int level_blocks_generic(int count) { return (count + 3) / 4; }
-
-bool has_fast_path(int k, int dmax, bool f64, const LaunchCfg &cfg) {
-    if (f64 || cfg.strict) return false;
-    if (k < 64 || k > 256 || k % 4 != 0) return false; // k = 64/128/256: exact kernels; other multiples of 4: masked float4 slots
-    if (dmax > 16) return false;
-    return true;
+LevelKernel level_kernel(int k, int dmax, bool f64, const LaunchCfg &cfg) {
+    if (f64 || cfg.strict || dmax > 16) return LevelKernel::GENERIC;
+    if (k >= 64 && k <= 256 && k % 4 == 0) return LevelKernel::FAST; // k = 64/128/256: exact kernels; other multiples of 4: masked float4 slots
+    if (k < 64 && cfg.model != CAMF_C) return LevelKernel::SMALL;
+    return LevelKernel::GENERIC;
 }
 
-// small-k path: lanes per tuple
 int small_lpt(int k, int dmax) {
     if (k <= 16 && dmax <= 4) return 4;
     if (k <= 32 && dmax <= 8) return 8;
     return 16;
 }
-bool has_small_path(int k, int dmax, bool f64, const LaunchCfg &cfg) {
-    if (f64 || cfg.strict || cfg.model == CAMF_C) return false;
-    return k < 64 && dmax <= 16;
-}
-constexpr int SMALL_TPG = 2;
-int level_blocks_small(int k, int dmax, int count) {
-    const int per = (256 / small_lpt(k, dmax)) * SMALL_TPG;
-    return (count + per - 1) / per;
-}
-template <int MODEL>
-static hipError_t launch_small_model(const SgdArgs<float> &a, int64_t begin, int count, int64_t slot0, hipStream_t s) {
-    const dim3 grid(level_blocks_small(a.k, a.dmax, count)), block(256);
-    switch (small_lpt(a.k, a.dmax)) {
-    case 4: hipLaunchKernelGGL((sgd_level_small_f32<MODEL, 4, SMALL_TPG>), grid, block, 0, s, a, begin, count, slot0); break;
-    case 8: hipLaunchKernelGGL((sgd_level_small_f32<MODEL, 8, SMALL_TPG>), grid, block, 0, s, a, begin, count, slot0); break;
-    default: hipLaunchKernelGGL((sgd_level_small_f32<MODEL, 16, SMALL_TPG>), grid, block, 0, s, a, begin, count, slot0); break;
+
+int level_blocks(LevelKernel kn, int k, int dmax, int count) {
+    switch (kn) {
+    case LevelKernel::FAST: return (count + 16 * FAST_TPG - 1) / (16 * FAST_TPG);
+    case LevelKernel::SMALL: {
+        const int per = (256 / small_lpt(k, dmax)) * SMALL_TPG;
+        return (count + per - 1) / per;
     }
-    return hipGetLastError();
-}
-hipError_t launch_level_small_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int64_t begin, int count, int64_t slot0,
-                                  hipStream_t s) {
-    if (count <= 0) return hipSuccess;
-    switch (cfg.model) {
-    case BIASEDMF: return launch_small_model<BIASEDMF>(a, begin, count, slot0, s);
-    case PMF: return launch_small_model<PMF>(a, begin, count, slot0, s);
-    case CAMF_CI: return launch_small_model<CAMF_CI>(a, begin, count, slot0, s);
-    case CAMF_CU: return launch_small_model<CAMF_CU>(a, begin, count, slot0, s);
-    case CAMF_CUCI: return launch_small_model<CAMF_CUCI>(a, begin, count, slot0, s);
+    default: return (count + 3) / 4;
     }
-    return hipErrorInvalidValue;
 }
 
-template <int MODEL>
-static hipError_t launch_fast_model(const SgdArgs<float> &a, const LaunchCfg &, int64_t begin, int count,
-                                    int64_t slot0, hipStream_t s) {
-    constexpr int T = FAST_TPG;
-    const dim3 grid(level_blocks_f32_fast(a.k, count)), block(256);
-    switch (a.k) {
-    case 64: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 1, T>), grid, block, 0, s, a, begin, count, slot0); break;
-    case 128: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, T>), grid, block, 0, s, a, begin, count, slot0); break;
-    case 256: hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, T>), grid, block, 0, s, a, begin, count, slot0); break;
-    default: // ragged k (multiple of 4)
-        if (a.k < 128) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 2, T, true>), grid, block, 0, s, a, begin, count, slot0);
-        else if (a.k < 192) hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 3, T, true>), grid, block, 0, s, a, begin, count, slot0);
-        else hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, 4, T, true>), grid, block, 0, s, a, begin, count, slot0);
-        break;
-    }
-    return hipGetLastError();
-}
-
-template <int MODEL>
-static void *fast_kernel_ptr_model(int k) {
-    constexpr int T = FAST_TPG;
+// the float4 kernels' shape for k: f(VPL, RAGGED) with VPL float4 slots per lane, RAGGED = the slots past k are masked
+template <typename F>
+static hipError_t with_fast_shape(int k, F &&f) {
+    using std::integral_constant;
     switch (k) {
-    case 64: return (void *)sgd_level_fast_f32<MODEL, 1, T>;
-    case 128: return (void *)sgd_level_fast_f32<MODEL, 2, T>;
-    case 256: return (void *)sgd_level_fast_f32<MODEL, 4, T>;
+    case 64: return f(integral_constant<int, 1>{}, std::false_type{});
+    case 128: return f(integral_constant<int, 2>{}, std::false_type{});
+    case 256: return f(integral_constant<int, 4>{}, std::false_type{});
     }
-    if (k > 64 && k < 256 && k % 4 == 0) {
-        if (k < 128) return (void *)sgd_level_fast_f32<MODEL, 2, T, true>;
-        if (k < 192) return (void *)sgd_level_fast_f32<MODEL, 3, T, true>;
-        return (void *)sgd_level_fast_f32<MODEL, 4, T, true>;
+    if (k < 128) return f(integral_constant<int, 2>{}, std::true_type{});
+    if (k < 192) return f(integral_constant<int, 3>{}, std::true_type{});
+    return f(integral_constant<int, 4>{}, std::true_type{});
+}
+// the small-k kernels' lanes per tuple: f(LPT)
+template <typename F>
+static hipError_t with_small_lpt(int k, int dmax, F &&f) {
+    switch (small_lpt(k, dmax)) {
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
     }
-    return nullptr;
 }
 
-hipError_t launch_level_fast_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int64_t begin, int count,
-                                 int64_t slot0, hipStream_t s) {
+template <typename T>
+hipError_t launch_level(const SgdArgs<T> &a, const LaunchCfg &cfg, LevelKernel kn, int64_t begin, int count, int64_t slot0,
+                        hipStream_t s) {
     if (count <= 0) return hipSuccess;
-    switch (cfg.model) {
-    case BIASEDMF: return launch_fast_model<BIASEDMF>(a, cfg, begin, count, slot0, s);
-    case PMF: return launch_fast_model<PMF>(a, cfg, begin, count, slot0, s);
-    case CAMF_CI: return launch_fast_model<CAMF_CI>(a, cfg, begin, count, slot0, s);
-    case CAMF_CU: return launch_fast_model<CAMF_CU>(a, cfg, begin, count, slot0, s);
-    case CAMF_CUCI: return launch_fast_model<CAMF_CUCI>(a, cfg, begin, count, slot0, s);
+    const dim3 grid(level_blocks(kn, a.k, a.dmax, count)), block(256);
+    if (kn == LevelKernel::GENERIC)
+        return dispatch_model<ModelSet::ALL>(cfg.model, hipErrorInvalidValue, [&](auto m) {
+            constexpr int MODEL = decltype(m)::value;
+            if (cfg.strict) hipLaunchKernelGGL((sgd_level_generic<T, MODEL, true>), grid, block, 0, s, a, begin, count, slot0);
+            else hipLaunchKernelGGL((sgd_level_generic<T, MODEL, false>), grid, block, 0, s, a, begin, count, slot0);
+            return hipGetLastError();
+        });
+    if constexpr (std::is_same_v<T, float>) {
+        return dispatch_model<ModelSet::PARALLEL>(cfg.model, hipErrorInvalidValue, [&](auto m) {
+            constexpr int MODEL = decltype(m)::value;
+            if (kn == LevelKernel::FAST)
+                return with_fast_shape(a.k, [&](auto vpl, auto ragged) {
+                    hipLaunchKernelGGL((sgd_level_fast_f32<MODEL, decltype(vpl)::value, FAST_TPG, decltype(ragged)::value>), grid, block, 0, s,
+                                       a, begin, count, slot0);
+                    return hipGetLastError();
+                });
+            return with_small_lpt(a.k, a.dmax, [&](auto lpt) {
+                hipLaunchKernelGGL((sgd_level_small_f32<MODEL, decltype(lpt)::value, SMALL_TPG>), grid, block, 0, s, a, begin, count, slot0);
+                return hipGetLastError();
+            });
+        });
     }
-    return hipErrorInvalidValue;
+    return hipErrorInvalidValue; // no fp64 form of the fp32 kernels
 }
-
-
-template <typename T, int MODEL>
-static hipError_t launch_generic_model(const SgdArgs<T> &a, const LaunchCfg &cfg, int64_t begin, int count,
-                                       int64_t slot0, hipStream_t s) {
-    const dim3 grid(level_blocks_generic(count)), block(256);
-    if (cfg.strict)
-        hipLaunchKernelGGL((sgd_level_generic<T, MODEL, true>), grid, block, 0, s, a, begin, count, slot0);
-    else
-        hipLaunchKernelGGL((sgd_level_generic<T, MODEL, false>), grid, block, 0, s, a, begin, count, slot0);
-    return hipGetLastError();
-}
+template hipError_t launch_level<float>(const SgdArgs<float> &, const LaunchCfg &, LevelKernel, int64_t, int, int64_t, hipStream_t);
+template hipError_t launch_level<double>(const SgdArgs<double> &, const LaunchCfg &, LevelKernel, int64_t, int, int64_t, hipStream_t);
 
 template <typename T>
-hipError_t launch_tail(const SgdArgs<T> &a, const LaunchCfg &cfg, const int64_t *tail_off, int n_tail, int64_t slot,
-                       hipStream_t s);
-template <int MODEL>
-static hipError_t launch_tail_fast_model(const SgdArgs<float> &a, const int64_t *tail_off, int n_tail, int64_t slot, hipStream_t s) {
-    const dim3 g(1), b(1024);
-    switch (a.k) {
-    case 64: hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 1, false>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    case 128: hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 2, false>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    case 256: hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 4, false>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    default:
-        if (a.k < 128) hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 2, true>), g, b, 0, s, a, tail_off, n_tail, slot);
-        else if (a.k < 192) hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 3, true>), g, b, 0, s, a, tail_off, n_tail, slot);
-        else hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, 4, true>), g, b, 0, s, a, tail_off, n_tail, slot);
-    }
-    return hipGetLastError();
-}
-template <int MODEL>
-static hipError_t launch_tail_small_model(const SgdArgs<float> &a, const int64_t *tail_off, int n_tail, int64_t slot, hipStream_t s) {
-    const dim3 g(1), b(1024);
-    switch (small_lpt(a.k, a.dmax)) {
-    case 4: hipLaunchKernelGGL((sgd_tail_small_f32<MODEL, 4>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    case 8: hipLaunchKernelGGL((sgd_tail_small_f32<MODEL, 8>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    default: hipLaunchKernelGGL((sgd_tail_small_f32<MODEL, 16>), g, b, 0, s, a, tail_off, n_tail, slot); break;
-    }
-    return hipGetLastError();
-}
-// kind: 0 generic (any k / fp64 / strict), 1 the float4 kernels' arithmetic, 2 the small-k kernels' arithmetic
-hipError_t launch_tail_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int kind, const int64_t *tail_off, int n_tail,
-                           int64_t slot, hipStream_t s) {
+hipError_t launch_narrow_run(const SgdArgs<T> &a, const LaunchCfg &cfg, LevelKernel kn, const int64_t *tail_off, int n_tail,
+                             int64_t slot, hipStream_t s) {
     if (n_tail <= 0) return hipSuccess;
-    if (kind == 0) return launch_tail<float>(a, cfg, tail_off, n_tail, slot, s);
-    switch (cfg.model) {
-    case BIASEDMF: return kind == 1 ? launch_tail_fast_model<BIASEDMF>(a, tail_off, n_tail, slot, s) : launch_tail_small_model<BIASEDMF>(a, tail_off, n_tail, slot, s);
-    case PMF: return kind == 1 ? launch_tail_fast_model<PMF>(a, tail_off, n_tail, slot, s) : launch_tail_small_model<PMF>(a, tail_off, n_tail, slot, s);
-    case CAMF_CI: return kind == 1 ? launch_tail_fast_model<CAMF_CI>(a, tail_off, n_tail, slot, s) : launch_tail_small_model<CAMF_CI>(a, tail_off, n_tail, slot, s);
-    case CAMF_CU: return kind == 1 ? launch_tail_fast_model<CAMF_CU>(a, tail_off, n_tail, slot, s) : launch_tail_small_model<CAMF_CU>(a, tail_off, n_tail, slot, s);
-    case CAMF_CUCI: return kind == 1 ? launch_tail_fast_model<CAMF_CUCI>(a, tail_off, n_tail, slot, s) : launch_tail_small_model<CAMF_CUCI>(a, tail_off, n_tail, slot, s);
-    }
-    return hipErrorInvalidValue;
+    const dim3 g(1), b(1024);
+    return dispatch_model<ModelSet::PARALLEL>(cfg.model, hipErrorInvalidValue, [&](auto m) {
+        constexpr int MODEL = decltype(m)::value;
+        if constexpr (std::is_same_v<T, float>) {
+            if (kn == LevelKernel::FAST)
+                return with_fast_shape(a.k, [&](auto vpl, auto ragged) {
+                    hipLaunchKernelGGL((sgd_tail_fast_f32<MODEL, decltype(vpl)::value, decltype(ragged)::value>), g, b, 0, s, a, tail_off, n_tail, slot);
+                    return hipGetLastError();
+                });
+            if (kn == LevelKernel::SMALL)
+                return with_small_lpt(a.k, a.dmax, [&](auto lpt) {
+                    hipLaunchKernelGGL((sgd_tail_small_f32<MODEL, decltype(lpt)::value>), g, b, 0, s, a, tail_off, n_tail, slot);
+                    return hipGetLastError();
+                });
+        }
+        if (kn != LevelKernel::GENERIC) return hipErrorInvalidValue;
+        if (cfg.strict) hipLaunchKernelGGL((sgd_tail_kernel<T, MODEL, true>), g, b, 0, s, a, tail_off, n_tail, slot);
+        else hipLaunchKernelGGL((sgd_tail_kernel<T, MODEL, false>), g, b, 0, s, a, tail_off, n_tail, slot);
+        return hipGetLastError();
+    });
 }
-
-template <typename T, int MODEL>
-static hipError_t launch_tail_model(const SgdArgs<T> &a, const LaunchCfg &cfg, const int64_t *tail_off, int n_tail,
-                                    int64_t slot, hipStream_t s) {
-    if (cfg.strict) hipLaunchKernelGGL((sgd_tail_kernel<T, MODEL, true>), dim3(1), dim3(1024), 0, s, a, tail_off, n_tail, slot);
-    else hipLaunchKernelGGL((sgd_tail_kernel<T, MODEL, false>), dim3(1), dim3(1024), 0, s, a, tail_off, n_tail, slot);
-    return hipGetLastError();
-}
-
-template <typename T>
-hipError_t launch_tail(const SgdArgs<T> &a, const LaunchCfg &cfg, const int64_t *tail_off, int n_tail, int64_t slot,
-                       hipStream_t s) {
-    if (n_tail <= 0) return hipSuccess;
-    switch (cfg.model) {
-    case BIASEDMF: return launch_tail_model<T, BIASEDMF>(a, cfg, tail_off, n_tail, slot, s);
-    case PMF: return launch_tail_model<T, PMF>(a, cfg, tail_off, n_tail, slot, s);
-    case CAMF_CI: return launch_tail_model<T, CAMF_CI>(a, cfg, tail_off, n_tail, slot, s);
-    case CAMF_CU: return launch_tail_model<T, CAMF_CU>(a, cfg, tail_off, n_tail, slot, s);
-    case CAMF_CUCI: return launch_tail_model<T, CAMF_CUCI>(a, cfg, tail_off, n_tail, slot, s);
-    }
-    return hipErrorInvalidValue;
-}
-template hipError_t launch_tail<float>(const SgdArgs<float> &, const LaunchCfg &, const int64_t *, int, int64_t, hipStream_t);
-template hipError_t launch_tail<double>(const SgdArgs<double> &, const LaunchCfg &, const int64_t *, int, int64_t, hipStream_t);
-
-template <typename T>
-hipError_t launch_level_generic(const SgdArgs<T> &a, const LaunchCfg &cfg, int64_t begin, int count, int64_t slot0,
-                                hipStream_t s) {
-    if (count <= 0) return hipSuccess;
-    switch (cfg.model) {
-    case BIASEDMF: return launch_generic_model<T, BIASEDMF>(a, cfg, begin, count, slot0, s);
-    case PMF: return launch_generic_model<T, PMF>(a, cfg, begin, count, slot0, s);
-    case CAMF_C: return launch_generic_model<T, CAMF_C>(a, cfg, begin, count, slot0, s);
-    case CAMF_CI: return launch_generic_model<T, CAMF_CI>(a, cfg, begin, count, slot0, s);
-    case CAMF_CU: return launch_generic_model<T, CAMF_CU>(a, cfg, begin, count, slot0, s);
-    case CAMF_CUCI: return launch_generic_model<T, CAMF_CUCI>(a, cfg, begin, count, slot0, s);
-    }
-    return hipErrorInvalidValue;
-}
-template hipError_t launch_level_generic<float>(const SgdArgs<float> &, const LaunchCfg &, int64_t, int, int64_t,
-                                                hipStream_t);
-template hipError_t launch_level_generic<double>(const SgdArgs<double> &, const LaunchCfg &, int64_t, int, int64_t,
-                                                 hipStream_t);
+template hipError_t launch_narrow_run<float>(const SgdArgs<float> &, const LaunchCfg &, LevelKernel, const int64_t *, int, int64_t,
+                                             hipStream_t);
+template hipError_t launch_narrow_run<double>(const SgdArgs<double> &, const LaunchCfg &, LevelKernel, const int64_t *, int, int64_t,
+                                              hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // CAMF_C, exact and (partly) parallel: conflict-free CRS blocks
@@ -1516,15 +1439,8 @@ static hipError_t launch_serial_model(const SgdArgs<T> &a, const LaunchCfg &cfg,
 
 template <typename T>
 hipError_t launch_serial(const SgdArgs<T> &a, const LaunchCfg &cfg, int64_t n, double *loss_out, hipStream_t s) {
-    switch (cfg.model) {
-    case BIASEDMF: return launch_serial_model<T, BIASEDMF>(a, cfg, n, loss_out, s);
-    case PMF: return launch_serial_model<T, PMF>(a, cfg, n, loss_out, s);
-    case CAMF_C: return launch_serial_model<T, CAMF_C>(a, cfg, n, loss_out, s);
-    case CAMF_CI: return launch_serial_model<T, CAMF_CI>(a, cfg, n, loss_out, s);
-    case CAMF_CU: return launch_serial_model<T, CAMF_CU>(a, cfg, n, loss_out, s);
-    case CAMF_CUCI: return launch_serial_model<T, CAMF_CUCI>(a, cfg, n, loss_out, s);
-    }
-    return hipErrorInvalidValue;
+    return dispatch_model<ModelSet::ALL>(cfg.model, hipErrorInvalidValue,
+                                         [&](auto m) { return launch_serial_model<T, decltype(m)::value>(a, cfg, n, loss_out, s); });
 }
 template hipError_t launch_serial<float>(const SgdArgs<float> &, const LaunchCfg &, int64_t, double *, hipStream_t);
 template hipError_t launch_serial<double>(const SgdArgs<double> &, const LaunchCfg &, int64_t, double *, hipStream_t);

@@ -10,6 +10,17 @@ namespace cmi {
 enum Model { BIASEDMF = 0, CAMF_C = 1, CAMF_CI = 2, CAMF_CU = 3, CAMF_CUCI = 4, PMF = 5,
              SVDPP = 6, CAMF_ICS = 7, CAMF_LCS = 8, CAMF_MCS = 9 }; // 6..9: ext_kernels.hip (serial only)
 
+// Which parameters a model trains (for the MF models 0..5; Traits<MODEL> in sgd_device.hpp is this at compile time)
+struct ModelParams {
+    bool has_bu, has_bj, has_bc, has_ic, has_uc;
+    bool has_ctx; // iterates the contextual matrix
+};
+constexpr ModelParams model_params(int model) {
+    return {model == BIASEDMF || model == CAMF_C || model == CAMF_CI, model == BIASEDMF || model == CAMF_C || model == CAMF_CU,
+            model == CAMF_C, model == CAMF_CI || model == CAMF_CUCI, model == CAMF_CU || model == CAMF_CUCI,
+            !(model == BIASEDMF || model == PMF)};
+}
+
 // Device-resident hyper-parameters, rewritten before every epoch by set_hparams (so a captured
 // hipGraph of level launches can be replayed with a new learning rate).
 struct HParams {
@@ -58,37 +69,30 @@ struct LaunchCfg {
     bool strict; // left-to-right dot (DenseMatrix.rowMult order) + reference loss order
 };
 
+// The kernel family of the plain levels and their narrow runs (same arithmetic, so a narrow run gives the bits of the level
+// launches it replaces):
+//   GENERIC  any k / fp64 state / strict order: one wave64 per tuple, lane-strided factors;
+//   FAST     fp32 state, 64 <= k <= 256 (k % 4 == 0), dmax <= 16: 16 lanes per tuple, float4 factors;
+//   SMALL    fp32 state, k < 64, dmax <= 16, not CAMF_C: 4 / 8 / 16 lanes per tuple (small_lpt).
+enum class LevelKernel { GENERIC, FAST, SMALL };
+LevelKernel level_kernel(int k, int dmax, bool f64, const LaunchCfg &cfg);
+int small_lpt(int k, int dmax); // lanes per tuple of the small-k kernels (LPT >= dmax and 4 * LPT >= k)
 // number of workgroups a level of `count` tuples occupies (= loss_part slots it writes)
-int level_blocks_f32_fast(int k, int count);
-int level_blocks_generic(int count);
-bool has_fast_path(int k, int dmax, bool f64, const LaunchCfg &cfg);
-// all narrow tail levels of a schedule in one launch (one workgroup, a barrier per level); tail_off = n_tail+1 device offsets
+int level_blocks(LevelKernel kn, int k, int dmax, int count);
+// one dependency level: tuples [begin, begin+count) of the schedule run concurrently
 template <typename T>
-hipError_t launch_tail(const SgdArgs<T> &a, const LaunchCfg &cfg, const int64_t *tail_off, int n_tail, int64_t slot,
-                       hipStream_t s);
-// fp32 state: kind 0 = generic arithmetic, 1 = the float4 level kernels', 2 = the small-k level kernels' (same bits as the
-// level launches the run replaces)
-hipError_t launch_tail_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int kind, const int64_t *tail_off, int n_tail,
-                           int64_t slot, hipStream_t s);
+hipError_t launch_level(const SgdArgs<T> &a, const LaunchCfg &cfg, LevelKernel kn, int64_t begin, int count, int64_t slot0,
+                        hipStream_t s);
+// a narrow run: n_tail consecutive narrow levels in one launch (one workgroup, a barrier per level); tail_off = n_tail+1 device offsets
+template <typename T>
+hipError_t launch_narrow_run(const SgdArgs<T> &a, const LaunchCfg &cfg, LevelKernel kn, const int64_t *tail_off, int n_tail,
+                             int64_t slot, hipStream_t s);
 // CAMF_C over conflict-free CRS blocks (<= 64 tuples sharing no user and no item; blk_off = n_blocks+1 device offsets):
 // exact, with the per-tuple gather/dot/update parallel inside a block and only the scalar condBias chain sequential
 size_t camfc_blocks_lds(int n_conds, int dmax, size_t esize);
 template <typename T>
 hipError_t launch_camfc_blocks(const SgdArgs<T> &a, const int32_t *blk_off, int n_blocks, double *loss_out, hipStream_t s);
-// small-k fast path (fp32 state, k < 64): 4 / 8 / 16 lanes per tuple
-bool has_small_path(int k, int dmax, bool f64, const LaunchCfg &cfg);
-int level_blocks_small(int k, int dmax, int count);
-hipError_t launch_level_small_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int64_t begin, int count, int64_t slot0,
-                                  hipStream_t s);
 
-// one dependency level: tuples [begin, begin+count) of the schedule run concurrently
-hipError_t launch_level_fast_f32(const SgdArgs<float> &a, const LaunchCfg &cfg, int64_t begin, int count,
-                                 int64_t slot0, hipStream_t s);
-template <typename T>
-hipError_t launch_level_generic(const SgdArgs<T> &a, const LaunchCfg &cfg, int64_t begin, int count, int64_t slot0,
-                                hipStream_t s);
-// Explicit hipGraph nodes (the two-lane schedule needs a DAG, not a linear capture): one fast-path level segment,
-// and the two-stage loss reduction.  count == 0 adds an empty node so dependency chains stay uniform.
 // Hub-chain level kernel (chain_kernels.hip): one 16-lane group walks a unit of the chain schedule with the hub row on chip.
 // units [ubegin, ubegin+count) of unit_off (n_units+1 device offsets into the tuple stream) form one level.
 bool has_chain_path(int model, int k, int dmax, int n_conds, bool f64, bool strict);

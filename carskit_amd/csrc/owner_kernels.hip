@@ -989,25 +989,25 @@ struct OwnerDepth {
 
 // 64-condition words of a context-bias row: 1, 2 or 6 (<= 64, <= 128, <= 384 conditions); models without context: 1
 int owner_mask_words(int model, int n_conds) {
-    const bool has_ctx = model != BIASEDMF && model != PMF;
-    if (!has_ctx || n_conds <= 64) return 1;
+    if (!model_params(model).has_ctx || n_conds <= 64) return 1;
     return n_conds <= 128 ? 2 : 6;
 }
 
 bool has_owner_path(int model, int k, int n_conds, bool f64, bool strict) {
     if (strict && !f64) return false; // the strict form is the fp64 reference arithmetic
-    if (model != BIASEDMF && model != PMF && model != CAMF_CI && model != CAMF_CU && model != CAMF_CUCI) return false;
+    if (!dispatch_model<ModelSet::PARALLEL>(model, false, [](auto) { return true; })) return false;
     if (k < 1 || k > (f64 ? 128 : 256)) return false;
-    const bool has_ctx = model != BIASEDMF && model != PMF;
-    if (has_ctx && n_conds > 384) return false; // lane l carries conditions l, l + 64, ..., l + 320
+    if (model_params(model).has_ctx && n_conds > 384) return false; // lane l carries conditions l, l + 64, ..., l + 320
     return true;
 }
 int owner_depth() { return OWNER_DEPTH_MAX; }
 
+// the spoke side's context-bias row and scalar bias (what a spoke record carries besides the factor row)
+static bool spoke_ctx(int model, bool hub_is_item) { return hub_is_item ? model_params(model).has_uc : model_params(model).has_ic; }
+static bool spoke_bias(int model, bool hub_is_item) { return hub_is_item ? model_params(model).has_bu : model_params(model).has_bj; }
+
 int64_t owner_record_stride(int model, int k, int n_conds, bool f64, bool hub_is_item) {
-    const bool has_ic = model == CAMF_CI || model == CAMF_CUCI, has_uc = model == CAMF_CU || model == CAMF_CUCI;
-    const bool has_bu = model == BIASEDMF || model == CAMF_CI, has_bj = model == BIASEDMF || model == CAMF_CU;
-    const bool sc = hub_is_item ? has_uc : has_ic, sb = hub_is_item ? has_bu : has_bj;
+    const bool sc = spoke_ctx(model, hub_is_item), sb = spoke_bias(model, hub_is_item);
     return owner_record_granules(owner_vpl(k), sc ? owner_mask_words(model, n_conds) : 0, sb, f64 ? 2 : 1);
 }
 
@@ -1043,14 +1043,11 @@ static OwnerKernel owner_kernel_ctx(int ncw, int k, bool hub_is_item, bool stric
 template <typename T>
 static OwnerKernel owner_kernel(int model, int n_conds, int k, bool hub_is_item, bool strict) {
     const int ncw = owner_mask_words(model, n_conds);
-    switch (model) {
-    case BIASEDMF: return owner_kernel_k<T, BIASEDMF, 1>(k, hub_is_item, strict);
-    case PMF: return owner_kernel_k<T, PMF, 1>(k, hub_is_item, strict);
-    case CAMF_CI: return owner_kernel_ctx<T, CAMF_CI>(ncw, k, hub_is_item, strict);
-    case CAMF_CU: return owner_kernel_ctx<T, CAMF_CU>(ncw, k, hub_is_item, strict);
-    case CAMF_CUCI: return owner_kernel_ctx<T, CAMF_CUCI>(ncw, k, hub_is_item, strict);
-    }
-    return {nullptr, 0};
+    return dispatch_model<ModelSet::PARALLEL>(model, OwnerKernel{nullptr, 0}, [&](auto m) {
+        constexpr int MODEL = decltype(m)::value;
+        if constexpr (Traits<MODEL>::has_ctx) return owner_kernel_ctx<T, MODEL>(ncw, k, hub_is_item, strict);
+        else return owner_kernel_k<T, MODEL, 1>(k, hub_is_item, strict);
+    });
 }
 
 // Owners = wavefronts that are resident together (a waiting owner must never keep a runnable one off the chip).
@@ -1069,9 +1066,7 @@ hipError_t launch_owner_epoch(const SgdArgs<T> &a, int model, bool hub_is_item, 
                               int n_owners, int n_team, void *tagged, int64_t stride, int n_spokes, int *error, uint32_t tag0, hipStream_t s) {
     const OwnerKernel kn = owner_kernel<T>(model, a.n_conds, a.k, hub_is_item, strict);
     if (!kn.fn) return hipErrorInvalidValue;
-    const bool has_ic = model == CAMF_CI || model == CAMF_CUCI, has_uc = model == CAMF_CU || model == CAMF_CUCI;
-    const bool has_bu = model == BIASEDMF || model == CAMF_CI, has_bj = model == BIASEDMF || model == CAMF_CU;
-    const bool sc = hub_is_item ? has_uc : has_ic, sb = hub_is_item ? has_bu : has_bj;
+    const bool sc = spoke_ctx(model, hub_is_item), sb = spoke_bias(model, hub_is_item);
     T *rows = hub_is_item ? a.P : a.Q;
     T *ctx = sc ? (hub_is_item ? a.ucBias : a.icBias) : nullptr;
     T *bias = sb ? (hub_is_item ? a.userBias : a.itemBias) : nullptr;

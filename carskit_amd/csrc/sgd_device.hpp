@@ -1,9 +1,11 @@
-// sgd_device.hpp -- device-side helpers shared by the SGD kernel translation units (mf_sgd_kernels.hip,
-// chain_kernels.hip): DPP row reductions and the per-model container traits.  Internal header.
+// sgd_device.hpp -- helpers shared by the SGD kernel translation units (mf_sgd_kernels.hip, chain_kernels.hip,
+// owner_kernels.hip): DPP row reductions, the per-model container traits and the host's model dispatch.  Internal header.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "mf_sgd_kernels.hpp"
+
+#include <type_traits>
 
 namespace cmi {
 
@@ -36,14 +38,28 @@ __device__ __forceinline__ T wave_sum64(T x) {
 
 template <int MODEL>
 struct Traits {
-    static constexpr bool has_bu = MODEL == BIASEDMF || MODEL == CAMF_C || MODEL == CAMF_CI;
-    static constexpr bool has_bj = MODEL == BIASEDMF || MODEL == CAMF_C || MODEL == CAMF_CU;
-    static constexpr bool has_bc = MODEL == CAMF_C;
-    static constexpr bool has_ic = MODEL == CAMF_CI || MODEL == CAMF_CUCI;
-    static constexpr bool has_uc = MODEL == CAMF_CU || MODEL == CAMF_CUCI;
-    static constexpr bool has_ctx = !(MODEL == BIASEDMF || MODEL == PMF); // iterates the contextual matrix
+    static constexpr ModelParams p = model_params(MODEL);
+    static constexpr bool has_bu = p.has_bu, has_bj = p.has_bj, has_bc = p.has_bc, has_ic = p.has_ic, has_uc = p.has_uc;
+    static constexpr bool has_ctx = p.has_ctx;
 };
 
+// Host side: call f(std::integral_constant<int, MODEL>) for the runtime model id; `invalid` for a model outside the set.
+// PARALLEL = the models with fast / small / narrow-run / chain / owner kernels; ALL adds CAMF_C (generic level and serial kernels).
+enum class ModelSet { PARALLEL, ALL };
+template <ModelSet SET, typename R, typename F>
+R dispatch_model(int model, R invalid, F &&f) {
+    switch (model) {
+    case BIASEDMF: return f(std::integral_constant<int, BIASEDMF>{});
+    case PMF: return f(std::integral_constant<int, PMF>{});
+    case CAMF_C:
+        if constexpr (SET == ModelSet::ALL) return f(std::integral_constant<int, CAMF_C>{});
+        break;
+    case CAMF_CI: return f(std::integral_constant<int, CAMF_CI>{});
+    case CAMF_CU: return f(std::integral_constant<int, CAMF_CU>{});
+    case CAMF_CUCI: return f(std::integral_constant<int, CAMF_CUCI>{});
+    }
+    return invalid;
+}
 
 // Sum over the LPT (4, 8 or 16) lanes of a group that shares one tuple in the small-k kernels: quad permutes, then row
 // (half-)mirrors; every lane of the group ends with the same total.

@@ -302,12 +302,12 @@ int cmi_last_loss(cmi_handle h, double *loss_out);
 /* schedule facts: info[0]=level launches per epoch (a long run of narrow final levels counts as ONE launch: a single
  * workgroup walks them),  info[1]=largest level, info[2]=tuples,
  * info[3]=max conditions per tuple (D), info[4]=state bytes on device, info[5]=tuple-stream bytes on device,
- * info[6]=schedule kind actually running (0 level launches, 1 serial, 2 dataflow, 3 two-lane level graph,
+ * info[6]=schedule kind actually running (0 level launches, 1 serial, 2 and 3 reserved (schedules removed in ABI 3),
  * 4 hub-chain levels along items, 5 hub-chain levels along users; then info[1]=most units in a level, info[7]=units;
  * 6 owner epoch with items owned, 7 with users owned; then info[0]=1, info[1]=tuples of the busiest owner, info[7]=owners in the
  * low 32 bits and, in the high 32 bits, how many of them run as teams of three wavefronts),
- * info[7]=workgroups of the dataflow launch; for CAMF_C the number of conflict-free CRS blocks its epoch is cut into
- * (0: the serial wave) */
+ * info[7] for kind 1: CAMF_C's number of conflict-free CRS blocks its epoch is cut into (0: the serial wave); its former meaning
+ * "workgroups of the dataflow launch" is reserved (removed in ABI 3) */
 int cmi_schedule_info(cmi_handle h, int64_t info[8]);
 /* host-only: the bookkeeping of the spoke arena (CMI_FLAG_SPOKE_ARENA).  spoke[p] = spoke row id of the tuple at stream position p;
  * next[p] = position of the next tuple of the same row, the last one wrapping to the first; first[row] = position of the row's first

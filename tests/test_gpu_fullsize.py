@@ -2,8 +2,7 @@
 
 C3 (CAMF_CI k=128, 1 M users x 100 K items x 32 conditions, 50 M ratings): a direct one-epoch comparison with the CPU oracle
 (about 30 s of single-thread CPU), plus size-independent properties -- idempotence at lr = 0, loss consistency with
-evalRatings, and schedule independence (hub-chain levels, plain levels, eager launches and the two-lane graph give the
-bit-identical model).
+evalRatings, and schedule independence (hub-chain levels, plain levels and eager launches give the bit-identical model).
 C5 (CAMF_CU k=256, one GPU's share of 10 M x 1 M x 128 conditions / 500 M ratings = 1.25 M users, 62.5 M ratings) and the
 north_star shape (CAMF_CI k=128, 10 M x 1 M x 64 conditions, 200 M ratings): the same properties at full size, and a one-epoch
 oracle comparison on a 5 M-tuple prefix (same id spaces, same tables).
