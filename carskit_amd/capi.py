@@ -421,28 +421,28 @@ def _eval_rankings(fn, chk, h, train, test, bin_thold=-1.0, num_recs=10, num_ign
     return res, lists
 
 
-class Group:
-    """One recommender trained over several GPUs from this one process (a `cmi_group_handle`): ratings sharded by user, item-side
-    containers merged (mean of the shards' moves) after every epoch through RCCL, or in-process when shards share a device."""
+class _Handle:
+    """The lifetime of one C handle: `_api` names its create, destroy and last-error functions; the subclass's __init__ hands the
+    create arguments (all but the trailing out-pointer) to this one."""
 
-    def __init__(self, model, k, n_users, n_items, n_conds, n_shards, devices=None, flags=0):
+    _api = ("", "", "")
+
+    def __init__(self, *args):
         self.L = lib()
-        self.model = model if isinstance(model, str) else {v: n for n, v in MODEL_IDS.items()}[model]
-        self.k, self.n_users, self.n_items, self.n_conds, self.num_f = k, n_users, n_items, n_conds, 0
+        create, _, last_error = (getattr(self.L, n) for n in self._api)
         self.h = _vp()
-        dev = None if devices is None else np.ascontiguousarray(devices, dtype=np.int32)
-        rc = self.L.cmi_group_create(MODEL_IDS[self.model], k, n_users, n_items, n_conds, n_shards, _p(dev), flags, C.byref(self.h))
+        rc = create(*args, C.byref(self.h))
         if rc != OK:
             self.h = None
-            raise CmiError(rc, self.L.cmi_group_last_error(None).decode())
+            raise CmiError(rc, last_error(None).decode())
 
     def _chk(self, rc):
         if rc != OK:
-            raise CmiError(rc, self.L.cmi_group_last_error(self.h).decode())
+            raise CmiError(rc, getattr(self.L, self._api[2])(self.h).decode())
 
     def close(self):
         if getattr(self, "h", None):
-            self.L.cmi_group_destroy(self.h)
+            getattr(self.L, self._api[1])(self.h)
             self.h = None
 
     def __del__(self):
@@ -450,6 +450,25 @@ class Group:
             self.close()
         except Exception:
             pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class Group(_Handle):
+    """One recommender trained over several GPUs from this one process (a `cmi_group_handle`): ratings sharded by user, item-side
+    containers merged (mean of the shards' moves) after every epoch through RCCL, or in-process when shards share a device."""
+
+    _api = ("cmi_group_create", "cmi_group_destroy", "cmi_group_last_error")
+
+    def __init__(self, model, k, n_users, n_items, n_conds, n_shards, devices=None, flags=0):
+        self.model = model if isinstance(model, str) else {v: n for n, v in MODEL_IDS.items()}[model]
+        self.k, self.n_users, self.n_items, self.n_conds, self.num_f = k, n_users, n_items, n_conds, 0
+        dev = None if devices is None else np.ascontiguousarray(devices, dtype=np.int32)
+        super().__init__(MODEL_IDS[self.model], k, n_users, n_items, n_conds, n_shards, _p(dev), flags)
 
     def size(self):
         return self.L.cmi_group_size(self.h)
@@ -560,41 +579,17 @@ class Group:
         return inst
 
 
-class Instance:
+class Instance(_Handle):
     """One recommender instance on one GPU (a `cmi_handle`)."""
 
+    _api = ("cmi_create", "cmi_destroy", "cmi_last_error")
+
     def __init__(self, model, k, n_users, n_items, n_conds, device=0, flags=0):
-        self.L = lib()
         self.model = model if isinstance(model, str) else {v: n for n, v in MODEL_IDS.items()}[model]
         self.k, self.n_users, self.n_items, self.n_conds = k, n_users, n_items, n_conds
         self.flags = flags
         self.num_f = 0
-        self.h = _vp()
-        rc = self.L.cmi_create(MODEL_IDS[self.model], k, n_users, n_items, n_conds, device, flags, C.byref(self.h))
-        if rc != OK:
-            self.h = None
-            raise CmiError(rc, self.L.cmi_last_error(None).decode())
-
-    def _chk(self, rc):
-        if rc != OK:
-            raise CmiError(rc, self.L.cmi_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.cmi_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
+        super().__init__(MODEL_IDS[self.model], k, n_users, n_items, n_conds, device, flags)
 
     # -- data ---------------------------------------------------------------------------------------
     def set_sim_params(self, num_f, n_ctx_dims, empty_conds):
@@ -814,33 +809,15 @@ class Instance:
                               strategy, with_lists)
 
 
-class FMInstance:
+class FMInstance(_Handle):
     """The reference's FM recommender on one GPU (a `cmi_fm_handle`)."""
 
+    _api = ("cmi_fm_create", "cmi_fm_destroy", "cmi_fm_last_error")
+
     def __init__(self, k, n_users, n_items, n_conds, n_ctx_dims, device=0, flags=0):
-        self.L = lib()
         self.k, self.n_users, self.n_items, self.n_conds = k, n_users, n_items, n_conds
         self.p = n_users + n_items + n_conds
-        self.h = _vp()
-        rc = self.L.cmi_fm_create(k, n_users, n_items, n_conds, n_ctx_dims, device, flags, C.byref(self.h))
-        if rc != OK:
-            self.h = None
-            raise CmiError(rc, self.L.cmi_fm_last_error(None).decode())
-
-    def _chk(self, rc):
-        if rc != OK:
-            raise CmiError(rc, self.L.cmi_fm_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.cmi_fm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(k, n_users, n_items, n_conds, n_ctx_dims, device, flags)
 
     def set_hparams(self, regLw, regLf, global_size=0):
         self._chk(self.L.cmi_fm_set_hparams(self.h, regLw, regLf, global_size))
@@ -939,34 +916,16 @@ def knn_measure(name):
     return lib().cmi_knn_measure(name.encode())
 
 
-class KNNInstance:
+class KNNInstance(_Handle):
     """The reference's ItemKNN (kind="item") or UserKNN (kind="user") on one GPU (a `cmi_knn_handle`)."""
 
+    _api = ("cmi_knn_create", "cmi_knn_destroy", "cmi_knn_last_error")
+
     def __init__(self, kind, n_users, n_items, device=0, flags=0):
-        self.L = lib()
         k = {"user": KNN_USER, "item": KNN_ITEM}.get(kind, kind)
         self.kind, self.n_users, self.n_items = k, n_users, n_items
         self.n = n_items if k == KNN_ITEM else n_users
-        self.h = _vp()
-        rc = self.L.cmi_knn_create(k if isinstance(k, int) else -1, n_users, n_items, device, flags, C.byref(self.h))
-        if rc != OK:
-            self.h = None
-            raise CmiError(rc, self.L.cmi_knn_last_error(None).decode())
-
-    def _chk(self, rc):
-        if rc != OK:
-            raise CmiError(rc, self.L.cmi_knn_last_error(self.h).decode())
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.cmi_knn_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().__init__(k if isinstance(k, int) else -1, n_users, n_items, device, flags)
 
     def set_ratings(self, u, i, r):
         """the 2-D train matrix as cells (user, item, value)"""

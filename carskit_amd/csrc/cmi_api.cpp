@@ -19,6 +19,7 @@
 #include <mutex>
 #include <vector>
 
+#include "abi.hpp"
 #include "cmi_instance.hpp"
 #include "host_pool.hpp"
 #include "level_schedule.hpp"
@@ -27,7 +28,10 @@
 
 using namespace cmi;
 
-static thread_local std::string g_create_err;
+std::string &cmi_thread_err() {
+    static thread_local std::string err;
+    return err;
+}
 
 #include "owner_gate.hpp"
 
@@ -77,28 +81,16 @@ extern "C" int cmi_device_count(void) {
     return n;
 }
 
-extern "C" const char *cmi_last_error(cmi_handle h) { return h ? h->err.c_str() : g_create_err.c_str(); }
+extern "C" const char *cmi_last_error(cmi_handle h) { return h ? h->err.c_str() : cmi_thread_err().c_str(); }
 
 static void free_eval_set(cmi_instance *h) {
-    void *ptrs[] = {h->d_eu, h->d_ej, h->d_ectx, h->d_er, h->d_epart};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    h->d_eu = h->d_ej = h->d_ectx = nullptr;
-    h->d_er = h->d_epart = nullptr;
+    abi_free(h->d_eu, h->d_ej, h->d_ectx, h->d_er, h->d_epart);
     h->n_eval = 0;
-}
-
-static void free_and_null(std::initializer_list<void **> ptrs) {
-    for (void **p : ptrs)
-        if (*p) {
-            hipFree(*p);
-            *p = nullptr;
-        }
 }
 
 // the spoke arena and its position lists; the model table is the master copy again
 static void release_arena(cmi_instance *h) {
-    free_and_null({(void **)&h->d_arena, (void **)&h->d_next, (void **)&h->d_first});
+    abi_free(h->d_arena, h->d_next, h->d_first);
     h->arena_on = h->arena_valid = false;
     h->table_valid = true;
 }
@@ -113,10 +105,8 @@ static void free_ratings(cmi_instance *h) {
         hipGraphExecDestroy(h->graph_exec);
         h->graph_exec = nullptr;
     }
-    free_and_null({(void **)&h->d_su, (void **)&h->d_sj, (void **)&h->d_sconds, (void **)&h->d_ctx_ptr, (void **)&h->d_ctx_conds,
-                   (void **)&h->d_sr, (void **)&h->d_loss_part, (void **)&h->d_flow_err, (void **)&h->d_tail_off, (void **)&h->d_blk_off,
-                   (void **)&h->d_unit_off, (void **)&h->d_ui_ptr, (void **)&h->d_ui_items, (void **)&h->d_own_recs, (void **)&h->d_own_off,
-                   (void **)&h->d_tagged});
+    abi_free(h->d_su, h->d_sj, h->d_sconds, h->d_ctx_ptr, h->d_ctx_conds, h->d_sr, h->d_loss_part, h->d_flow_err, h->d_tail_off, h->d_blk_off,
+             h->d_unit_off, h->d_ui_ptr, h->d_ui_items, h->d_own_recs, h->d_own_off, h->d_tagged);
     h->sched = Sched::NONE;
     h->level_kernel = LevelKernel::GENERIC;
     h->owner_stalled = false;
@@ -135,17 +125,8 @@ extern "C" int cmi_destroy(cmi_handle h) {
     free_ratings(h);
     cmi_comm_release(h);
     h->rank_ws.release();
-    for (void *&p : h->state)
-        if (p) {
-            hipFree(p);
-            p = nullptr;
-        }
-    if (h->d_empty) hipFree(h->d_empty);
-    if (h->d_xbucket) hipFree(h->d_xbucket);
-    if (h->d_xsnap) hipFree(h->d_xsnap);
-    if (h->d_scratch) hipFree(h->d_scratch);
-    if (h->d_loss) hipFree(h->d_loss);
-    if (h->d_hp) hipFree(h->d_hp);
+    for (void *&p : h->state) abi_free(p);
+    abi_free(h->d_empty, h->d_xbucket, h->d_xsnap, h->d_scratch, h->d_loss, h->d_hp);
     if (h->h_loss) hipHostFree(h->h_loss);
     if (h->ev0) hipEventDestroy(h->ev0);
     if (h->ev1) hipEventDestroy(h->ev1);
@@ -156,75 +137,69 @@ extern "C" int cmi_destroy(cmi_handle h) {
 
 extern "C" int cmi_create(int model, int k, int n_users, int n_items, int n_conds, int device, unsigned flags,
                           cmi_handle *out) {
-    if (out) *out = nullptr;
-    if (!out || model < 0 || model > CMI_MODEL_CAMF_MCS || k <= 0 || n_users <= 0 || n_items <= 0 || n_conds < 0) {
-        g_create_err = "cmi_create: invalid argument";
-        return CMI_E_INVALID;
-    }
-    int ndev = cmi_device_count();
-    if (ndev <= 0) {
-        g_create_err = "cmi_create: no HIP device visible (libcarskit_mi355x has no CPU fallback)";
-        return CMI_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        g_create_err = "cmi_create: device index out of range";
-        return CMI_E_INVALID;
-    }
-    if (model == CMI_MODEL_CAMF_C && !(flags & CMI_FLAG_SCHED_SERIAL)) {
-        g_create_err =
-            "cmi_create: CAMF_C updates the shared condBias vector on every tuple, so its tuples do not commute and "
-            "no order-exact level schedule exists; pass CMI_FLAG_SCHED_SERIAL";
-        return CMI_E_UNSUPPORTED;
-    }
-    if (is_ext_model(model) && !(flags & CMI_FLAG_SCHED_SERIAL)) {
-        g_create_err =
-            "cmi_create: SVD++ / CAMF_ICS / CAMF_LCS / CAMF_MCS update parameters shared by (nearly) every tuple, so no order-exact "
-            "parallel schedule exists; pass CMI_FLAG_SCHED_SERIAL";
-        return CMI_E_UNSUPPORTED;
-    }
-    cmi_instance *h = new cmi_instance();
-    h->model = model;
-    h->k = k;
-    h->n_users = n_users;
-    h->n_items = n_items;
-    h->n_conds = n_conds;
-    h->device = device;
-    h->flags = flags;
-    h->f64 = flags & CMI_FLAG_STATE_F64;
-    h->strict = flags & CMI_FLAG_STRICT;
-    h->use_graph = !(flags & CMI_FLAG_NO_GRAPH);
-    const char *step = "";
-    hipError_t e = hipSuccess;
-#define TRY(x)                                                                                          \
-    if (e == hipSuccess) {                                                                              \
-        step = #x;                                                                                      \
-        e = (x);                                                                                        \
-    }
-    TRY(hipSetDevice(device));
-    TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    TRY(hipEventCreate(&h->ev0));
-    TRY(hipEventCreate(&h->ev1));
-    for (int w = 0; w < CMI_STATE_COUNT; ++w) {
-        if (!cmi_model_has(model, w)) continue;
-        h->state_count[w] = state_elems(h, w);
-        size_t bytes = (size_t)h->state_count[w] * esize(h);
-        if (bytes == 0) continue;
-        TRY(hipMalloc(&h->state[w], bytes));
-        TRY(hipMemsetAsync(h->state[w], 0, bytes, h->stream));
-    }
-    TRY(hipMalloc((void **)&h->d_scratch, 256 * sizeof(double)));
-    TRY(hipMalloc((void **)&h->d_loss, sizeof(double)));
-    TRY(hipMalloc((void **)&h->d_hp, sizeof(HParams)));
-    TRY(hipHostMalloc((void **)&h->h_loss, sizeof(double), hipHostMallocDefault));
-    TRY(hipStreamSynchronize(h->stream));
-#undef TRY
-    if (e != hipSuccess) {
-        g_create_err = std::string("cmi_create: ") + step + " failed: " + hipGetErrorString(e);
-        cmi_destroy(h);
-        return CMI_E_HIP;
-    }
-    *out = h;
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_create", [&] {
+        if (out) *out = nullptr;
+        if (!out || model < 0 || model > CMI_MODEL_CAMF_MCS || k <= 0 || n_users <= 0 || n_items <= 0 || n_conds < 0) {
+            cmi_thread_err() = "cmi_create: invalid argument";
+            return CMI_E_INVALID;
+        }
+        if (int rc = abi_check_device(cmi_thread_err(), "cmi_create", device)) return rc;
+        if (model == CMI_MODEL_CAMF_C && !(flags & CMI_FLAG_SCHED_SERIAL)) {
+            cmi_thread_err() =
+                "cmi_create: CAMF_C updates the shared condBias vector on every tuple, so its tuples do not commute and "
+                "no order-exact level schedule exists; pass CMI_FLAG_SCHED_SERIAL";
+            return CMI_E_UNSUPPORTED;
+        }
+        if (is_ext_model(model) && !(flags & CMI_FLAG_SCHED_SERIAL)) {
+            cmi_thread_err() =
+                "cmi_create: SVD++ / CAMF_ICS / CAMF_LCS / CAMF_MCS update parameters shared by (nearly) every tuple, so no order-exact "
+                "parallel schedule exists; pass CMI_FLAG_SCHED_SERIAL";
+            return CMI_E_UNSUPPORTED;
+        }
+        cmi_instance *h = new cmi_instance();
+        h->model = model;
+        h->k = k;
+        h->n_users = n_users;
+        h->n_items = n_items;
+        h->n_conds = n_conds;
+        h->device = device;
+        h->flags = flags;
+        h->f64 = flags & CMI_FLAG_STATE_F64;
+        h->strict = flags & CMI_FLAG_STRICT;
+        h->use_graph = !(flags & CMI_FLAG_NO_GRAPH);
+        const char *step = "";
+        hipError_t e = hipSuccess;
+    #define TRY(x)                                                                                          \
+        if (e == hipSuccess) {                                                                              \
+            step = #x;                                                                                      \
+            e = (x);                                                                                        \
+        }
+        TRY(hipSetDevice(device));
+        TRY(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+        TRY(hipEventCreate(&h->ev0));
+        TRY(hipEventCreate(&h->ev1));
+        for (int w = 0; w < CMI_STATE_COUNT; ++w) {
+            if (!cmi_model_has(model, w)) continue;
+            h->state_count[w] = state_elems(h, w);
+            size_t bytes = (size_t)h->state_count[w] * esize(h);
+            if (bytes == 0) continue;
+            TRY(hipMalloc(&h->state[w], bytes));
+            TRY(hipMemsetAsync(h->state[w], 0, bytes, h->stream));
+        }
+        TRY(hipMalloc((void **)&h->d_scratch, 256 * sizeof(double)));
+        TRY(hipMalloc((void **)&h->d_loss, sizeof(double)));
+        TRY(hipMalloc((void **)&h->d_hp, sizeof(HParams)));
+        TRY(hipHostMalloc((void **)&h->h_loss, sizeof(double), hipHostMallocDefault));
+        TRY(hipStreamSynchronize(h->stream));
+    #undef TRY
+        if (e != hipSuccess) {
+            cmi_thread_err() = std::string("cmi_create: ") + step + " failed: " + hipGetErrorString(e);
+            cmi_destroy(h);
+            return CMI_E_HIP;
+        }
+        *out = h;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_set_hparams(cmi_handle h, double regU, double regI, double regB, double regC, double global_mean) {
@@ -246,38 +221,40 @@ extern "C" int cmi_set_device_share(cmi_handle h, int instances) {
 
 extern "C" int cmi_set_sim_params(cmi_handle h, int num_f, int n_ctx_dims, const int32_t *empty_conds, int n_empty) {
     if (!h) return CMI_E_INVALID;
-    if (!is_ext_model(h->model) || h->model == CMI_MODEL_SVDPP) return CMI_OK; // nothing to configure
-    if (n_empty < 0 || (n_empty > 0 && !empty_conds) || n_ctx_dims < 1 || (h->model == CMI_MODEL_CAMF_LCS && num_f < 1))
-        CMI_FAIL(h, CMI_E_INVALID, "set_sim_params: invalid argument");
-    for (int i = 0; i < n_empty; ++i)
-        if (empty_conds[i] < 0 || empty_conds[i] >= h->n_conds) CMI_FAIL(h, CMI_E_INVALID, "set_sim_params: empty condition id %d out of range", empty_conds[i]);
-    CMI_HIP(h, hipSetDevice(h->device));
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    h->n_ctx_dims = n_ctx_dims;
-    h->sim_params_set = true;
-    h->empty_conds.assign(empty_conds, empty_conds + n_empty);
-    if (h->d_empty) hipFree(h->d_empty);
-    h->d_empty = nullptr;
-    if (n_empty > 0) {
-        CMI_HIP(h, hipMalloc((void **)&h->d_empty, (size_t)n_empty * 4));
-        // (never the legacy stream: a synchronous hipMemcpy / hipMemset fails with hipErrorStreamCaptureImplicit while ANOTHER fold's
-        //  thread is capturing its level graph -- found by tests/test_gpu_soak.py)
-        CMI_HIP(h, hipMemcpyAsync(h->d_empty, empty_conds, (size_t)n_empty * 4, hipMemcpyHostToDevice, h->stream));
+    return abi_barrier(h->err, "set_sim_params", [&] {
+        if (!is_ext_model(h->model) || h->model == CMI_MODEL_SVDPP) return CMI_OK; // nothing to configure
+        if (n_empty < 0 || (n_empty > 0 && !empty_conds) || n_ctx_dims < 1 || (h->model == CMI_MODEL_CAMF_LCS && num_f < 1))
+            CMI_FAIL(h, CMI_E_INVALID, "set_sim_params: invalid argument");
+        for (int i = 0; i < n_empty; ++i)
+            if (empty_conds[i] < 0 || empty_conds[i] >= h->n_conds) CMI_FAIL(h, CMI_E_INVALID, "set_sim_params: empty condition id %d out of range", empty_conds[i]);
+        CMI_HIP(h, hipSetDevice(h->device));
         CMI_HIP(h, hipStreamSynchronize(h->stream));
-    }
-    if (h->model == CMI_MODEL_CAMF_LCS && num_f != h->num_f) {
-        if (h->state[CMI_STATE_CF_MATRIX]) hipFree(h->state[CMI_STATE_CF_MATRIX]);
-        h->state[CMI_STATE_CF_MATRIX] = nullptr;
-        h->num_f = num_f;
-        h->state_count[CMI_STATE_CF_MATRIX] = (int64_t)h->n_conds * num_f;
-        const size_t bytes = (size_t)h->state_count[CMI_STATE_CF_MATRIX] * esize(h);
-        if (bytes) {
-            CMI_HIP(h, hipMalloc(&h->state[CMI_STATE_CF_MATRIX], bytes));
-            CMI_HIP(h, hipMemsetAsync(h->state[CMI_STATE_CF_MATRIX], 0, bytes, h->stream));
+        h->n_ctx_dims = n_ctx_dims;
+        h->sim_params_set = true;
+        h->empty_conds.assign(empty_conds, empty_conds + n_empty);
+        if (h->d_empty) hipFree(h->d_empty);
+        h->d_empty = nullptr;
+        if (n_empty > 0) {
+            CMI_HIP(h, hipMalloc((void **)&h->d_empty, (size_t)n_empty * 4));
+            // (never the legacy stream: a synchronous hipMemcpy / hipMemset fails with hipErrorStreamCaptureImplicit while ANOTHER fold's
+            //  thread is capturing its level graph -- found by tests/test_gpu_soak.py)
+            CMI_HIP(h, hipMemcpyAsync(h->d_empty, empty_conds, (size_t)n_empty * 4, hipMemcpyHostToDevice, h->stream));
             CMI_HIP(h, hipStreamSynchronize(h->stream));
         }
-    }
-    return CMI_OK;
+        if (h->model == CMI_MODEL_CAMF_LCS && num_f != h->num_f) {
+            if (h->state[CMI_STATE_CF_MATRIX]) hipFree(h->state[CMI_STATE_CF_MATRIX]);
+            h->state[CMI_STATE_CF_MATRIX] = nullptr;
+            h->num_f = num_f;
+            h->state_count[CMI_STATE_CF_MATRIX] = (int64_t)h->n_conds * num_f;
+            const size_t bytes = (size_t)h->state_count[CMI_STATE_CF_MATRIX] * esize(h);
+            if (bytes) {
+                CMI_HIP(h, hipMalloc(&h->state[CMI_STATE_CF_MATRIX], bytes));
+                CMI_HIP(h, hipMemsetAsync(h->state[CMI_STATE_CF_MATRIX], 0, bytes, h->stream));
+                CMI_HIP(h, hipStreamSynchronize(h->stream));
+            }
+        }
+        return CMI_OK;
+    });
 }
 
 // ---- state copy-in / copy-back -------------------------------------------------------------------
@@ -372,23 +349,6 @@ extern "C" int cmi_state_device_ptr(cmi_handle h, int which, void **ptr, int64_t
 
 // ---- ratings + schedule ----------------------------------------------------------------------------
 
-template <typename V>
-static hipError_t upload(void **dst, const std::vector<V> &v, hipStream_t s) {
-    *dst = nullptr;
-    if (v.empty()) return hipSuccess;
-    hipError_t e = hipMalloc(dst, v.size() * sizeof(V));
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(V), hipMemcpyHostToDevice, s);
-}
-
-template <typename V>
-static hipError_t upload(void **dst, const V *v, size_t count, hipStream_t s) {
-    *dst = nullptr;
-    if (!count) return hipSuccess;
-    hipError_t e = hipMalloc(dst, count * sizeof(V));
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*dst, v, count * sizeof(V), hipMemcpyHostToDevice, s);
-}
 // a host array that is written once, in ranges, before it is read: not zero-filled first (5.6 GB for the north_star tuple stream)
 template <typename V>
 struct HostBuf {
@@ -400,9 +360,9 @@ struct HostBuf {
     V &operator[](size_t i) { return p[i]; }
     const V &operator[](size_t i) const { return p[i]; }
 };
-template <typename V>
-static hipError_t upload(void **dst, const HostBuf<V> &v, hipStream_t s) {
-    return upload(dst, v.data(), v.n, s);
+template <typename D, typename V>
+static hipError_t abi_upload(D **dst, const HostBuf<V> &v, hipStream_t s) {
+    return abi_upload(dst, v.data(), v.n, s);
 }
 
 // Spoke arena bookkeeping: next[p] = stream position of the next tuple of the same spoke row (a row's tuples sit in ascending levels,
@@ -469,11 +429,13 @@ static void arena_positions(int64_t n, const int32_t *spoke, int64_t n_spokes, i
 }
 // host-only export of the same (tests/test_chain_schedule.py)
 extern "C" int cmi_arena_positions(int64_t n, const int32_t *spoke, int32_t n_spokes, int32_t *next, int32_t *first) {
-    if (n < 0 || n_spokes < 0 || (n > 0 && (!spoke || !next)) || (n_spokes > 0 && !first)) return CMI_E_INVALID;
-    for (int64_t p = 0; p < n; ++p)
-        if (spoke[p] < 0 || spoke[p] >= n_spokes) return CMI_E_INVALID;
-    arena_positions(n, spoke, n_spokes, next, first);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_arena_positions", [&] {
+        if (n < 0 || n_spokes < 0 || (n > 0 && (!spoke || !next)) || (n_spokes > 0 && !first)) return CMI_E_INVALID;
+        for (int64_t p = 0; p < n; ++p)
+            if (spoke[p] < 0 || spoke[p] >= n_spokes) return CMI_E_INVALID;
+        arena_positions(n, spoke, n_spokes, next, first);
+        return CMI_OK;
+    });
 }
 
 // CMI_CHAIN_HUB / CMI_OWNER_HUB = item | user (tests): the hub side forced; unset or anything else keeps `dflt`
@@ -916,16 +878,16 @@ static hipError_t upload_stream(cmi_instance *h, const RatingsIn &in, int dmax, 
     const int64_t ns = in.n;
     hipError_t e = hipSuccess;
     if (!dev_stream) {
-        e = upload((void **)&h->d_su, hs.su, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_sj, hs.sj, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_sconds, hs.sconds, h->stream);
-        if (e == hipSuccess) e = h->f64 ? upload(&h->d_sr, hs.sr64, h->stream) : upload(&h->d_sr, hs.sr32, h->stream);
+        e = abi_upload(&h->d_su, hs.su, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_sj, hs.sj, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_sconds, hs.sconds, h->stream);
+        if (e == hipSuccess) e = h->f64 ? abi_upload(&h->d_sr, hs.sr64, h->stream) : abi_upload(&h->d_sr, hs.sr32, h->stream);
     }
     if (e == hipSuccess && !is_2d_model(h->model)) {
         std::vector<int32_t> cp(in.ctx_ptr, in.ctx_ptr + in.n_ctx + 1), cc(in.ctx_conds, in.ctx_conds + in.ctx_ptr[in.n_ctx]);
         h->ctx_nnz = (int64_t)cc.size();
-        e = upload((void **)&h->d_ctx_ptr, cp, h->stream);
-        if (e == hipSuccess) e = upload((void **)&h->d_ctx_conds, cc, h->stream);
+        e = abi_upload(&h->d_ctx_ptr, cp, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_ctx_conds, cc, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // cp/cc are locals
     }
     if (e == hipSuccess && dev_stream) {
@@ -938,7 +900,7 @@ static hipError_t upload_stream(cmi_instance *h, const RatingsIn &in, int dmax, 
                                                 h->f64, h->d_su, h->d_sj, h->d_sconds, h->d_sr);
     }
     free_keep(keep);
-    if (e == hipSuccess && h->sched == Sched::CHAIN) e = upload((void **)&h->d_unit_off, csch.unit_off, h->stream);
+    if (e == hipSuccess && h->sched == Sched::CHAIN) e = abi_upload(&h->d_unit_off, csch.unit_off, h->stream);
     return e;
 }
 
@@ -1053,8 +1015,8 @@ static hipError_t pack_owner_records(cmi_instance *h, const RatingsIn &in, const
     }
     for (; w < h->n_owners; ++w) // owners without tuples (n == 0 never gets here)
         for (int i = 0; i < pad; ++i) nop(w);
-    hipError_t e = upload((void **)&h->d_own_recs, recs, h->stream);
-    if (e == hipSuccess) e = upload((void **)&h->d_own_off, osch.own_off, h->stream);
+    hipError_t e = abi_upload(&h->d_own_recs, recs, h->stream);
+    if (e == hipSuccess) e = abi_upload(&h->d_own_off, osch.own_off, h->stream);
     if (e == hipSuccess) e = hipMalloc(&h->d_tagged, ((size_t)n_spokes + (size_t)h->n_owners) * (size_t)h->own_stride * 8);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_flow_err, 16);
     if (e == hipSuccess) e = hipMemsetAsync(h->d_flow_err, 0, 16, h->stream);
@@ -1073,8 +1035,8 @@ static hipError_t build_user_items(cmi_instance *h, const RatingsIn &in) {
         for (int64_t t = 0; t < n; ++t) items[(size_t)cur[(size_t)in.u[t]]++] = in.j[t];
     }
     for (int32_t x = 0; x < h->n_users; ++x) std::sort(items.begin() + ptr[(size_t)x], items.begin() + ptr[(size_t)x + 1]);
-    hipError_t e = upload((void **)&h->d_ui_ptr, ptr, h->stream);
-    if (e == hipSuccess) e = upload((void **)&h->d_ui_items, items, h->stream);
+    hipError_t e = abi_upload(&h->d_ui_ptr, ptr, h->stream);
+    if (e == hipSuccess) e = abi_upload(&h->d_ui_items, items, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream); // ptr/items are locals
     return e;
 }
@@ -1087,8 +1049,8 @@ static hipError_t alloc_launch_buffers(cmi_instance *h) {
         e = hipMalloc((void **)&h->d_loss_part, (size_t)h->n_slots * sizeof(double));
         if (e == hipSuccess) e = hipMemsetAsync(h->d_loss_part, 0, (size_t)h->n_slots * sizeof(double), h->stream);
     }
-    if (e == hipSuccess && h->sched == Sched::CAMFC_BLOCKS) e = upload((void **)&h->d_blk_off, h->blk_off, h->stream);
-    if (e == hipSuccess && h->n_tail > 0) e = upload((void **)&h->d_tail_off, h->level_off, h->stream); // the tail launches read their level offsets from the device
+    if (e == hipSuccess && h->sched == Sched::CAMFC_BLOCKS) e = abi_upload(&h->d_blk_off, h->blk_off, h->stream);
+    if (e == hipSuccess && h->n_tail > 0) e = abi_upload(&h->d_tail_off, h->level_off, h->stream); // the tail launches read their level offsets from the device
     return e;
 }
 
@@ -1167,20 +1129,12 @@ static int set_ratings_impl(cmi_instance *h, const RatingsIn &in) {
     return rc;
 }
 
-// the exception barrier of the boundary: the schedule construction allocates O(tuples) host memory on the host pool's threads
-// (host_pool.hpp hands a range body's exception to the caller); nothing C++ may cross into a C / JNI / ctypes host
+// the schedule construction allocates O(tuples) host memory on the host pool's threads
 extern "C" int cmi_set_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                const double *r, int32_t n_ctx, const int32_t *ctx_ptr, const int32_t *ctx_conds) {
     if (!h) return CMI_E_INVALID;
-    try {
-        return set_ratings_impl(h, RatingsIn{n, u, j, ctx, r, n_ctx, ctx_ptr, ctx_conds});
-    } catch (const std::exception &e) {
-        free_ratings(h);
-        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure: %s", e.what());
-    } catch (...) {
-        free_ratings(h);
-        CMI_FAIL(h, CMI_E_HOST, "set_ratings: host-side failure (unknown exception)");
-    }
+    return abi_barrier(h->err, "set_ratings", [&] { return set_ratings_impl(h, RatingsIn{n, u, j, ctx, r, n_ctx, ctx_ptr, ctx_conds}); },
+                       [h] { free_ratings(h); });
 }
 
 extern "C" int cmi_schedule_info(cmi_handle h, int64_t info[8]) {
@@ -1295,17 +1249,19 @@ extern "C" int cmi_debug_owner_trace(cmi_handle h) {
 }
 extern "C" int cmi_debug_owner_trace_dump(cmi_handle h, const char *path) {
     if (!h || !h->d_trace || !path) return CMI_E_INVALID;
-    if (hipSetDevice(h->device) != hipSuccess) return CMI_E_HIP;
-    std::vector<double> host(h->trace_doubles);
-    CMI_HIP(h, hipMemcpyAsync(host.data(), h->d_trace, h->trace_doubles * 8, hipMemcpyDeviceToHost, h->stream));
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    FILE *f = fopen(path, "wb");
-    if (!f) CMI_FAIL(h, CMI_E_INVALID, "cannot open %s", path);
-    const size_t wrote = fwrite(host.data(), 8, host.size(), f);
-    fclose(f);
-    (void)hipFree(h->d_trace);
-    h->d_trace = nullptr;
-    return wrote == host.size() ? CMI_OK : CMI_E_INVALID;
+    return abi_barrier(h->err, "debug_owner_trace_dump", [&] {
+        if (hipSetDevice(h->device) != hipSuccess) return CMI_E_HIP;
+        std::vector<double> host(h->trace_doubles);
+        CMI_HIP(h, hipMemcpyAsync(host.data(), h->d_trace, h->trace_doubles * 8, hipMemcpyDeviceToHost, h->stream));
+        CMI_HIP(h, hipStreamSynchronize(h->stream));
+        FILE *f = fopen(path, "wb");
+        if (!f) CMI_FAIL(h, CMI_E_INVALID, "cannot open %s", path);
+        const size_t wrote = fwrite(host.data(), 8, host.size(), f);
+        fclose(f);
+        (void)hipFree(h->d_trace);
+        h->d_trace = nullptr;
+        return wrote == host.size() ? CMI_OK : CMI_E_INVALID;
+    });
 }
 #endif
 
@@ -1514,7 +1470,9 @@ static int arena_probe(cmi_instance *h) {
 
 extern "C" int cmi_train_epoch_async(cmi_handle h, double lrate) {
     if (!h) return CMI_E_INVALID;
-    return enqueue_epoch(h, lrate);
+    return abi_barrier(h->err, "train_epoch", [&] {
+        return enqueue_epoch(h, lrate);
+    });
 }
 
 extern "C" int cmi_last_loss(cmi_handle h, double *loss_out) {
@@ -1540,11 +1498,13 @@ extern "C" int cmi_last_loss(cmi_handle h, double *loss_out) {
 
 extern "C" int cmi_train_epoch(cmi_handle h, double lrate, double *loss_out) {
     if (!h) return CMI_E_INVALID;
-    if (int rc = enqueue_epoch(h, lrate)) return rc;
-    double loss = 0.0;
-    if (int rc = cmi_last_loss(h, &loss)) return rc;
-    if (loss_out) *loss_out = loss;
-    return CMI_OK;
+    return abi_barrier(h->err, "train_epoch", [&] {
+        if (int rc = enqueue_epoch(h, lrate)) return rc;
+        double loss = 0.0;
+        if (int rc = cmi_last_loss(h, &loss)) return rc;
+        if (loss_out) *loss_out = loss;
+        return CMI_OK;
+    });
 }
 
 // IterativeRecommender.isConverged + updateLRate (IterativeRecommender.java:145-229), host side.  first_iter / last_loss let a
@@ -1599,11 +1559,13 @@ extern "C" int cmi_train_from(cmi_handle h, int first_iter, double prev_loss, in
                               int bold_driver, double decay, int early_stop, double *losses, double *lrates, int *iters_run,
                               double *final_lrate) {
     if (!h) return CMI_E_INVALID;
-    std::string err;
-    const int rc = cmi_train_loop([h](double lr, double *loss) { return cmi_train_epoch(h, lr, loss); }, err, first_iter, prev_loss,
-                                  num_iters, init_lrate, max_lrate, bold_driver, decay, early_stop, losses, lrates, iters_run, final_lrate);
-    if (rc != CMI_OK && !err.empty()) h->err = err;
-    return rc;
+    return abi_barrier(h->err, "train", [&] {
+        std::string err;
+        const int rc = cmi_train_loop([h](double lr, double *loss) { return cmi_train_epoch(h, lr, loss); }, err, first_iter, prev_loss,
+                                      num_iters, init_lrate, max_lrate, bold_driver, decay, early_stop, losses, lrates, iters_run, final_lrate);
+        if (rc != CMI_OK && !err.empty()) h->err = err;
+        return rc;
+    });
 }
 
 extern "C" int cmi_train(cmi_handle h, int num_iters, double init_lrate, double max_lrate, int bold_driver,
@@ -1621,50 +1583,52 @@ extern "C" int cmi_stream(cmi_handle h, void **stream) {
 // ---- multi-GPU exchange plumbing ----------------------------------------------------------------------
 extern "C" int cmi_exchange_setup(cmi_handle h, int64_t pad_to, void **bucket, int64_t *count) {
     if (!h || !bucket || !count || pad_to < 1) return CMI_E_INVALID;
-    if (h->model == CMI_MODEL_CAMF_C) CMI_FAIL(h, CMI_E_UNSUPPORTED, "exchange: CAMF_C shares condBias between all tuples and is not sharded");
-    // SVD++ (Y) and CAMF_ICS / LCS / MCS (ccMatrix, cfMatrix, cVector) update containers every tuple reads: they are not in the bucket,
-    // so a merge would silently leave them diverged between the ranks
-    if (is_ext_model(h->model)) CMI_FAIL(h, CMI_E_UNSUPPORTED, "exchange: model %d is a single serial chain and is not sharded", h->model);
-    CMI_HIP(h, hipSetDevice(h->device));
-    if (int rc = cmi_sync_table_from_arena(h)) return rc;
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    if (h->d_xbucket) hipFree(h->d_xbucket);
-    if (h->d_xsnap) hipFree(h->d_xsnap);
-    h->d_xbucket = h->d_xsnap = nullptr;
-    h->x_which.clear();
-    h->x_off.clear();
-    int64_t off = 0;
-    for (int w : {CMI_STATE_Q, CMI_STATE_ITEM_BIAS, CMI_STATE_IC_BIAS}) {
-        if (!cmi_model_has(h->model, w)) continue;
-        h->x_which.push_back(w);
-        h->x_off.push_back(off);
-        off += (h->state_count[w] + 3) / 4 * 4;
-    }
-    {   // total: a multiple of pad_to (even split over the ranks of a reduce-scatter) and of 4 elements (16-byte vectors)
-        int64_t g = pad_to, r4 = 4;
-        while (r4) {
-            const int64_t t = g % r4;
-            g = r4;
-            r4 = t;
+    return abi_barrier(h->err, "exchange_setup", [&] {
+        if (h->model == CMI_MODEL_CAMF_C) CMI_FAIL(h, CMI_E_UNSUPPORTED, "exchange: CAMF_C shares condBias between all tuples and is not sharded");
+        // SVD++ (Y) and CAMF_ICS / LCS / MCS (ccMatrix, cfMatrix, cVector) update containers every tuple reads: they are not in the bucket,
+        // so a merge would silently leave them diverged between the ranks
+        if (is_ext_model(h->model)) CMI_FAIL(h, CMI_E_UNSUPPORTED, "exchange: model %d is a single serial chain and is not sharded", h->model);
+        CMI_HIP(h, hipSetDevice(h->device));
+        if (int rc = cmi_sync_table_from_arena(h)) return rc;
+        CMI_HIP(h, hipStreamSynchronize(h->stream));
+        if (h->d_xbucket) hipFree(h->d_xbucket);
+        if (h->d_xsnap) hipFree(h->d_xsnap);
+        h->d_xbucket = h->d_xsnap = nullptr;
+        h->x_which.clear();
+        h->x_off.clear();
+        int64_t off = 0;
+        for (int w : {CMI_STATE_Q, CMI_STATE_ITEM_BIAS, CMI_STATE_IC_BIAS}) {
+            if (!cmi_model_has(h->model, w)) continue;
+            h->x_which.push_back(w);
+            h->x_off.push_back(off);
+            off += (h->state_count[w] + 3) / 4 * 4;
         }
-        const int64_t step = pad_to / g * 4;
-        off = (off + step - 1) / step * step;
-    }
-    h->x_count = off;
-    const size_t bytes = (size_t)off * esize(h);
-    CMI_HIP(h, hipMalloc(&h->d_xbucket, bytes));
-    CMI_HIP(h, hipMalloc(&h->d_xsnap, bytes));
-    CMI_HIP(h, hipMemsetAsync(h->d_xbucket, 0, bytes, h->stream));
-    CMI_HIP(h, hipMemsetAsync(h->d_xsnap, 0, bytes, h->stream));
-    for (size_t i = 0; i < h->x_which.size(); ++i) {
-        const int w = h->x_which[i];
-        CMI_HIP(h, hipMemcpyAsync((char *)h->d_xsnap + (size_t)h->x_off[i] * esize(h), h->state[w], (size_t)h->state_count[w] * esize(h),
-                                  hipMemcpyDeviceToDevice, h->stream));
-    }
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    *bucket = h->d_xbucket;
-    *count = h->x_count;
-    return CMI_OK;
+        {   // total: a multiple of pad_to (even split over the ranks of a reduce-scatter) and of 4 elements (16-byte vectors)
+            int64_t g = pad_to, r4 = 4;
+            while (r4) {
+                const int64_t t = g % r4;
+                g = r4;
+                r4 = t;
+            }
+            const int64_t step = pad_to / g * 4;
+            off = (off + step - 1) / step * step;
+        }
+        h->x_count = off;
+        const size_t bytes = (size_t)off * esize(h);
+        CMI_HIP(h, hipMalloc(&h->d_xbucket, bytes));
+        CMI_HIP(h, hipMalloc(&h->d_xsnap, bytes));
+        CMI_HIP(h, hipMemsetAsync(h->d_xbucket, 0, bytes, h->stream));
+        CMI_HIP(h, hipMemsetAsync(h->d_xsnap, 0, bytes, h->stream));
+        for (size_t i = 0; i < h->x_which.size(); ++i) {
+            const int w = h->x_which[i];
+            CMI_HIP(h, hipMemcpyAsync((char *)h->d_xsnap + (size_t)h->x_off[i] * esize(h), h->state[w], (size_t)h->state_count[w] * esize(h),
+                                      hipMemcpyDeviceToDevice, h->stream));
+        }
+        CMI_HIP(h, hipStreamSynchronize(h->stream));
+        *bucket = h->d_xbucket;
+        *count = h->x_count;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_exchange_pack(cmi_handle h) {
@@ -1843,26 +1807,30 @@ static int eval_common(cmi_instance *h, int64_t n, const int32_t *u, const int32
 extern "C" int cmi_predict_batch(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                  int bound, double lo, double hi, double *out) {
     if (!h) return CMI_E_INVALID;
-    if (n > 0 && !out) CMI_FAIL(h, CMI_E_INVALID, "predict_batch: null output");
-    double sums[5];
-    return eval_common(h, n, u, j, ctx, nullptr, bound, lo, hi, 1.0, out, sums);
+    return abi_barrier(h->err, "predict_batch", [&] {
+        if (n > 0 && !out) CMI_FAIL(h, CMI_E_INVALID, "predict_batch: null output");
+        double sums[5];
+        return eval_common(h, n, u, j, ctx, nullptr, bound, lo, hi, 1.0, out, sums);
+    });
 }
 
 extern "C" int cmi_eval_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                 const double *r, double min_rate, double max_rate, double *out, int64_t *count) {
     if (!h) return CMI_E_INVALID;
-    if (!out || (n > 0 && !r)) CMI_FAIL(h, CMI_E_INVALID, "eval_ratings: null argument");
-    double sums[5];
-    if (int rc = eval_common(h, n, u, j, ctx, r, 1, min_rate, max_rate, min_rate, nullptr, sums)) return rc;
-    const double cnt = sums[4];
-    const double mae = sums[0] / cnt;
-    out[0] = mae;
-    out[1] = std::sqrt(sums[1] / cnt);
-    out[2] = mae / (max_rate - min_rate);
-    out[3] = sums[2] / cnt;
-    out[4] = std::sqrt(sums[3] / cnt);
-    if (count) *count = (int64_t)cnt;
-    return CMI_OK;
+    return abi_barrier(h->err, "eval_ratings", [&] {
+        if (!out || (n > 0 && !r)) CMI_FAIL(h, CMI_E_INVALID, "eval_ratings: null argument");
+        double sums[5];
+        if (int rc = eval_common(h, n, u, j, ctx, r, 1, min_rate, max_rate, min_rate, nullptr, sums)) return rc;
+        const double cnt = sums[4];
+        const double mae = sums[0] / cnt;
+        out[0] = mae;
+        out[1] = std::sqrt(sums[1] / cnt);
+        out[2] = mae / (max_rate - min_rate);
+        out[3] = sums[2] / cnt;
+        out[4] = std::sqrt(sums[3] / cnt);
+        if (count) *count = (int64_t)cnt;
+        return CMI_OK;
+    });
 }
 
 // the five sums behind cmi_eval_ratings (sum|e|, sum e^2, rounded forms, count), so that cmi_group_eval_ratings can merge shards exactly
@@ -1930,120 +1898,134 @@ int cmi_eval_resident_sums(cmi_instance *h, double min_rate, double max_rate, do
 
 extern "C" int cmi_eval_resident(cmi_handle h, double min_rate, double max_rate, double out[5], int64_t *count) {
     if (!h || !out) return CMI_E_INVALID;
-    double sums[5];
-    if (int rc = cmi_eval_resident_sums(h, min_rate, max_rate, sums)) return rc;
-    const double cnt = sums[4];
-    const double mae = sums[0] / cnt;
-    out[0] = mae;
-    out[1] = std::sqrt(sums[1] / cnt);
-    out[2] = mae / (max_rate - min_rate);
-    out[3] = sums[2] / cnt;
-    out[4] = std::sqrt(sums[3] / cnt);
-    if (count) *count = (int64_t)cnt;
-    return CMI_OK;
+    return abi_barrier(h->err, "eval_resident", [&] {
+        double sums[5];
+        if (int rc = cmi_eval_resident_sums(h, min_rate, max_rate, sums)) return rc;
+        const double cnt = sums[4];
+        const double mae = sums[0] / cnt;
+        out[0] = mae;
+        out[1] = std::sqrt(sums[1] / cnt);
+        out[2] = mae / (max_rate - min_rate);
+        out[3] = sums[2] / cnt;
+        out[4] = std::sqrt(sums[3] / cnt);
+        if (count) *count = (int64_t)cnt;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_level_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items,
                                   int order, int32_t *perm, int64_t *level_off, int64_t level_cap,
                                   int64_t *n_levels) {
-    if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_levels || order < 0 || order > 3)
-        return CMI_E_INVALID;
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
-    LevelSchedule sch;
-    if (!build_level_schedule(n, u, j, n_users, n_items, order, sch)) return CMI_E_UNSUPPORTED;
-    *n_levels = sch.n_levels();
-    if (level_off) {
-        if (level_cap < sch.n_levels() + 1) return CMI_E_INVALID;
-        for (size_t i = 0; i < sch.level_off.size(); ++i) level_off[i] = sch.level_off[i];
-    }
-    if (perm)
-        for (int64_t s = 0; s < n; ++s) perm[s] = sch.perm[(size_t)s];
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_level_schedule", [&] {
+        if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_levels || order < 0 || order > 3)
+            return CMI_E_INVALID;
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
+        LevelSchedule sch;
+        if (!build_level_schedule(n, u, j, n_users, n_items, order, sch)) return CMI_E_UNSUPPORTED;
+        *n_levels = sch.n_levels();
+        if (level_off) {
+            if (level_cap < sch.n_levels() + 1) return CMI_E_INVALID;
+            for (size_t i = 0; i < sch.level_off.size(); ++i) level_off[i] = sch.level_off[i];
+        }
+        if (perm)
+            for (int64_t s = 0; s < n; ++s) perm[s] = sch.perm[(size_t)s];
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_chain_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int hub,
                                   int max_chain, int32_t *perm, int32_t *unit_off, int64_t unit_cap, int64_t *level_off,
                                   int64_t level_cap, int64_t *n_units, int64_t *n_levels, int *hub_used) {
-    if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_units || !n_levels || max_chain < 1) return CMI_E_INVALID;
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
-    ChainSchedule cs;
-    if (!build_chain_schedule(n, u, j, n_users, n_items, hub, max_chain, cs)) return CMI_E_UNSUPPORTED;
-    *n_units = cs.n_units();
-    *n_levels = cs.n_levels();
-    if (hub_used) *hub_used = cs.hub_is_item;
-    if (!perm) return CMI_OK;
-    if (!unit_off || !level_off || unit_cap < cs.n_units() + 1 || level_cap < cs.n_levels() + 1) return CMI_E_INVALID;
-    std::copy(cs.perm.begin(), cs.perm.end(), perm);
-    std::copy(cs.unit_off.begin(), cs.unit_off.end(), unit_off);
-    std::copy(cs.level_off.begin(), cs.level_off.end(), level_off);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_chain_schedule", [&] {
+        if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_units || !n_levels || max_chain < 1) return CMI_E_INVALID;
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
+        ChainSchedule cs;
+        if (!build_chain_schedule(n, u, j, n_users, n_items, hub, max_chain, cs)) return CMI_E_UNSUPPORTED;
+        *n_units = cs.n_units();
+        *n_levels = cs.n_levels();
+        if (hub_used) *hub_used = cs.hub_is_item;
+        if (!perm) return CMI_OK;
+        if (!unit_off || !level_off || unit_cap < cs.n_units() + 1 || level_cap < cs.n_levels() + 1) return CMI_E_INVALID;
+        std::copy(cs.perm.begin(), cs.perm.end(), perm);
+        std::copy(cs.unit_off.begin(), cs.unit_off.end(), unit_off);
+        std::copy(cs.level_off.begin(), cs.level_off.end(), level_off);
+        return CMI_OK;
+    });
 }
 
 // the same schedule built on the device (what cmi_set_ratings uses for large sets): tests compare the two element for element
 extern "C" int cmi_chain_schedule_device(int device, int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int hub,
                                          int max_chain, int32_t *perm, int32_t *unit_off, int64_t unit_cap, int64_t *level_off,
                                          int64_t level_cap, int64_t *n_units, int64_t *n_levels, int *hub_used) {
-    if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_units || !n_levels || max_chain < 1) return CMI_E_INVALID;
-    if (device < 0 || device >= cmi_device_count()) return CMI_E_NO_DEVICE;
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
-    ChainSchedule cs;
-    hipStream_t st = nullptr;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return CMI_E_HIP;
-    const bool ok = build_chain_schedule_device(device, st, n, u, j, n_users, n_items, hub, max_chain, cs);
-    (void)hipStreamDestroy(st);
-    if (!ok) return CMI_E_UNSUPPORTED;
-    *n_units = cs.n_units();
-    *n_levels = cs.n_levels();
-    if (hub_used) *hub_used = cs.hub_is_item;
-    if (!perm) return CMI_OK;
-    if (!unit_off || !level_off || unit_cap < cs.n_units() + 1 || level_cap < cs.n_levels() + 1) return CMI_E_INVALID;
-    std::copy(cs.perm.begin(), cs.perm.end(), perm);
-    std::copy(cs.unit_off.begin(), cs.unit_off.end(), unit_off);
-    std::copy(cs.level_off.begin(), cs.level_off.end(), level_off);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_chain_schedule_device", [&] {
+        if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || !n_units || !n_levels || max_chain < 1) return CMI_E_INVALID;
+        if (device < 0 || device >= cmi_device_count()) return CMI_E_NO_DEVICE;
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
+        ChainSchedule cs;
+        hipStream_t st = nullptr;
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return CMI_E_HIP;
+        const bool ok = build_chain_schedule_device(device, st, n, u, j, n_users, n_items, hub, max_chain, cs);
+        (void)hipStreamDestroy(st);
+        if (!ok) return CMI_E_UNSUPPORTED;
+        *n_units = cs.n_units();
+        *n_levels = cs.n_levels();
+        if (hub_used) *hub_used = cs.hub_is_item;
+        if (!perm) return CMI_OK;
+        if (!unit_off || !level_off || unit_cap < cs.n_units() + 1 || level_cap < cs.n_levels() + 1) return CMI_E_INVALID;
+        std::copy(cs.perm.begin(), cs.perm.end(), perm);
+        std::copy(cs.unit_off.begin(), cs.unit_off.end(), unit_off);
+        std::copy(cs.level_off.begin(), cs.level_off.end(), level_off);
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_owner_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int hub, int n_owners,
                                   int depth, int32_t *perm, int64_t *own_off, uint32_t *want, uint32_t *flags, int *hub_used) {
-    if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || n_owners < 1 || depth < 1 || !perm || !own_off || !want || !flags)
-        return CMI_E_INVALID;
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
-    OwnerSchedule os;
-    if (!build_owner_schedule(n, u, j, n_users, n_items, hub, n_owners, depth, os)) return CMI_E_UNSUPPORTED;
-    if (hub_used) *hub_used = os.hub_is_item;
-    std::copy(os.perm.begin(), os.perm.end(), perm);
-    std::copy(os.own_off.begin(), os.own_off.end(), own_off);
-    std::copy(os.want.begin(), os.want.end(), want);
-    std::copy(os.flags.begin(), os.flags.end(), flags);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_owner_schedule", [&] {
+        if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || n_owners < 1 || depth < 1 || !perm || !own_off || !want || !flags)
+            return CMI_E_INVALID;
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
+        OwnerSchedule os;
+        if (!build_owner_schedule(n, u, j, n_users, n_items, hub, n_owners, depth, os)) return CMI_E_UNSUPPORTED;
+        if (hub_used) *hub_used = os.hub_is_item;
+        std::copy(os.perm.begin(), os.perm.end(), perm);
+        std::copy(os.own_off.begin(), os.own_off.end(), own_off);
+        std::copy(os.want.begin(), os.want.end(), want);
+        std::copy(os.flags.begin(), os.flags.end(), flags);
+        return CMI_OK;
+    });
 }
 
 // host-only views of the two schedule post-passes (tests): narrow runs of a level schedule, conflict-free CRS blocks
 extern "C" int cmi_narrow_runs(int64_t n_levels, const int64_t *level_off, int64_t max_tuples, int64_t min_levels,
                                int32_t *run_len, int64_t *n_launches) {
-    if (n_levels < 0 || !level_off || !n_launches || (n_levels > 0 && !run_len)) return CMI_E_INVALID;
-    std::vector<int64_t> off(level_off, level_off + n_levels + 1);
-    std::vector<int32_t> rl;
-    *n_launches = build_narrow_runs(off, max_tuples, min_levels, rl);
-    for (int64_t l = 0; l < n_levels; ++l) run_len[l] = rl[(size_t)l];
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_narrow_runs", [&] {
+        if (n_levels < 0 || !level_off || !n_launches || (n_levels > 0 && !run_len)) return CMI_E_INVALID;
+        std::vector<int64_t> off(level_off, level_off + n_levels + 1);
+        std::vector<int32_t> rl;
+        *n_launches = build_narrow_runs(off, max_tuples, min_levels, rl);
+        for (int64_t l = 0; l < n_levels; ++l) run_len[l] = rl[(size_t)l];
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items,
                                         int32_t max_block, int32_t *off, int64_t off_cap, int64_t *n_blocks) {
-    if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || max_block <= 0 || !n_blocks || n >= ((int64_t)1 << 31))
-        return CMI_E_INVALID;
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
-    std::vector<int32_t> o;
-    build_conflict_free_blocks(n, u, j, n_users, n_items, max_block, o);
-    *n_blocks = (int64_t)o.size() - 1;
-    if (!off) return CMI_OK;
-    if (off_cap < (int64_t)o.size()) return CMI_E_INVALID;
-    std::copy(o.begin(), o.end(), off);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_conflict_free_blocks", [&] {
+        if (n < 0 || (n > 0 && (!u || !j)) || n_users <= 0 || n_items <= 0 || max_block <= 0 || !n_blocks || n >= ((int64_t)1 << 31))
+            return CMI_E_INVALID;
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items) return CMI_E_INVALID;
+        std::vector<int32_t> o;
+        build_conflict_free_blocks(n, u, j, n_users, n_items, max_block, o);
+        *n_blocks = (int64_t)o.size() - 1;
+        if (!off) return CMI_OK;
+        if (off_cap < (int64_t)o.size()) return CMI_E_INVALID;
+        std::copy(o.begin(), o.end(), off);
+        return CMI_OK;
+    });
 }

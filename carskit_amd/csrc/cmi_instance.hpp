@@ -109,20 +109,6 @@ struct cmi_instance {
     double last_rank_flops = 0.0; // 2 * queries * candidates * padded operand length of that loop
 };
 
-#define CMI_FAIL(h, code, ...)                                                                          \
-    do {                                                                                                \
-        char buf_[512];                                                                                 \
-        snprintf(buf_, sizeof buf_, __VA_ARGS__);                                                       \
-        (h)->err = buf_;                                                                                \
-        return (code);                                                                                  \
-    } while (0)
-
-#define CMI_HIP(h, expr)                                                                                \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) CMI_FAIL(h, CMI_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
 bool cmi_model_has(int model, int which); // which containers a model owns (cmi_api.cpp)
 // evaluation-side view of an SVD++ / CAMF_*CS instance (cmi_api.cpp); the tuple / output pointers may be null for the ranking operands
 template <typename T>

@@ -10,6 +10,7 @@
 //     buckets in index order, insertion order inside a bucket).
 // Plain C++ (no GPU involved); exported through the same C ABI so the Java/ctypes hosts and the tests share it.
 #include "../../include/carskit_mi355x.h"
+#include "abi.hpp"
 
 #include <algorithm>
 #include <cerrno>
@@ -467,20 +468,6 @@ extern "C" int cmi_dao_destroy(cmi_dao_handle h) {
     return CMI_OK;
 }
 
-static int dao_read_body(const char *path, const cmi_dao *base, cmi_dao_handle *out);
-static int dao_read_impl(const char *path, const cmi_dao *base, cmi_dao_handle *out) { // exception barrier (ranged reader on the host pool)
-    try {
-        return dao_read_body(path, base, out);
-    } catch (const std::exception &e) {
-        if (out) *out = nullptr;
-        g_dao_err = std::string("cmi_dao_read: host-side failure: ") + e.what();
-        return CMI_E_HOST;
-    } catch (...) {
-        if (out) *out = nullptr;
-        g_dao_err = "cmi_dao_read: host-side failure (unknown exception)";
-        return CMI_E_HOST;
-    }
-}
 static int dao_read_body(const char *path, const cmi_dao *base, cmi_dao_handle *out) {
     if (out) *out = nullptr;
     if (!path || !out) {
@@ -946,14 +933,18 @@ static int dao_read_body(const char *path, const cmi_dao *base, cmi_dao_handle *
     return CMI_OK;
 }
 
-extern "C" int cmi_dao_read(const char *path, cmi_dao_handle *out) { return dao_read_impl(path, nullptr, out); }
+// (the ranged reader runs on the host pool)
+static int dao_read(const char *path, const cmi_dao *base, cmi_dao_handle *out) {
+    return abi_barrier(g_dao_err, "cmi_dao_read", [&] { return dao_read_body(path, base, out); }, [out] {
+        if (out) *out = nullptr;
+    });
+}
+
+extern "C" int cmi_dao_read(const char *path, cmi_dao_handle *out) { return dao_read(path, nullptr, out); }
 
 extern "C" int cmi_dao_read_shared(const char *path, cmi_dao_handle train, cmi_dao_handle *out) {
-    if (!train) {
-        g_dao_err = "cmi_dao_read_shared: null training DAO";
-        return CMI_E_INVALID;
-    }
-    return dao_read_impl(path, train, out);
+    if (!train) return abi_fail(g_dao_err, CMI_E_INVALID, "cmi_dao_read_shared: null training DAO");
+    return dao_read(path, train, out);
 }
 
 extern "C" int cmi_dao_counts(cmi_dao_handle h, int64_t out[8]) {
@@ -1029,20 +1020,22 @@ extern "C" int cmi_dao_rating_scale(cmi_dao_handle h, double *out, int32_t cap, 
 // kind: 0 user, 1 item, 2 condition (header token), 3 context key ("c0,c1,.."), 4 dimension, 5 "u,i" pair key
 extern "C" const char *cmi_dao_raw_id(cmi_dao_handle h, int kind, int32_t idx) {
     if (!h || idx < 0) return nullptr;
-    const std::vector<std::string> *v = nullptr;
-    switch (kind) {
-    case 0: v = &h->users; break;
-    case 1: v = &h->items; break;
-    case 2: v = &h->conds; break;
-    case 3: v = &h->ctxs; break;
-    case 4: v = &h->dims; break;
-    case 5: // the reference's key string of a (user, item) pair: inner ids joined by ',' (DataDAO.java:266)
-        if ((size_t)idx >= h->ui_user.size()) return nullptr;
-        h->scratch = std::to_string(h->ui_user[(size_t)idx]) + "," + std::to_string(h->ui_item[(size_t)idx]);
-        return h->scratch.c_str();
-    default: return nullptr;
-    }
-    return (size_t)idx < v->size() ? (*v)[(size_t)idx].c_str() : nullptr;
+    return abi_barrier_or<const char *>(nullptr, h->err, "cmi_dao_raw_id", [&]() -> const char * {
+        const std::vector<std::string> *v = nullptr;
+        switch (kind) {
+        case 0: v = &h->users; break;
+        case 1: v = &h->items; break;
+        case 2: v = &h->conds; break;
+        case 3: v = &h->ctxs; break;
+        case 4: v = &h->dims; break;
+        case 5: // the reference's key string of a (user, item) pair: inner ids joined by ',' (DataDAO.java:266)
+            if ((size_t)idx >= h->ui_user.size()) return nullptr;
+            h->scratch = std::to_string(h->ui_user[(size_t)idx]) + "," + std::to_string(h->ui_item[(size_t)idx]);
+            return h->scratch.c_str();
+        default: return nullptr;
+        }
+        return (size_t)idx < v->size() ? (*v)[(size_t)idx].c_str() : nullptr;
+    });
 }
 
 // ---- java.util.HashMap<String,?> iteration order ---------------------------------------------------------
@@ -1086,14 +1079,16 @@ std::vector<size_t> java_hashmap_order(const std::vector<std::string> &distinct_
 
 // positions[i] = index (into the caller's list of n keys, which must be distinct) of the i-th key visited
 extern "C" int cmi_java_hashmap_order(int64_t n, const char *const *keys, int64_t *positions, int *treeified) {
-    if (n < 0 || (n > 0 && (!keys || !positions))) return CMI_E_INVALID;
-    std::vector<std::string> ks((size_t)n);
-    for (int64_t i = 0; i < n; ++i) ks[(size_t)i] = keys[i];
-    bool tree = false;
-    const std::vector<size_t> ord = java_hashmap_order(ks, &tree);
-    for (size_t i = 0; i < ord.size(); ++i) positions[i] = (int64_t)ord[i];
-    if (treeified) *treeified = tree ? 1 : 0;
-    return CMI_OK;
+    return abi_barrier(g_dao_err, "cmi_java_hashmap_order", [&] {
+        if (n < 0 || (n > 0 && (!keys || !positions))) return CMI_E_INVALID;
+        std::vector<std::string> ks((size_t)n);
+        for (int64_t i = 0; i < n; ++i) ks[(size_t)i] = keys[i];
+        bool tree = false;
+        const std::vector<size_t> ord = java_hashmap_order(ks, &tree);
+        for (size_t i = 0; i < ord.size(); ++i) positions[i] = (int64_t)ord[i];
+        if (treeified) *treeified = tree ? 1 : 0;
+        return CMI_OK;
+    });
 }
 
 // ---- DataTransformer (src/carskit/data/processor/DataTransformer.java) -------------------------------------------
@@ -1337,9 +1332,11 @@ int transform_one(const std::vector<std::string> &lines, int fmt, bool is_test, 
 } // namespace
 
 extern "C" int cmi_validate_data_format(const char *path) {
-    std::vector<std::string> lines;
-    if (!path || !read_lines(path, lines, g_dao_err)) return CMI_E_INVALID;
-    return validate_format(lines);
+    return abi_barrier(g_dao_err, "cmi_validate_data_format", [&] {
+        std::vector<std::string> lines;
+        if (!path || !read_lines(path, lines, g_dao_err)) return CMI_E_INVALID;
+        return validate_format(lines);
+    });
 }
 
 // DataTransformer.run() (DataTransformer.java:331-396).  test_in == NULL: only the training file is converted
@@ -1347,55 +1344,59 @@ extern "C" int cmi_validate_data_format(const char *path) {
 // multimap (adding "na" to every dimension that lacks it) and both files are rewritten against it.
 extern "C" int cmi_transform(const char *train_in, const char *train_out, const char *test_in, const char *test_out,
                              int *treeified) {
-    if (treeified) *treeified = 0;
-    if (!train_in || !train_out || (test_in && !test_out)) return CMI_E_INVALID;
-    std::vector<std::string> tr, te;
-    if (!read_lines(train_in, tr, g_dao_err)) return CMI_E_INVALID;
-    const int ftr = validate_format(tr);
-    if (ftr == 0) {
-        g_dao_err = "transform: the training file is not a rating file validateDataFormat accepts (no data line, a short line, or a non-integer under a dim:cond column)";
-        return CMI_E_INVALID;
-    }
-    bool tree = false;
-    if (!test_in) {
-        if (ftr == 1) { // FileIO.copyFile
-            std::ifstream src(train_in, std::ios::binary);
-            std::ofstream dst(train_out, std::ios::binary);
-            dst << src.rdbuf();
-            return dst ? CMI_OK : CMI_E_INVALID;
+    return abi_barrier(g_dao_err, "cmi_transform", [&] {
+        if (treeified) *treeified = 0;
+        if (!train_in || !train_out || (test_in && !test_out)) return CMI_E_INVALID;
+        std::vector<std::string> tr, te;
+        if (!read_lines(train_in, tr, g_dao_err)) return CMI_E_INVALID;
+        const int ftr = validate_format(tr);
+        if (ftr == 0) {
+            g_dao_err = "transform: the training file is not a rating file validateDataFormat accepts (no data line, a short line, or a non-integer under a dim:cond column)";
+            return CMI_E_INVALID;
         }
-        const int rc = transform_one(tr, ftr, false, nullptr, train_out, &tree);
+        bool tree = false;
+        if (!test_in) {
+            if (ftr == 1) { // FileIO.copyFile
+                std::ifstream src(train_in, std::ios::binary);
+                std::ofstream dst(train_out, std::ios::binary);
+                dst << src.rdbuf();
+                return dst ? CMI_OK : CMI_E_INVALID;
+            }
+            const int rc = transform_one(tr, ftr, false, nullptr, train_out, &tree);
+            if (treeified) *treeified = tree;
+            return rc;
+        }
+        if (!read_lines(test_in, te, g_dao_err)) return CMI_E_INVALID;
+        const int fte = validate_format(te);
+        if (fte == 0) {
+            g_dao_err = "transform: the test file is not a rating file validateDataFormat accepts (no data line, a short line, or a non-integer under a dim:cond column)";
+            return CMI_E_INVALID;
+        }
+        Conditions merged;
+        merged.sorted = true;
+        if (!collect_conditions(tr, ftr, merged, g_dao_err) || !collect_conditions(te, fte, merged, g_dao_err)) return CMI_E_INVALID;
+        for (const std::string &dim : std::vector<std::string>(merged.dims))
+            if (!merged.has(dim, "na")) merged.put(dim, "na");
+        int rc = transform_one(tr, ftr, false, &merged, train_out, &tree);
+        if (rc == CMI_OK) rc = transform_one(te, fte, true, &merged, test_out, &tree);
         if (treeified) *treeified = tree;
         return rc;
-    }
-    if (!read_lines(test_in, te, g_dao_err)) return CMI_E_INVALID;
-    const int fte = validate_format(te);
-    if (fte == 0) {
-        g_dao_err = "transform: the test file is not a rating file validateDataFormat accepts (no data line, a short line, or a non-integer under a dim:cond column)";
-        return CMI_E_INVALID;
-    }
-    Conditions merged;
-    merged.sorted = true;
-    if (!collect_conditions(tr, ftr, merged, g_dao_err) || !collect_conditions(te, fte, merged, g_dao_err)) return CMI_E_INVALID;
-    for (const std::string &dim : std::vector<std::string>(merged.dims))
-        if (!merged.has(dim, "na")) merged.put(dim, "na");
-    int rc = transform_one(tr, ftr, false, &merged, train_out, &tree);
-    if (rc == CMI_OK) rc = transform_one(te, fte, true, &merged, test_out, &tree);
-    if (treeified) *treeified = tree;
-    return rc;
+    });
 }
 
 // kept for callers that know their input is compact
 extern "C" int cmi_transform_compact_to_binary(const char *in_path, const char *out_path, int *treeified) {
-    if (!in_path || !out_path) return CMI_E_INVALID;
-    std::vector<std::string> lines;
-    if (!read_lines(in_path, lines, g_dao_err)) return CMI_E_INVALID;
-    if (lines.empty()) {
-        g_dao_err = "transform: empty file";
-        return CMI_E_INVALID;
-    }
-    bool tree = false;
-    const int rc = transform_one(lines, 3, false, nullptr, out_path, &tree);
-    if (treeified) *treeified = tree ? 1 : 0;
-    return rc;
+    return abi_barrier(g_dao_err, "cmi_transform_compact_to_binary", [&] {
+        if (!in_path || !out_path) return CMI_E_INVALID;
+        std::vector<std::string> lines;
+        if (!read_lines(in_path, lines, g_dao_err)) return CMI_E_INVALID;
+        if (lines.empty()) {
+            g_dao_err = "transform: empty file";
+            return CMI_E_INVALID;
+        }
+        bool tree = false;
+        const int rc = transform_one(lines, 3, false, nullptr, out_path, &tree);
+        if (treeified) *treeified = tree ? 1 : 0;
+        return rc;
+    });
 }

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "abi.hpp"
 #include "fm_kernels.hpp"
 #include "host_pool.hpp"
 #include "rank_host.hpp"
@@ -71,37 +72,16 @@ struct cmi_fm_instance {
 
 static thread_local std::string g_fm_create_err;
 
-#define FM_FAIL(h, code, ...)                                                                           \
-    do {                                                                                                \
-        char buf_[512];                                                                                 \
-        snprintf(buf_, sizeof buf_, __VA_ARGS__);                                                       \
-        (h)->err = buf_;                                                                                \
-        return (code);                                                                                  \
-    } while (0)
-#define FM_HIP(h, expr)                                                                                 \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) FM_FAIL(h, CMI_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));    \
-    } while (0)
-
 extern "C" const char *cmi_fm_last_error(cmi_fm_handle h) { return h ? h->err.c_str() : g_fm_create_err.c_str(); }
 
 static void fm_free_ratings(cmi_fm_instance *h) {
-    void *ptrs[] = {h->d_r, h->d_u, h->d_j, h->d_ctx, h->d_src[0], h->d_src[1], h->d_src[2], h->d_E};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    h->d_r = h->d_E = nullptr;
-    h->d_u = h->d_j = h->d_ctx = h->d_src[0] = h->d_src[1] = h->d_src[2] = nullptr;
+    abi_free(h->d_r, h->d_u, h->d_j, h->d_ctx, h->d_src[0], h->d_src[1], h->d_src[2], h->d_E);
     for (FmCellsDev &c : h->cell) {
-        void *q[] = {c.err0, c.partial3, c.w0part, c.pk, c.fo, c.fcx, c.flag0, c.bat_off, c.slot_off, c.slot_coord, c.cplx, c.bat, c.poff};
-        for (void *p : q)
-            if (p) (void)hipFree(p);
+        abi_free(c.err0, c.partial3, c.w0part, c.pk, c.fo, c.fcx, c.flag0, c.bat_off, c.slot_off, c.slot_coord, c.cplx, c.bat, c.poff);
         c = FmCellsDev();
     }
     for (FmOrderDev &o : h->ord) {
-        void *q[] = {o.rec, o.piece_off};
-        for (void *p : q)
-            if (p) (void)hipFree(p);
+        abi_free(o.rec, o.piece_off);
         o = FmOrderDev();
     }
     h->have_ratings = h->initialised = false;
@@ -116,9 +96,7 @@ extern "C" int cmi_fm_destroy(cmi_fm_handle h) {
     if (h->comm) (void)ncclCommDestroy(h->comm);
     h->comm = nullptr;
     h->rank_ws.release();
-    void *ptrs[] = {h->d_w0, h->d_d0, h->d_w, h->d_V, h->d_Vt, h->d_part, h->d_scratch, h->d_tab};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
+    abi_free(h->d_w0, h->d_d0, h->d_w, h->d_V, h->d_Vt, h->d_part, h->d_scratch, h->d_tab);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return CMI_OK;
@@ -126,54 +104,48 @@ extern "C" int cmi_fm_destroy(cmi_fm_handle h) {
 
 extern "C" int cmi_fm_create(int k, int n_users, int n_items, int n_conds, int n_ctx_dims, int device,
                              unsigned flags, cmi_fm_handle *out) {
-    if (out) *out = nullptr;
-    if (!out || k <= 0 || n_users <= 0 || n_items <= 0 || n_conds < 0 || n_ctx_dims <= 0) {
-        g_fm_create_err = "cmi_fm_create: invalid argument";
-        return CMI_E_INVALID;
-    }
-    const int ndev = cmi_device_count();
-    if (ndev <= 0) {
-        g_fm_create_err = "cmi_fm_create: no HIP device visible (libcarskit_mi355x has no CPU fallback)";
-        return CMI_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        g_fm_create_err = "cmi_fm_create: device index out of range";
-        return CMI_E_INVALID;
-    }
-    cmi_fm_instance *h = new cmi_fm_instance();
-    if (const char *v = getenv("CMI_FM_SLICE")) h->slice_entries = atoll(v); // experiment knob: 0 = one slice
-    if (const char *v = getenv("CMI_FM_BATCH")) h->batch_cap = std::max(1, std::min(atoi(v), FMC_RCAP));
-    if (const char *v = getenv("CMI_FM_SLOTS")) h->slot_cap = std::max((FMC_RCAP + FMC_RUN - 1) / FMC_RUN, std::min(atoi(v), FMC_SLOTS));
-    // the reference's sweep is deterministic (FM.java:148-218): so is the default here; the relaxed (LDS-atomic) sums are an opt-in, and
-    // an explicit CMI_FM_FLAG_DETERMINISTIC / CMI_FM_DETERMINISTIC=1 wins over the environment's opt-in
-    h->atomic = ((flags & CMI_FM_FLAG_RELAXED_SUMS) || getenv("CMI_FM_RELAXED_SUMS")) && !(flags & CMI_FM_FLAG_DETERMINISTIC) && !getenv("CMI_FM_DETERMINISTIC") ? 1 : 0;
-    h->k = k;
-    h->n_users = n_users;
-    h->n_items = n_items;
-    h->n_conds = n_conds;
-    h->n_ctx_dims = n_ctx_dims;
-    h->device = device;
-    h->p = (int64_t)n_users + n_items + n_conds;
-    h->part_count = 2 * (int64_t)std::max(std::max(n_users, n_items), std::max(n_conds, 2));
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_w0, sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_d0, sizeof(double));
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_d0, 0, sizeof(double), h->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_w, (size_t)h->p * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_V, (size_t)h->p * k * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_Vt, (size_t)h->p * k * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_part, (size_t)h->part_count * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_scratch, 256 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_tab, (size_t)(h->p + 1) * sizeof(double2)); // + 1: fm_rec_eval's dummy gather
-    if (e == hipSuccess) e = hipMemsetAsync(h->d_tab, 0, (size_t)(h->p + 1) * sizeof(double2), h->stream);
-    if (e != hipSuccess) {
-        g_fm_create_err = std::string("cmi_fm_create: ") + hipGetErrorString(e);
-        cmi_fm_destroy(h);
-        return CMI_E_HIP;
-    }
-    *out = h;
-    return CMI_OK;
+    return abi_barrier(g_fm_create_err, "cmi_fm_create", [&] {
+        if (out) *out = nullptr;
+        if (!out || k <= 0 || n_users <= 0 || n_items <= 0 || n_conds < 0 || n_ctx_dims <= 0) {
+            g_fm_create_err = "cmi_fm_create: invalid argument";
+            return CMI_E_INVALID;
+        }
+        if (int rc = abi_check_device(g_fm_create_err, "cmi_fm_create", device)) return rc;
+        cmi_fm_instance *h = new cmi_fm_instance();
+        if (const char *v = getenv("CMI_FM_SLICE")) h->slice_entries = atoll(v); // experiment knob: 0 = one slice
+        if (const char *v = getenv("CMI_FM_BATCH")) h->batch_cap = std::max(1, std::min(atoi(v), FMC_RCAP));
+        if (const char *v = getenv("CMI_FM_SLOTS")) h->slot_cap = std::max((FMC_RCAP + FMC_RUN - 1) / FMC_RUN, std::min(atoi(v), FMC_SLOTS));
+        // the reference's sweep is deterministic (FM.java:148-218): so is the default here; the relaxed (LDS-atomic) sums are an opt-in, and
+        // an explicit CMI_FM_FLAG_DETERMINISTIC / CMI_FM_DETERMINISTIC=1 wins over the environment's opt-in
+        h->atomic = ((flags & CMI_FM_FLAG_RELAXED_SUMS) || getenv("CMI_FM_RELAXED_SUMS")) && !(flags & CMI_FM_FLAG_DETERMINISTIC) && !getenv("CMI_FM_DETERMINISTIC") ? 1 : 0;
+        h->k = k;
+        h->n_users = n_users;
+        h->n_items = n_items;
+        h->n_conds = n_conds;
+        h->n_ctx_dims = n_ctx_dims;
+        h->device = device;
+        h->p = (int64_t)n_users + n_items + n_conds;
+        h->part_count = 2 * (int64_t)std::max(std::max(n_users, n_items), std::max(n_conds, 2));
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_w0, sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_d0, sizeof(double));
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_d0, 0, sizeof(double), h->stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_w, (size_t)h->p * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_V, (size_t)h->p * k * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_Vt, (size_t)h->p * k * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_part, (size_t)h->part_count * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_scratch, 256 * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_tab, (size_t)(h->p + 1) * sizeof(double2)); // + 1: fm_rec_eval's dummy gather
+        if (e == hipSuccess) e = hipMemsetAsync(h->d_tab, 0, (size_t)(h->p + 1) * sizeof(double2), h->stream);
+        if (e != hipSuccess) {
+            g_fm_create_err = std::string("cmi_fm_create: ") + hipGetErrorString(e);
+            cmi_fm_destroy(h);
+            return CMI_E_HIP;
+        }
+        *out = h;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_fm_set_hparams(cmi_fm_handle h, double regLw, double regLf, int64_t global_size) {
@@ -186,11 +158,11 @@ extern "C" int cmi_fm_set_hparams(cmi_fm_handle h, double regLw, double regLf, i
 
 extern "C" int cmi_fm_set_model(cmi_fm_handle h, double w0, const double *w, const double *V) {
     if (!h || !w || !V) return CMI_E_INVALID;
-    FM_HIP(h, hipSetDevice(h->device));
-    FM_HIP(h, hipMemcpyAsync(h->d_w0, &w0, sizeof(double), hipMemcpyHostToDevice, h->stream));
-    FM_HIP(h, hipMemcpyAsync(h->d_w, w, (size_t)h->p * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    FM_HIP(h, hipMemcpyAsync(h->d_V, V, (size_t)h->p * h->k * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipMemcpyAsync(h->d_w0, &w0, sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CMI_HIP(h, hipMemcpyAsync(h->d_w, w, (size_t)h->p * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CMI_HIP(h, hipMemcpyAsync(h->d_V, V, (size_t)h->p * h->k * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     h->have_model = true;
     h->initialised = false;
     h->col[0] = h->col[1] = h->col[2] = -1;
@@ -202,35 +174,26 @@ extern "C" int cmi_fm_set_model(cmi_fm_handle h, double w0, const double *w, con
 // the sweeps keep the factors column-major (Vt); everything else reads V
 static int fm_sync_V(cmi_fm_instance *h) {
     if (h->v_valid) return CMI_OK;
-    FM_HIP(h, fm_launch_transpose(h->d_Vt, h->d_V, h->k, h->p, h->stream));
+    CMI_HIP(h, fm_launch_transpose(h->d_Vt, h->d_V, h->k, h->p, h->stream));
     h->v_valid = true;
     return CMI_OK;
 }
 static int fm_sync_Vt(cmi_fm_instance *h) {
     if (h->vt_valid) return CMI_OK;
-    FM_HIP(h, fm_launch_transpose(h->d_V, h->d_Vt, h->p, h->k, h->stream));
+    CMI_HIP(h, fm_launch_transpose(h->d_V, h->d_Vt, h->p, h->k, h->stream));
     h->vt_valid = true;
     return CMI_OK;
 }
 
 extern "C" int cmi_fm_get_model(cmi_fm_handle h, double *w0, double *w, double *V) {
     if (!h) return CMI_E_INVALID;
-    FM_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipSetDevice(h->device));
     if (int rc = fm_sync_V(h)) return rc;
-    if (w0) FM_HIP(h, hipMemcpyAsync(w0, h->d_w0, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (w) FM_HIP(h, hipMemcpyAsync(w, h->d_w, (size_t)h->p * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (V) FM_HIP(h, hipMemcpyAsync(V, h->d_V, (size_t)h->p * h->k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+    if (w0) CMI_HIP(h, hipMemcpyAsync(w0, h->d_w0, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (w) CMI_HIP(h, hipMemcpyAsync(w, h->d_w, (size_t)h->p * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (V) CMI_HIP(h, hipMemcpyAsync(V, h->d_V, (size_t)h->p * h->k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     return CMI_OK;
-}
-
-template <typename T>
-static hipError_t up(T **dst, const std::vector<T> &v, hipStream_t s) {
-    *dst = nullptr;
-    if (v.empty()) return hipSuccess;
-    hipError_t e = hipMalloc((void **)dst, v.size() * sizeof(T));
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
 }
 
 // ---- the three streams (fm_kernels.hpp FmOrder), built once per cmi_fm_set_ratings ------------------------------------
@@ -607,16 +570,16 @@ static hipError_t fm_upload_cells(const FmCellsHost &o, FmCellsDev &d, hipStream
     d.n_rec = (int64_t)o.pk.size();
     d.poff_len = (int64_t)o.poff.size();
     d.slice_len = o.slice_len;
-    hipError_t e = up(&d.pk, o.pk, s);
-    if (e == hipSuccess) e = up(&d.fo, o.fo, s);
-    if (e == hipSuccess) e = up(&d.fcx, o.fcx, s);
-    if (e == hipSuccess) e = up(&d.flag0, o.flag0, s);
-    if (e == hipSuccess) e = up(&d.bat, o.bat, s);
-    if (e == hipSuccess) e = up(&d.bat_off, o.bat_off, s);
-    if (e == hipSuccess) e = up(&d.poff, o.poff, s);
-    if (e == hipSuccess) e = up(&d.slot_off, o.slot_off, s);
-    if (e == hipSuccess) e = up(&d.slot_coord, o.slot_coord, s);
-    if (e == hipSuccess) e = up(&d.cplx, o.cplx, s);
+    hipError_t e = abi_upload(&d.pk, o.pk, s);
+    if (e == hipSuccess) e = abi_upload(&d.fo, o.fo, s);
+    if (e == hipSuccess) e = abi_upload(&d.fcx, o.fcx, s);
+    if (e == hipSuccess) e = abi_upload(&d.flag0, o.flag0, s);
+    if (e == hipSuccess) e = abi_upload(&d.bat, o.bat, s);
+    if (e == hipSuccess) e = abi_upload(&d.bat_off, o.bat_off, s);
+    if (e == hipSuccess) e = abi_upload(&d.poff, o.poff, s);
+    if (e == hipSuccess) e = abi_upload(&d.slot_off, o.slot_off, s);
+    if (e == hipSuccess) e = abi_upload(&d.slot_coord, o.slot_coord, s);
+    if (e == hipSuccess) e = abi_upload(&d.cplx, o.cplx, s);
     if (e == hipSuccess && d.n_rec > 0) e = hipMalloc((void **)&d.err0, (size_t)d.n_rec * sizeof(double));
     if (e == hipSuccess && d.n_rec > 0) e = hipMemsetAsync(d.err0, 0, (size_t)d.n_rec * sizeof(double), s);
     if (e == hipSuccess && d.n_slots > 0) e = hipMalloc((void **)&d.partial3, (size_t)d.n_slots * 3 * sizeof(double));
@@ -627,38 +590,19 @@ static hipError_t fm_upload_cells(const FmCellsHost &o, FmCellsDev &d, hipStream
 static hipError_t fm_upload_order(const FmOrderHost &o, FmOrderDev &d, hipStream_t s) {
     d.count = o.count;
     d.n_rec = (int64_t)o.rec.size();
-    hipError_t e = up(&d.rec, o.rec, s);
-    if (e == hipSuccess) e = up(&d.piece_off, o.piece_off, s);
+    hipError_t e = abi_upload(&d.rec, o.rec, s);
+    if (e == hipSuccess) e = abi_upload(&d.piece_off, o.piece_off, s);
     return e;
 }
 
-static int fm_set_ratings_impl(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r);
-
-// The exception barrier of the boundary: the cell streams allocate O(tuples) host memory, part of it on the host pool's
-// threads (host_pool.hpp hands a range body's exception to the caller) and on the two side threads below; nothing C++ may cross into a
-// C / JNI / ctypes host.
-extern "C" int cmi_fm_set_ratings(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
-                                  const double *r) {
-    if (!h) return CMI_E_INVALID;
-    try {
-        return fm_set_ratings_impl(h, n, u, j, ctx, r);
-    } catch (const std::exception &e) {
-        fm_free_ratings(h);
-        FM_FAIL(h, CMI_E_HOST, "fm_set_ratings: host-side failure: %s", e.what());
-    } catch (...) {
-        fm_free_ratings(h);
-        FM_FAIL(h, CMI_E_HOST, "fm_set_ratings: host-side failure (unknown exception)");
-    }
-}
-
 static int fm_set_ratings_impl(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r) {
-    if (n < 0 || (n > 0 && (!u || !j || !ctx || !r))) FM_FAIL(h, CMI_E_INVALID, "fm_set_ratings: null arrays");
-    if (n >= ((int64_t)1 << 31)) FM_FAIL(h, CMI_E_UNSUPPORTED, "fm_set_ratings: more than 2^31-1 tuples");
+    if (n < 0 || (n > 0 && (!u || !j || !ctx || !r))) CMI_FAIL(h, CMI_E_INVALID, "fm_set_ratings: null arrays");
+    if (n >= ((int64_t)1 << 31)) CMI_FAIL(h, CMI_E_UNSUPPORTED, "fm_set_ratings: more than 2^31-1 tuples");
     for (int64_t t = 0; t < n; ++t)
         if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || ctx[t] < 0)
-            FM_FAIL(h, CMI_E_INVALID, "fm_set_ratings: id out of range at tuple %lld", (long long)t);
-    FM_HIP(h, hipSetDevice(h->device));
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+            CMI_FAIL(h, CMI_E_INVALID, "fm_set_ratings: id out of range at tuple %lld", (long long)t);
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     fm_free_ratings(h);
     const bool times = getenv("CMI_SETUP_TIMES") != nullptr;
     auto T0 = std::chrono::steady_clock::now();
@@ -723,37 +667,37 @@ static int fm_set_ratings_impl(cmi_fm_handle h, int64_t n, const int32_t *u, con
     lap("cells + context order (three threads)");
     // the ratings as plain arrays in the caller's order (cmi_fm_init computes err0 there; every stream copies its err0 through `src`)
     hipError_t e = hipSuccess;
-    {
-        auto up_raw = [&](auto **dst, const auto *src) { // straight from the caller's arrays (they outlive the synchronize below)
-            *dst = nullptr;
-            if (n == 0) return hipSuccess;
-            hipError_t e2 = hipMalloc((void **)dst, (size_t)n * sizeof(**dst));
-            if (e2 == hipSuccess) e2 = hipMemcpyAsync(*dst, src, (size_t)n * sizeof(**dst), hipMemcpyHostToDevice, h->stream);
-            return e2;
-        };
-        e = up_raw(&h->d_u, u);
-        if (e == hipSuccess) e = up_raw(&h->d_j, j);
-        if (e == hipSuccess) e = up_raw(&h->d_ctx, ctx);
-        if (e == hipSuccess) e = up_raw(&h->d_r, r);
+    { // straight from the caller's arrays (they outlive the synchronize below)
+        e = abi_upload(&h->d_u, u, (size_t)n, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_j, j, (size_t)n, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_ctx, ctx, (size_t)n, h->stream);
+        if (e == hipSuccess) e = abi_upload(&h->d_r, r, (size_t)n, h->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     }
     lap("tuple upload");
     if (e == hipSuccess && n > 0) e = hipMalloc((void **)&h->d_E, (size_t)n * sizeof(double));
-    if (e == hipSuccess) e = up(&h->d_src[0], cu.src, h->stream);
-    if (e == hipSuccess) e = up(&h->d_src[1], ci.src, h->stream);
-    if (e == hipSuccess) e = up(&h->d_src[2], oc.src, h->stream);
+    if (e == hipSuccess) e = abi_upload(&h->d_src[0], cu.src, h->stream);
+    if (e == hipSuccess) e = abi_upload(&h->d_src[1], ci.src, h->stream);
+    if (e == hipSuccess) e = abi_upload(&h->d_src[2], oc.src, h->stream);
     if (e == hipSuccess) e = fm_upload_cells(cu, h->cell[0], h->stream);
     if (e == hipSuccess) e = fm_upload_cells(ci, h->cell[1], h->stream);
     if (e == hipSuccess) e = fm_upload_order(oc, h->ord[2], h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         fm_free_ratings(h);
-        FM_FAIL(h, CMI_E_HIP, "fm_set_ratings: upload failed: %s", hipGetErrorString(e));
+        CMI_FAIL(h, CMI_E_HIP, "fm_set_ratings: upload failed: %s", hipGetErrorString(e));
     }
     lap("stream upload");
     h->n = n;
     h->have_ratings = true;
     return CMI_OK;
+}
+
+// the cell streams allocate O(tuples) host memory, part of it on the host pool's threads and on the two side threads above
+extern "C" int cmi_fm_set_ratings(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
+                                  const double *r) {
+    if (!h) return CMI_E_INVALID;
+    return abi_barrier(h->err, "fm_set_ratings", [&] { return fm_set_ratings_impl(h, n, u, j, ctx, r); }, [h] { fm_free_ratings(h); });
 }
 
 static FmArgs fm_args(cmi_fm_instance *h) {
@@ -797,10 +741,10 @@ static FmArgs fm_args(cmi_fm_instance *h) {
 }
 
 static int fm_ready(cmi_fm_instance *h, bool need_init) {
-    if (!h->have_ratings) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_ratings first");
-    if (!h->have_model) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
-    if (need_init && !h->initialised) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_init first");
-    FM_HIP(h, hipSetDevice(h->device));
+    if (!h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_ratings first");
+    if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
+    if (need_init && !h->initialised) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_init first");
+    CMI_HIP(h, hipSetDevice(h->device));
     return CMI_OK;
 }
 
@@ -809,8 +753,8 @@ extern "C" int cmi_fm_init(cmi_fm_handle h) {
     if (int rc = fm_ready(h, false)) return rc;
     if (int rc = fm_sync_V(h)) return rc;
     h->col[0] = h->col[1] = h->col[2] = -1;
-    FM_HIP(h, fm_launch_init(fm_args(h), h->stream));
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, fm_launch_init(fm_args(h), h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     h->initialised = true;
     return CMI_OK;
 }
@@ -849,7 +793,7 @@ static int fm_before_phase(cmi_fm_instance *h, int field, int f) {
     if (f < 0 || field == 2) return CMI_OK;
     for (int g = 0; g < 3; ++g) {
         if (g == field || h->col[g] == f) continue;
-        FM_HIP(h, fm_launch_col_load(fm_args(h), g, f, h->stream));
+        CMI_HIP(h, fm_launch_col_load(fm_args(h), g, f, h->stream));
         h->col[g] = f;
     }
     return CMI_OK;
@@ -864,13 +808,13 @@ extern "C" int cmi_fm_phase_reduce(cmi_fm_handle h, int phase) {
     if (!h) return CMI_E_INVALID;
     if (int rc = fm_ready(h, true)) return rc;
     int field, f;
-    if (!phase_decode(h, phase, &field, &f)) FM_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
+    if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     if (int rc = fm_before_phase(h, field, f)) return rc;
     const FmArgs a = fm_args(h);
     if (phase == 0) {
-        FM_HIP(h, fm_launch_w0_reduce(a, h->d_scratch, h->stream));
+        CMI_HIP(h, fm_launch_w0_reduce(a, h->d_scratch, h->stream));
     } else {
-        FM_HIP(h, fm_launch_phase(a, field, f, 0, h->stream));
+        CMI_HIP(h, fm_launch_phase(a, field, f, 0, h->stream));
     }
     h->last_phase = phase;
     return CMI_OK;
@@ -879,7 +823,7 @@ extern "C" int cmi_fm_phase_reduce(cmi_fm_handle h, int phase) {
 extern "C" int cmi_fm_phase_buffer(cmi_fm_handle h, int phase, void **dev_ptr, int64_t *count) {
     if (!h || !dev_ptr || !count) return CMI_E_INVALID;
     int field, f;
-    if (!phase_decode(h, phase, &field, &f)) FM_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
+    if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     *dev_ptr = h->d_part;
     *count = phase == 0 ? 2 : 2 * (int64_t)(field == 0 ? h->n_users : field == 1 ? h->n_items : h->n_conds);
     return CMI_OK;
@@ -889,13 +833,13 @@ extern "C" int cmi_fm_phase_apply(cmi_fm_handle h, int phase) {
     if (!h) return CMI_E_INVALID;
     if (int rc = fm_ready(h, true)) return rc;
     int field, f;
-    if (!phase_decode(h, phase, &field, &f)) FM_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
-    if (h->last_phase != phase) FM_FAIL(h, CMI_E_INVALID, "fm: phase_apply(%d) without the matching phase_reduce", phase);
+    if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
+    if (h->last_phase != phase) CMI_FAIL(h, CMI_E_INVALID, "fm: phase_apply(%d) without the matching phase_reduce", phase);
     FmArgs a = fm_args(h);
-    if (phase == 0) FM_HIP(h, fm_launch_w0_apply(a, h->stream));
+    if (phase == 0) CMI_HIP(h, fm_launch_w0_apply(a, h->stream));
     else {
         a.xcol = fm_xcol(h, field, f);
-        FM_HIP(h, fm_launch_apply(a, field, f, h->stream));
+        CMI_HIP(h, fm_launch_apply(a, field, f, h->stream));
         fm_after_update(h, field, f);
     }
     h->last_phase = -1;
@@ -908,15 +852,15 @@ extern "C" int cmi_fm_phase_run(cmi_fm_handle h, int phase) {
     if (!h) return CMI_E_INVALID;
     if (int rc = fm_ready(h, true)) return rc;
     int field, f;
-    if (!phase_decode(h, phase, &field, &f)) FM_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
+    if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     if (int rc = fm_before_phase(h, field, f)) return rc;
     FmArgs a = fm_args(h);
     if (phase == 0) {
-        FM_HIP(h, fm_launch_w0_reduce(a, h->d_scratch, h->stream));
-        FM_HIP(h, fm_launch_w0_apply(a, h->stream));
+        CMI_HIP(h, fm_launch_w0_reduce(a, h->d_scratch, h->stream));
+        CMI_HIP(h, fm_launch_w0_apply(a, h->stream));
     } else {
         a.xcol = fm_xcol(h, field, f);
-        FM_HIP(h, fm_launch_phase(a, field, f, 2, h->stream));
+        CMI_HIP(h, fm_launch_phase(a, field, f, 2, h->stream));
         fm_after_update(h, field, f);
     }
     h->last_phase = -1;
@@ -938,7 +882,7 @@ extern "C" int cmi_fm_sweep(cmi_fm_handle h) {
 // the user field alone, [9] of the item field alone, [10] slice entries, [11] p.
 extern "C" int cmi_fm_layout(cmi_fm_handle h, int64_t out[12]) {
     if (!h || !out) return CMI_E_INVALID;
-    if (!h->have_ratings) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_ratings first");
+    if (!h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_ratings first");
     int64_t factor = 0, red[3] = {0, 0, 0};
     for (int f = 0; f < 2; ++f) {
         const FmCellsDev &c = h->cell[f];
@@ -978,12 +922,12 @@ extern "C" int cmi_fm_time_reduce(cmi_fm_handle h, int phase, int reps, double *
     if (!h || !avg_ms || reps < 1) return CMI_E_INVALID;
     if (int rc = fm_ready(h, true)) return rc;
     int field, f;
-    if (!phase_decode(h, phase, &field, &f) || phase == 0) FM_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
+    if (!phase_decode(h, phase, &field, &f) || phase == 0) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     if (int rc = fm_before_phase(h, field, f)) return rc;
     const FmArgs a = fm_args(h);
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    FM_HIP(h, hipEventCreate(&e0));
-    FM_HIP(h, hipEventCreate(&e1));
+    CMI_HIP(h, hipEventCreate(&e0));
+    CMI_HIP(h, hipEventCreate(&e1));
     hipError_t e = fm_launch_reduce_only(a, field, f, h->stream); // warm
     if (e == hipSuccess) e = hipEventRecord(e0, h->stream);
     for (int i = 0; i < reps && e == hipSuccess; ++i) e = fm_launch_reduce_only(a, field, f, h->stream);
@@ -993,7 +937,7 @@ extern "C" int cmi_fm_time_reduce(cmi_fm_handle h, int phase, int reps, double *
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    FM_HIP(h, e);
+    CMI_HIP(h, e);
     *avg_ms = (double)ms / reps;
     return CMI_OK;
 }
@@ -1007,20 +951,20 @@ extern "C" int cmi_fm_time_reduce(cmi_fm_handle h, int phase, int reps, double *
 extern "C" int cmi_fm_comm_init(cmi_fm_handle h, const void *id, int rank, int world) {
     if (!h || !id || world < 1 || rank < 0 || rank >= world) return CMI_E_INVALID;
     static_assert(sizeof(ncclUniqueId) == CMI_COMM_ID_BYTES, "CMI_COMM_ID_BYTES must be sizeof(ncclUniqueId)");
-    FM_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipSetDevice(h->device));
     if (h->comm) (void)ncclCommDestroy(h->comm);
     h->comm = nullptr;
     ncclUniqueId u;
     memcpy(&u, id, sizeof u);
     const ncclResult_t r = ncclCommInitRank(&h->comm, world, u, rank);
-    if (r != ncclSuccess) FM_FAIL(h, CMI_E_HIP, "ncclCommInitRank failed: %s", ncclGetErrorString(r));
+    if (r != ncclSuccess) CMI_FAIL(h, CMI_E_HIP, "ncclCommInitRank failed: %s", ncclGetErrorString(r));
     h->comm_world = world;
     return CMI_OK;
 }
 
 extern "C" int cmi_fm_comm_sweep(cmi_fm_handle h) {
     if (!h) return CMI_E_INVALID;
-    if (!h->comm) FM_FAIL(h, CMI_E_INVALID, "fm_comm_sweep: call cmi_fm_comm_init first");
+    if (!h->comm) CMI_FAIL(h, CMI_E_INVALID, "fm_comm_sweep: call cmi_fm_comm_init first");
     const int np = cmi_fm_num_phases(h);
     for (int ph = 0; ph < np; ++ph) {
         int field, f;
@@ -1034,7 +978,7 @@ extern "C" int cmi_fm_comm_sweep(cmi_fm_handle h) {
         int64_t cnt = 0;
         if (int rc = cmi_fm_phase_buffer(h, ph, &buf, &cnt)) return rc;
         const ncclResult_t r = ncclAllReduce(buf, buf, (size_t)cnt, ncclDouble, ncclSum, h->comm, h->stream);
-        if (r != ncclSuccess) FM_FAIL(h, CMI_E_HIP, "ncclAllReduce (phase %d) failed: %s", ph, ncclGetErrorString(r));
+        if (r != ncclSuccess) CMI_FAIL(h, CMI_E_HIP, "ncclAllReduce (phase %d) failed: %s", ph, ncclGetErrorString(r));
         if (int rc = cmi_fm_phase_apply(h, ph)) return rc;
     }
     return CMI_OK;
@@ -1045,7 +989,7 @@ extern "C" int cmi_fm_train(cmi_fm_handle h, int num_iters) {
     if (int rc = cmi_fm_init(h)) return rc;
     for (int it = 0; it < num_iters; ++it)
         if (int rc = cmi_fm_sweep(h)) return rc;
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     return CMI_OK;
 }
 
@@ -1057,21 +1001,21 @@ extern "C" int cmi_fm_stream(cmi_fm_handle h, void **stream) {
 
 extern "C" int cmi_fm_synchronize(cmi_fm_handle h) {
     if (!h) return CMI_E_INVALID;
-    FM_HIP(h, hipSetDevice(h->device));
-    FM_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     return CMI_OK;
 }
 
 extern "C" int cmi_fm_predict_batch(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                     int bound, double lo, double hi, double *out) {
     if (!h) return CMI_E_INVALID;
-    if (!h->have_model) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
-    if (n < 0 || (n > 0 && (!u || !j || !ctx || !out))) FM_FAIL(h, CMI_E_INVALID, "fm_predict: null arrays");
+    if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
+    if (n < 0 || (n > 0 && (!u || !j || !ctx || !out))) CMI_FAIL(h, CMI_E_INVALID, "fm_predict: null arrays");
     for (int64_t t = 0; t < n; ++t)
         if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || ctx[t] < 0)
-            FM_FAIL(h, CMI_E_INVALID, "fm_predict: id out of range at tuple %lld", (long long)t);
+            CMI_FAIL(h, CMI_E_INVALID, "fm_predict: id out of range at tuple %lld", (long long)t);
     if (n == 0) return CMI_OK;
-    FM_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipSetDevice(h->device));
     if (int rc = fm_sync_V(h)) return rc;
     int32_t *du = nullptr, *dj = nullptr, *dc = nullptr;
     double *dout = nullptr;
@@ -1086,71 +1030,43 @@ extern "C" int cmi_fm_predict_batch(cmi_fm_handle h, int64_t n, const int32_t *u
     if (e == hipSuccess) e = fm_launch_predict(a, n, du, dj, dc, bound, lo, hi, dout, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    void *ptrs[] = {du, dj, dc, dout};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    FM_HIP(h, e);
+    abi_free(du, dj, dc, dout);
+    CMI_HIP(h, e);
     return CMI_OK;
 }
 
-// Recommender.evalRankings for the FM recommender (Recommender.java:668-964 with FM.predict, FM.java:93-113): same
-// bookkeeping, contraction and top-N selection as cmi_eval_rankings; fp64 like the rest of the FM path.
+// Recommender.evalRankings for the FM recommender (Recommender.java:668-964 with FM.predict, FM.java:93-113): the driver of
+// cmi_eval_rankings (rank_evaluate) around FM's scorer; fp64 like the rest of the FM path.
 extern "C" int cmi_fm_eval_rankings(cmi_fm_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
                                     const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
                                     const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy,
                                     double out[CMI_RANK_MEASURES], int64_t *n_queries, int32_t *q_user, int32_t *q_ctx,
                                     int32_t *q_count, int32_t *top_items, double *top_scores) {
     if (!h) return CMI_E_INVALID;
-    if (!out) FM_FAIL(h, CMI_E_INVALID, "fm_eval_rankings: null output");
-    if (!h->have_model) FM_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
-    if (n_train < 0 || n_test < 0 || (n_train > 0 && (!tu || !tj || !tctx)) || (n_test > 0 && (!su || !sj || !sctx || !sr)))
-        FM_FAIL(h, CMI_E_INVALID, "fm_eval_rankings: null tuple arrays");
-    if (num_recs < 1) FM_FAIL(h, CMI_E_INVALID, "fm_eval_rankings: -topN must be >= 1");
-    if (strategy != CMI_RANK_UCU && strategy != CMI_RANK_UC) FM_FAIL(h, CMI_E_INVALID, "fm_eval_rankings: bad strategy");
-    for (int pass = 0; pass < 2; ++pass) {
-        const int64_t n = pass ? n_test : n_train;
-        const int32_t *u = pass ? su : tu, *j = pass ? sj : tj, *c = pass ? sctx : tctx;
-        for (int64_t t = 0; t < n; ++t)
-            if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || c[t] < 0)
-                FM_FAIL(h, CMI_E_INVALID, "fm_eval_rankings: id out of range at %s tuple %lld", pass ? "test" : "train", (long long)t);
-    }
-    FM_HIP(h, hipSetDevice(h->device));
-    if (int rc = fm_sync_V(h)) return rc;
-    if (n_queries) *n_queries = 0;
-    RankPlan plan;
-    rank_build_plan(h->n_users, h->n_items, RankTuples{n_train, tu, tj, tctx, tr}, RankTuples{n_test, su, sj, sctx, sr}, bin_thold,
-                    num_ignore, plan);
-    RankWorkspace &ws = h->rank_ws;
-    const int64_t nq = (int64_t)plan.qu.size();
-    std::vector<double> vals((size_t)nq * 18);
-    std::vector<int32_t> no_lists;
-    const int32_t *top_count = nullptr;
-    if (nq > 0 && !plan.cand.empty()) {
-        RankOperands<double> ops;
-        ops.k_logical = h->k + 1;
-        const RankFmArgs base{h->d_w0, h->d_w, h->d_V, h->k, 0, h->n_users, h->n_items, h->n_conds, 1.0 / (double)h->n_ctx_dims};
-        ops.build_items = [base](double *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
-            RankFmArgs a = base;
-            a.kp = kp;
-            return rank_launch_fm_items(a, dcand, nc, dB, s);
+    return abi_barrier(h->err, "fm_eval_rankings", [&] {
+        auto ready = [h]() -> int {
+            if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
+            CMI_HIP(h, hipSetDevice(h->device));
+            return fm_sync_V(h);
         };
-        ops.build_queries = [base](double *dA, double *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
-            RankFmArgs a = base;
-            a.kp = kp;
-            return rank_launch_fm_queries(a, dqu, dqc, n, dA, drc, s);
+        auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
+            RankOperands<double> ops;
+            ops.k_logical = h->k + 1;
+            const RankFmArgs base{h->d_w0, h->d_w, h->d_V, h->k, 0, h->n_users, h->n_items, h->n_conds, 1.0 / (double)h->n_ctx_dims};
+            ops.build_items = [base](double *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
+                RankFmArgs a = base;
+                a.kp = kp;
+                return rank_launch_fm_items(a, dcand, nc, dB, s);
+            };
+            ops.build_queries = [base](double *dA, double *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
+                RankFmArgs a = base;
+                a.kp = kp;
+                return rank_launch_fm_queries(a, dqu, dqc, n, dA, drc, s);
+            };
+            return rank_run_device<double>(h->stream, h->rank_ws, plan, ops, bin_thold, num_recs, on_batch, nullptr, nullptr);
         };
-        auto on_batch = [&](int64_t q0, int64_t q1) {
-            rank_measures_range(plan, num_recs, (const int32_t *)ws.h_top.p, (const double *)ws.h_score.p, (const int32_t *)ws.h_count.p, q0, q1,
-                                vals.data(), q_user, q_ctx, q_count, top_items, top_scores);
-        };
-        FM_HIP(h, rank_run_device<double>(h->stream, ws, plan, ops, bin_thold, num_recs, on_batch, nullptr, nullptr));
-        top_count = (const int32_t *)ws.h_count.p;
-    } else {
-        no_lists.assign((size_t)nq, 0);
-        top_count = no_lists.data();
-        rank_measures_range(plan, num_recs, nullptr, nullptr, top_count, 0, nq, vals.data(), q_user, q_ctx, q_count, top_items, top_scores);
-    }
-    rank_average(plan, strategy, top_count, vals.data(), nullptr, RankFolded(), out);
-    if (n_queries) *n_queries = (int64_t)plan.qu.size();
-    return CMI_OK;
+        const RankEvalIO io{{n_train, tu, tj, tctx, tr}, {n_test, su, sj, sctx, sr}, bin_thold, num_recs, num_ignore, strategy, out, n_queries,
+                            q_user, q_ctx, q_count, top_items, top_scores};
+        return rank_evaluate(h->err, "fm_eval_rankings", h->rank_ws, h->n_users, h->n_items, INT64_MAX, io, ready, score);
+    });
 }

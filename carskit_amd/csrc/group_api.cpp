@@ -29,6 +29,7 @@
 #include <thread>
 #include <vector>
 
+#include "abi.hpp"
 #include "cmi_instance.hpp"
 
 struct cmi_group {
@@ -57,28 +58,16 @@ struct cmi_group {
 
 static thread_local std::string g_group_create_err;
 
-#define GRP_FAIL(g, code, ...)                    \
-    do {                                          \
-        char buf_[512];                           \
-        snprintf(buf_, sizeof buf_, __VA_ARGS__); \
-        (g)->err = buf_;                          \
-        return (code);                            \
-    } while (0)
-#define GRP_HIP(g, expr)                                                                              \
-    do {                                                                                              \
-        hipError_t e_ = (expr);                                                                       \
-        if (e_ != hipSuccess) GRP_FAIL(g, CMI_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 #define GRP_NCCL(g, expr)                                                                                 \
     do {                                                                                                  \
         ncclResult_t r_ = (expr);                                                                         \
-        if (r_ != ncclSuccess) GRP_FAIL(g, CMI_E_HIP, "%s failed: %s", #expr, ncclGetErrorString(r_));   \
+        if (r_ != ncclSuccess) CMI_FAIL(g, CMI_E_HIP, "%s failed: %s", #expr, ncclGetErrorString(r_));   \
     } while (0)
 // a member call failed: carry its message
 #define GRP_MEMBER(g, i, expr)                                                                                   \
     do {                                                                                                         \
         int rc_ = (expr);                                                                                        \
-        if (rc_ != CMI_OK) GRP_FAIL(g, rc_, "shard %d (device %d): %s", (int)(i), (g)->dev[(size_t)(i)], cmi_last_error((g)->inst[(size_t)(i)])); \
+        if (rc_ != CMI_OK) CMI_FAIL(g, rc_, "shard %d (device %d): %s", (int)(i), (g)->dev[(size_t)(i)], cmi_last_error((g)->inst[(size_t)(i)])); \
     } while (0)
 
 // THE exchange, one implementation for both hosts: the single-process group (cmi_group_*: ncclCommInitAll, one
@@ -163,37 +152,32 @@ extern "C" int cmi_group_destroy(cmi_group_handle g) {
 
 extern "C" int cmi_group_create(int model, int k, int n_users, int n_items, int n_conds, int n_shards, const int *devices, unsigned flags,
                                 cmi_group_handle *out) {
-    if (out) *out = nullptr;
-    if (!out || n_shards < 1 || n_shards > 64 || k <= 0 || n_users < n_shards || n_items <= 0 || n_conds < 0) {
-        g_group_create_err = "cmi_group_create: invalid argument (1..64 shards, at least one user per shard)";
-        return CMI_E_INVALID;
-    }
-    if (model == CMI_MODEL_CAMF_C || (model >= CMI_MODEL_SVDPP && model <= CMI_MODEL_CAMF_MCS)) {
-        if (n_shards > 1) {
-            g_group_create_err = "cmi_group_create: CAMF_C, SVD++ and CAMF_ICS/LCS/MCS are single serial chains (every tuple updates "
-                                 "parameters every other tuple reads) and are not sharded; use one shard";
-            return CMI_E_UNSUPPORTED;
-        }
-    }
-    const int ndev = cmi_device_count();
-    if (ndev <= 0) {
-        g_group_create_err = "cmi_group_create: no HIP device visible (libcarskit_mi355x has no CPU fallback)";
-        return CMI_E_NO_DEVICE;
-    }
-    cmi_group *g = new cmi_group();
-    g->model = model, g->k = k, g->n_users = n_users, g->n_items = n_items, g->n_conds = n_conds, g->flags = flags;
-    g->f64 = flags & CMI_FLAG_STATE_F64;
-    for (int s = 0; s < n_shards; ++s) {
-        const int d = devices ? devices[s] : s % ndev; // default: round robin over the visible devices
-        if (d < 0 || d >= ndev) {
-            g_group_create_err = "cmi_group_create: device index out of range";
-            delete g;
+    return abi_barrier(g_group_create_err, "cmi_group_create", [&] {
+        if (out) *out = nullptr;
+        if (!out || n_shards < 1 || n_shards > 64 || k <= 0 || n_users < n_shards || n_items <= 0 || n_conds < 0) {
+            g_group_create_err = "cmi_group_create: invalid argument (1..64 shards, at least one user per shard)";
             return CMI_E_INVALID;
         }
-        g->dev.push_back(d);
-    }
-    *out = g;
-    return CMI_OK;
+        if (model == CMI_MODEL_CAMF_C || (model >= CMI_MODEL_SVDPP && model <= CMI_MODEL_CAMF_MCS)) {
+            if (n_shards > 1) {
+                g_group_create_err = "cmi_group_create: CAMF_C, SVD++ and CAMF_ICS/LCS/MCS are single serial chains (every tuple updates "
+                                     "parameters every other tuple reads) and are not sharded; use one shard";
+                return CMI_E_UNSUPPORTED;
+            }
+        }
+        std::vector<int> dev;
+        const int ndev = std::max(cmi_device_count(), 1);
+        for (int s = 0; s < n_shards; ++s) {
+            dev.push_back(devices ? devices[s] : s % ndev); // default: round robin over the visible devices
+            if (int rc = abi_check_device(g_group_create_err, "cmi_group_create", dev.back())) return rc;
+        }
+        cmi_group *g = new cmi_group();
+        g->model = model, g->k = k, g->n_users = n_users, g->n_items = n_items, g->n_conds = n_conds, g->flags = flags;
+        g->f64 = flags & CMI_FLAG_STATE_F64;
+        g->dev = std::move(dev);
+        *out = g;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_group_size(cmi_group_handle g) { return g ? (int)g->dev.size() : 0; }
@@ -231,114 +215,116 @@ static int shard_of(const std::vector<int32_t> &cut, int32_t user) {
 extern "C" int cmi_group_set_ratings(cmi_group_handle g, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r,
                                      int32_t n_ctx, const int32_t *ctx_ptr, const int32_t *ctx_conds) {
     if (!g) return CMI_E_INVALID;
-    if (n < 0 || (n > 0 && (!u || !j || !r))) GRP_FAIL(g, CMI_E_INVALID, "group_set_ratings: null tuple arrays");
-    const int W = (int)g->dev.size();
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= g->n_users) GRP_FAIL(g, CMI_E_INVALID, "group_set_ratings: user id %d out of range at tuple %lld", u[t], (long long)t);
-    group_free_instances(g);
-    cut_users(n, u, g->n_users, W, g->cut);
-    // tuples of every shard, CRS order kept, user ids re-based to the shard
-    std::vector<std::vector<int32_t>> su((size_t)W), sj((size_t)W), sc((size_t)W);
-    std::vector<std::vector<double>> sr((size_t)W);
-    g->shard_n.assign((size_t)W, 0);
-    for (int64_t t = 0; t < n; ++t) g->shard_n[(size_t)shard_of(g->cut, u[t])]++;
-    for (int s = 0; s < W; ++s) {
-        su[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
-        sj[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
-        if (ctx) sc[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
-        sr[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
-    }
-    for (int64_t t = 0; t < n; ++t) {
-        const int s = shard_of(g->cut, u[t]);
-        su[(size_t)s].push_back(u[t] - g->cut[(size_t)s]);
-        sj[(size_t)s].push_back(j[t]);
-        if (ctx) sc[(size_t)s].push_back(ctx[t]);
-        sr[(size_t)s].push_back(r[t]);
-    }
-    g->inst.assign((size_t)W, nullptr);
-    for (int s = 0; s < W; ++s) {
-        const int rc = cmi_create(g->model, g->k, g->cut[(size_t)s + 1] - g->cut[(size_t)s], g->n_items, g->n_conds, g->dev[(size_t)s], g->flags,
-                                  &g->inst[(size_t)s]);
-        if (rc != CMI_OK) GRP_FAIL(g, rc, "shard %d (device %d): %s", s, g->dev[(size_t)s], cmi_last_error(nullptr));
-        if (g->have_hp) GRP_MEMBER(g, s, cmi_set_hparams(g->inst[(size_t)s], g->hp[0], g->hp[1], g->hp[2], g->hp[3], g->hp[4]));
-    }
-    // schedule construction is host integer work (seconds for tens of millions of tuples): one thread per shard
-    std::vector<int> rcs((size_t)W, CMI_OK);
-    {
-        std::vector<std::thread> th;
+    return abi_barrier(g->err, "group_set_ratings", [&] {
+        if (n < 0 || (n > 0 && (!u || !j || !r))) CMI_FAIL(g, CMI_E_INVALID, "group_set_ratings: null tuple arrays");
+        const int W = (int)g->dev.size();
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= g->n_users) CMI_FAIL(g, CMI_E_INVALID, "group_set_ratings: user id %d out of range at tuple %lld", u[t], (long long)t);
+        group_free_instances(g);
+        cut_users(n, u, g->n_users, W, g->cut);
+        // tuples of every shard, CRS order kept, user ids re-based to the shard
+        std::vector<std::vector<int32_t>> su((size_t)W), sj((size_t)W), sc((size_t)W);
+        std::vector<std::vector<double>> sr((size_t)W);
+        g->shard_n.assign((size_t)W, 0);
+        for (int64_t t = 0; t < n; ++t) g->shard_n[(size_t)shard_of(g->cut, u[t])]++;
+        for (int s = 0; s < W; ++s) {
+            su[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
+            sj[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
+            if (ctx) sc[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
+            sr[(size_t)s].reserve((size_t)g->shard_n[(size_t)s]);
+        }
+        for (int64_t t = 0; t < n; ++t) {
+            const int s = shard_of(g->cut, u[t]);
+            su[(size_t)s].push_back(u[t] - g->cut[(size_t)s]);
+            sj[(size_t)s].push_back(j[t]);
+            if (ctx) sc[(size_t)s].push_back(ctx[t]);
+            sr[(size_t)s].push_back(r[t]);
+        }
+        g->inst.assign((size_t)W, nullptr);
+        for (int s = 0; s < W; ++s) {
+            const int rc = cmi_create(g->model, g->k, g->cut[(size_t)s + 1] - g->cut[(size_t)s], g->n_items, g->n_conds, g->dev[(size_t)s], g->flags,
+                                      &g->inst[(size_t)s]);
+            if (rc != CMI_OK) CMI_FAIL(g, rc, "shard %d (device %d): %s", s, g->dev[(size_t)s], cmi_last_error(nullptr));
+            if (g->have_hp) GRP_MEMBER(g, s, cmi_set_hparams(g->inst[(size_t)s], g->hp[0], g->hp[1], g->hp[2], g->hp[3], g->hp[4]));
+        }
+        // schedule construction is host integer work (seconds for tens of millions of tuples): one thread per shard
+        std::vector<int> rcs((size_t)W, CMI_OK);
+        {
+            std::vector<std::thread> th;
+            for (int s = 0; s < W; ++s)
+                th.emplace_back([&, s] {
+                    rcs[(size_t)s] = cmi_set_ratings(g->inst[(size_t)s], g->shard_n[(size_t)s], su[(size_t)s].data(), sj[(size_t)s].data(),
+                                                     ctx ? sc[(size_t)s].data() : nullptr, sr[(size_t)s].data(), n_ctx, ctx_ptr, ctx_conds);
+                });
+            for (std::thread &t : th) t.join();
+        }
         for (int s = 0; s < W; ++s)
-            th.emplace_back([&, s] {
-                rcs[(size_t)s] = cmi_set_ratings(g->inst[(size_t)s], g->shard_n[(size_t)s], su[(size_t)s].data(), sj[(size_t)s].data(),
-                                                 ctx ? sc[(size_t)s].data() : nullptr, sr[(size_t)s].data(), n_ctx, ctx_ptr, ctx_conds);
-            });
-        for (std::thread &t : th) t.join();
-    }
-    for (int s = 0; s < W; ++s)
-        if (rcs[(size_t)s] != CMI_OK) GRP_FAIL(g, rcs[(size_t)s], "shard %d (device %d): %s", s, g->dev[(size_t)s], cmi_last_error(g->inst[(size_t)s]));
-    if (W == 1) return CMI_OK;
+            if (rcs[(size_t)s] != CMI_OK) CMI_FAIL(g, rcs[(size_t)s], "shard %d (device %d): %s", s, g->dev[(size_t)s], cmi_last_error(g->inst[(size_t)s]));
+        if (W == 1) return CMI_OK;
 
-    // exchange plumbing
-    g->bucket.assign((size_t)W, nullptr);
-    for (int s = 0; s < W; ++s) {
-        int64_t cnt = 0;
-        GRP_MEMBER(g, s, cmi_exchange_setup(g->inst[(size_t)s], W, &g->bucket[(size_t)s], &cnt));
-        if (s == 0) g->x_count = cnt;
-        else if (cnt != g->x_count) GRP_FAIL(g, CMI_E_INVALID, "group_set_ratings: bucket sizes differ between shards");
-    }
-    bool distinct = true;
-    for (int a = 0; a < W; ++a)
-        for (int b = a + 1; b < W; ++b) distinct = distinct && g->dev[(size_t)a] != g->dev[(size_t)b];
-    g->ev.assign((size_t)W + 1, nullptr);
-    for (int s = 0; s <= W; ++s) { // ev[W] belongs to shard 0's device
-        GRP_HIP(g, hipSetDevice(g->dev[s == W ? 0 : (size_t)s]));
-        GRP_HIP(g, hipEventCreateWithFlags(&g->ev[(size_t)s], hipEventDisableTiming));
-    }
-    g->tx.assign((size_t)W * 2, nullptr);
-    for (int s = 0; s < 2 * W; ++s) {
-        GRP_HIP(g, hipSetDevice(g->dev[(size_t)s / 2]));
-        GRP_HIP(g, hipEventCreate(&g->tx[(size_t)s]));
-    }
-    // The in-process exchange (peer copies) is ALWAYS set up: it is what shards that share a device use, and what a group falls back
-    // to when RCCL cannot be initialised or does not pass the pre-flight on this node (the first N > 1 RCCL call
-    // ever executed must not be the timed one, and a failure must still leave a working trainer).
-    GRP_HIP(g, hipSetDevice(g->dev[0]));
-    GRP_HIP(g, hipMalloc(&g->d_stage, (size_t)g->x_count * (g->f64 ? 8 : 4) + 8));
-    for (int s = 1; s < W; ++s)
-        if (g->dev[(size_t)s] != g->dev[0]) {
-            int can = 0;
-            hipDeviceCanAccessPeer(&can, g->dev[0], g->dev[(size_t)s]);
-            if (can) {
-                hipSetDevice(g->dev[0]);
-                hipDeviceEnablePeerAccess(g->dev[(size_t)s], 0); // already enabled is fine
-                hipSetDevice(g->dev[(size_t)s]);
-                hipDeviceEnablePeerAccess(g->dev[0], 0);
+        // exchange plumbing
+        g->bucket.assign((size_t)W, nullptr);
+        for (int s = 0; s < W; ++s) {
+            int64_t cnt = 0;
+            GRP_MEMBER(g, s, cmi_exchange_setup(g->inst[(size_t)s], W, &g->bucket[(size_t)s], &cnt));
+            if (s == 0) g->x_count = cnt;
+            else if (cnt != g->x_count) CMI_FAIL(g, CMI_E_INVALID, "group_set_ratings: bucket sizes differ between shards");
+        }
+        bool distinct = true;
+        for (int a = 0; a < W; ++a)
+            for (int b = a + 1; b < W; ++b) distinct = distinct && g->dev[(size_t)a] != g->dev[(size_t)b];
+        g->ev.assign((size_t)W + 1, nullptr);
+        for (int s = 0; s <= W; ++s) { // ev[W] belongs to shard 0's device
+            CMI_HIP(g, hipSetDevice(g->dev[s == W ? 0 : (size_t)s]));
+            CMI_HIP(g, hipEventCreateWithFlags(&g->ev[(size_t)s], hipEventDisableTiming));
+        }
+        g->tx.assign((size_t)W * 2, nullptr);
+        for (int s = 0; s < 2 * W; ++s) {
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s / 2]));
+            CMI_HIP(g, hipEventCreate(&g->tx[(size_t)s]));
+        }
+        // The in-process exchange (peer copies) is ALWAYS set up: it is what shards that share a device use, and what a group falls back
+        // to when RCCL cannot be initialised or does not pass the pre-flight on this node (the first N > 1 RCCL call
+        // ever executed must not be the timed one, and a failure must still leave a working trainer).
+        CMI_HIP(g, hipSetDevice(g->dev[0]));
+        CMI_HIP(g, hipMalloc(&g->d_stage, (size_t)g->x_count * (g->f64 ? 8 : 4) + 8));
+        for (int s = 1; s < W; ++s)
+            if (g->dev[(size_t)s] != g->dev[0]) {
+                int can = 0;
+                hipDeviceCanAccessPeer(&can, g->dev[0], g->dev[(size_t)s]);
+                if (can) {
+                    hipSetDevice(g->dev[0]);
+                    hipDeviceEnablePeerAccess(g->dev[(size_t)s], 0); // already enabled is fine
+                    hipSetDevice(g->dev[(size_t)s]);
+                    hipDeviceEnablePeerAccess(g->dev[0], 0);
+                    (void)hipGetLastError();
+                }
+            }
+        g->rccl = false;
+        g->path_note = "in-process exchange (sums on shard 0's stream, peer copies)";
+        // CMI_GROUP_TRY_RCCL=1 (test hook): attempt RCCL although shards share a device -- ncclCommInitAll refuses duplicate devices, which
+        // drives the fallback below on a single-GPU box (tests/test_gpu_bench_group.py)
+        const bool try_rccl = distinct || getenv("CMI_GROUP_TRY_RCCL");
+        if (!distinct && !try_rccl) g->path_note += ": shards share a device";
+        if (try_rccl) {
+            g->comm.assign((size_t)W, nullptr);
+            const ncclResult_t r = ncclCommInitAll(g->comm.data(), W, g->dev.data());
+            if (r != ncclSuccess) {
+                g->comm.clear();
                 (void)hipGetLastError();
+                g->path_note = std::string("in-process exchange (peer copies) -- FALLBACK: ncclCommInitAll failed: ") + ncclGetErrorString(r);
+                fprintf(stderr, "[cmi] group: %s\n", g->path_note.c_str());
+            } else {
+                g->rccl = true;
+                if (int rc = group_preflight(g)) return rc; // (may switch to the in-process exchange; only a HIP failure is an error)
             }
         }
-    g->rccl = false;
-    g->path_note = "in-process exchange (sums on shard 0's stream, peer copies)";
-    // CMI_GROUP_TRY_RCCL=1 (test hook): attempt RCCL although shards share a device -- ncclCommInitAll refuses duplicate devices, which
-    // drives the fallback below on a single-GPU box (tests/test_gpu_bench_group.py)
-    const bool try_rccl = distinct || getenv("CMI_GROUP_TRY_RCCL");
-    if (!distinct && !try_rccl) g->path_note += ": shards share a device";
-    if (try_rccl) {
-        g->comm.assign((size_t)W, nullptr);
-        const ncclResult_t r = ncclCommInitAll(g->comm.data(), W, g->dev.data());
-        if (r != ncclSuccess) {
-            g->comm.clear();
-            (void)hipGetLastError();
-            g->path_note = std::string("in-process exchange (peer copies) -- FALLBACK: ncclCommInitAll failed: ") + ncclGetErrorString(r);
-            fprintf(stderr, "[cmi] group: %s\n", g->path_note.c_str());
-        } else {
-            g->rccl = true;
-            if (int rc = group_preflight(g)) return rc; // (may switch to the in-process exchange; only a HIP failure is an error)
-        }
-    }
-    return CMI_OK;
+        return CMI_OK;
+    });
 }
 
 static int need_ratings(cmi_group *g, const char *what) {
-    if (g->inst.empty()) GRP_FAIL(g, CMI_E_INVALID, "%s: call cmi_group_set_ratings first (the user cut depends on the ratings)", what);
+    if (g->inst.empty()) CMI_FAIL(g, CMI_E_INVALID, "%s: call cmi_group_set_ratings first (the user cut depends on the ratings)", what);
     return CMI_OK;
 }
 
@@ -351,7 +337,7 @@ extern "C" int cmi_group_set_state(cmi_group_handle g, int which, const void *sr
         for (int s = 0; s < W; ++s) GRP_MEMBER(g, s, cmi_set_state(g->inst[(size_t)s], which, src, count, dtype));
         return CMI_OK;
     }
-    if (count % g->n_users != 0) GRP_FAIL(g, CMI_E_INVALID, "group_set_state: container %d: %lld elements is not a multiple of %d users", which, (long long)count, g->n_users);
+    if (count % g->n_users != 0) CMI_FAIL(g, CMI_E_INVALID, "group_set_state: container %d: %lld elements is not a multiple of %d users", which, (long long)count, g->n_users);
     const int64_t cols = count / g->n_users;
     for (int s = 0; s < W; ++s) {
         const int64_t lo = g->cut[(size_t)s], hi = g->cut[(size_t)s + 1];
@@ -369,7 +355,7 @@ extern "C" int cmi_group_get_state(cmi_group_handle g, int which, void *dst, int
         GRP_MEMBER(g, 0, cmi_get_state(g->inst[0], which, dst, count, dtype));
         return CMI_OK;
     }
-    if (count % g->n_users != 0) GRP_FAIL(g, CMI_E_INVALID, "group_get_state: container %d: %lld elements is not a multiple of %d users", which, (long long)count, g->n_users);
+    if (count % g->n_users != 0) CMI_FAIL(g, CMI_E_INVALID, "group_get_state: container %d: %lld elements is not a multiple of %d users", which, (long long)count, g->n_users);
     const int64_t cols = count / g->n_users;
     for (int s = 0; s < W; ++s) {
         const int64_t lo = g->cut[(size_t)s], hi = g->cut[(size_t)s + 1];
@@ -391,7 +377,7 @@ static int exchange_buckets(cmi_group *g, bool rccl, int64_t count, const std::v
                 const ncclResult_t r = exchange_collective(phase, g->comm[(size_t)s], g->bucket[(size_t)s], count, W, s, g->f64, dl[(size_t)s], st[(size_t)s]);
                 if (r != ncclSuccess) {
                     (void)ncclGroupEnd();
-                    GRP_FAIL(g, CMI_E_HIP, "exchange (phase %d, shard %d) failed: %s", phase, s, ncclGetErrorString(r));
+                    CMI_FAIL(g, CMI_E_HIP, "exchange (phase %d, shard %d) failed: %s", phase, s, ncclGetErrorString(r));
                 }
             }
             GRP_NCCL(g, ncclGroupEnd());
@@ -400,34 +386,34 @@ static int exchange_buckets(cmi_group *g, bool rccl, int64_t count, const std::v
         // in-process: shard 0's stream waits for every shard's pack, sums the buckets (and the losses) in shard order, the others copy
         // the sums back on their own streams
         for (int s = 1; s < W; ++s) {
-            GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-            GRP_HIP(g, hipEventRecord(g->ev[(size_t)s], st[(size_t)s]));
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+            CMI_HIP(g, hipEventRecord(g->ev[(size_t)s], st[(size_t)s]));
         }
-        GRP_HIP(g, hipSetDevice(g->dev[0]));
+        CMI_HIP(g, hipSetDevice(g->dev[0]));
         double *stage_loss = (double *)((char *)g->d_stage + (size_t)count * es);
         for (int s = 1; s < W; ++s) {
-            GRP_HIP(g, hipStreamWaitEvent(st[0], g->ev[(size_t)s], 0));
+            CMI_HIP(g, hipStreamWaitEvent(st[0], g->ev[(size_t)s], 0));
             const void *src = g->bucket[(size_t)s];
             if (g->dev[(size_t)s] != g->dev[0]) {
-                GRP_HIP(g, hipMemcpyPeerAsync(g->d_stage, g->dev[0], g->bucket[(size_t)s], g->dev[(size_t)s], (size_t)count * es, st[0]));
-                GRP_HIP(g, hipMemcpyPeerAsync(stage_loss, g->dev[0], dl[(size_t)s], g->dev[(size_t)s], 8, st[0]));
+                CMI_HIP(g, hipMemcpyPeerAsync(g->d_stage, g->dev[0], g->bucket[(size_t)s], g->dev[(size_t)s], (size_t)count * es, st[0]));
+                CMI_HIP(g, hipMemcpyPeerAsync(stage_loss, g->dev[0], dl[(size_t)s], g->dev[(size_t)s], 8, st[0]));
                 src = g->d_stage;
-                GRP_HIP(g, group_add(dl[0], stage_loss, 1, true, st[0]));
+                CMI_HIP(g, group_add(dl[0], stage_loss, 1, true, st[0]));
             } else {
-                GRP_HIP(g, group_add(dl[0], dl[(size_t)s], 1, true, st[0]));
+                CMI_HIP(g, group_add(dl[0], dl[(size_t)s], 1, true, st[0]));
             }
-            GRP_HIP(g, group_add(g->bucket[0], src, count, g->f64, st[0]));
+            CMI_HIP(g, group_add(g->bucket[0], src, count, g->f64, st[0]));
         }
-        GRP_HIP(g, hipEventRecord(g->ev[(size_t)W], st[0]));
+        CMI_HIP(g, hipEventRecord(g->ev[(size_t)W], st[0]));
         for (int s = 1; s < W; ++s) {
-            GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-            GRP_HIP(g, hipStreamWaitEvent(st[(size_t)s], g->ev[(size_t)W], 0));
-            GRP_HIP(g, hipMemcpyPeerAsync(g->bucket[(size_t)s], g->dev[(size_t)s], g->bucket[0], g->dev[0], (size_t)count * es, st[(size_t)s]));
-            GRP_HIP(g, hipMemcpyPeerAsync(dl[(size_t)s], g->dev[(size_t)s], dl[0], g->dev[0], 8, st[(size_t)s]));
-            GRP_HIP(g, hipEventRecord(g->ev[(size_t)s], st[(size_t)s])); // shard 0 must not start its next pack before the copies have read bucket 0
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+            CMI_HIP(g, hipStreamWaitEvent(st[(size_t)s], g->ev[(size_t)W], 0));
+            CMI_HIP(g, hipMemcpyPeerAsync(g->bucket[(size_t)s], g->dev[(size_t)s], g->bucket[0], g->dev[0], (size_t)count * es, st[(size_t)s]));
+            CMI_HIP(g, hipMemcpyPeerAsync(dl[(size_t)s], g->dev[(size_t)s], dl[0], g->dev[0], 8, st[(size_t)s]));
+            CMI_HIP(g, hipEventRecord(g->ev[(size_t)s], st[(size_t)s])); // shard 0 must not start its next pack before the copies have read bucket 0
         }
-        GRP_HIP(g, hipSetDevice(g->dev[0]));
-        for (int s = 1; s < W; ++s) GRP_HIP(g, hipStreamWaitEvent(st[0], g->ev[(size_t)s], 0));
+        CMI_HIP(g, hipSetDevice(g->dev[0]));
+        for (int s = 1; s < W; ++s) CMI_HIP(g, hipStreamWaitEvent(st[0], g->ev[(size_t)s], 0));
     }
     return CMI_OK;
 }
@@ -460,10 +446,10 @@ static int group_preflight(cmi_group *g) {
                 else ((float *)host.data())[i] = (float)value(i, s);
             }
             const double l = s + 1.0;
-            GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-            GRP_HIP(g, hipMemcpyAsync(g->bucket[(size_t)s], host.data(), (size_t)count * es, hipMemcpyHostToDevice, st[(size_t)s]));
-            GRP_HIP(g, hipMemcpyAsync(dl[(size_t)s], &l, 8, hipMemcpyHostToDevice, st[(size_t)s]));
-            GRP_HIP(g, hipStreamSynchronize(st[(size_t)s])); // (host and l are reused)
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+            CMI_HIP(g, hipMemcpyAsync(g->bucket[(size_t)s], host.data(), (size_t)count * es, hipMemcpyHostToDevice, st[(size_t)s]));
+            CMI_HIP(g, hipMemcpyAsync(dl[(size_t)s], &l, 8, hipMemcpyHostToDevice, st[(size_t)s]));
+            CMI_HIP(g, hipStreamSynchronize(st[(size_t)s])); // (host and l are reused)
         }
         const std::string keep = g->err;
         if (exchange_buckets(g, rccl, count, st, dl) != CMI_OK) {
@@ -474,10 +460,10 @@ static int group_preflight(cmi_group *g) {
         }
         for (int s = 0; s < W; ++s) {
             double l = 0.0;
-            GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-            GRP_HIP(g, hipMemcpyAsync(host.data(), g->bucket[(size_t)s], (size_t)count * es, hipMemcpyDeviceToHost, st[(size_t)s]));
-            GRP_HIP(g, hipMemcpyAsync(&l, dl[(size_t)s], 8, hipMemcpyDeviceToHost, st[(size_t)s]));
-            GRP_HIP(g, hipStreamSynchronize(st[(size_t)s]));
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+            CMI_HIP(g, hipMemcpyAsync(host.data(), g->bucket[(size_t)s], (size_t)count * es, hipMemcpyDeviceToHost, st[(size_t)s]));
+            CMI_HIP(g, hipMemcpyAsync(&l, dl[(size_t)s], 8, hipMemcpyDeviceToHost, st[(size_t)s]));
+            CMI_HIP(g, hipStreamSynchronize(st[(size_t)s]));
             for (int64_t i = 0; i < count && why.empty(); ++i) {
                 const double got = g->f64 ? ((double *)host.data())[i] : (double)((float *)host.data())[i];
                 if (got != want[(size_t)i]) {
@@ -494,7 +480,7 @@ static int group_preflight(cmi_group *g) {
     if (int rc = run(true, why_rccl)) return rc;
     if (getenv("CMI_GROUP_PREFLIGHT_FAIL")) why_rccl = "forced by CMI_GROUP_PREFLIGHT_FAIL (test hook)";
     if (int rc = run(false, why_local)) return rc;
-    if (!why_local.empty()) GRP_FAIL(g, CMI_E_HIP, "group: the in-process exchange failed its pre-flight: %s", why_local.c_str());
+    if (!why_local.empty()) CMI_FAIL(g, CMI_E_HIP, "group: the in-process exchange failed its pre-flight: %s", why_local.c_str());
     if (why_rccl.empty()) {
         g->path_note = "RCCL (grouped ncclReduceScatter + ncclAllGather + loss ncclAllReduce over the process's communicators); pre-flight: "
                        "bit-identical to the in-process exchange and to the host's sums";
@@ -516,16 +502,16 @@ static int group_exchange(cmi_group *g) {
     std::vector<double *> dl((size_t)W);
     for (int s = 0; s < W; ++s) {
         GRP_MEMBER(g, s, cmi_stream(g->inst[(size_t)s], (void **)&st[(size_t)s]));
-        GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-        GRP_HIP(g, hipEventRecord(g->tx[(size_t)2 * s], st[(size_t)s]));
+        CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+        CMI_HIP(g, hipEventRecord(g->tx[(size_t)2 * s], st[(size_t)s]));
         GRP_MEMBER(g, s, cmi_exchange_pack(g->inst[(size_t)s]));
         GRP_MEMBER(g, s, cmi_loss_device_ptr(g->inst[(size_t)s], (void **)&dl[(size_t)s]));
     }
     if (int rc = exchange_buckets(g, g->rccl, g->x_count, st, dl)) return rc;
     for (int s = 0; s < W; ++s) {
         GRP_MEMBER(g, s, cmi_exchange_apply(g->inst[(size_t)s], 1.0 / W));
-        GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-        GRP_HIP(g, hipEventRecord(g->tx[(size_t)2 * s + 1], st[(size_t)s]));
+        CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+        CMI_HIP(g, hipEventRecord(g->tx[(size_t)2 * s + 1], st[(size_t)s]));
     }
     g->timed = true;
     return CMI_OK;
@@ -541,9 +527,9 @@ extern "C" int cmi_group_last_times(cmi_group_handle g, float *compute_ms, float
         GRP_MEMBER(g, s, cmi_last_epoch_ms(g->inst[(size_t)s], &compute_ms[s]));
         exchange_ms[s] = 0.f;
         if (W > 1 && g->timed) {
-            GRP_HIP(g, hipSetDevice(g->dev[(size_t)s]));
-            GRP_HIP(g, hipEventSynchronize(g->tx[(size_t)2 * s + 1]));
-            GRP_HIP(g, hipEventElapsedTime(&exchange_ms[s], g->tx[(size_t)2 * s], g->tx[(size_t)2 * s + 1]));
+            CMI_HIP(g, hipSetDevice(g->dev[(size_t)s]));
+            CMI_HIP(g, hipEventSynchronize(g->tx[(size_t)2 * s + 1]));
+            CMI_HIP(g, hipEventElapsedTime(&exchange_ms[s], g->tx[(size_t)2 * s], g->tx[(size_t)2 * s + 1]));
         }
     }
     return CMI_OK;
@@ -551,18 +537,20 @@ extern "C" int cmi_group_last_times(cmi_group_handle g, float *compute_ms, float
 
 extern "C" int cmi_group_train_epoch(cmi_group_handle g, double lrate, double *loss_out) {
     if (!g) return CMI_E_INVALID;
-    if (int rc = need_ratings(g, "group_train_epoch")) return rc;
-    const int W = (int)g->inst.size();
-    const double local_lr = W > 1 ? lrate * g->lr_scale : lrate;
-    for (int s = 0; s < W; ++s) GRP_MEMBER(g, s, cmi_train_epoch_async(g->inst[(size_t)s], local_lr));
-    if (W > 1)
-        if (int rc = group_exchange(g)) return rc;
-    // the one host synchronisation of the epoch: the (already global) loss of shard 0, then the other shards' streams
-    double loss = 0.0, other = 0.0;
-    GRP_MEMBER(g, 0, cmi_last_loss(g->inst[0], &loss));
-    for (int s = 1; s < W; ++s) GRP_MEMBER(g, s, cmi_last_loss(g->inst[(size_t)s], &other)); // also surfaces a stalled owner epoch of that shard
-    if (loss_out) *loss_out = loss;
-    return CMI_OK;
+    return abi_barrier(g->err, "group_train_epoch", [&] {
+        if (int rc = need_ratings(g, "group_train_epoch")) return rc;
+        const int W = (int)g->inst.size();
+        const double local_lr = W > 1 ? lrate * g->lr_scale : lrate;
+        for (int s = 0; s < W; ++s) GRP_MEMBER(g, s, cmi_train_epoch_async(g->inst[(size_t)s], local_lr));
+        if (W > 1)
+            if (int rc = group_exchange(g)) return rc;
+        // the one host synchronisation of the epoch: the (already global) loss of shard 0, then the other shards' streams
+        double loss = 0.0, other = 0.0;
+        GRP_MEMBER(g, 0, cmi_last_loss(g->inst[0], &loss));
+        for (int s = 1; s < W; ++s) GRP_MEMBER(g, s, cmi_last_loss(g->inst[(size_t)s], &other)); // also surfaces a stalled owner epoch of that shard
+        if (loss_out) *loss_out = loss;
+        return CMI_OK;
+    });
 }
 
 // The mean merge divides every item row's move by W: at equal rate a W-shard run needs 1.2x / 1.4x / 1.6x the epochs of the sequential
@@ -570,7 +558,7 @@ extern "C" int cmi_group_train_epoch(cmi_group_handle g, double lrate, double *l
 // (tests/exp_merge_rule.py --time-to-rmse).  The host keeps steering the base rate (bold driver); default 1.
 extern "C" int cmi_group_set_lr_scale(cmi_group_handle g, double scale) {
     if (!g) return CMI_E_INVALID;
-    if (!(scale > 0.0)) GRP_FAIL(g, CMI_E_INVALID, "group_set_lr_scale: scale must be positive");
+    if (!(scale > 0.0)) CMI_FAIL(g, CMI_E_INVALID, "group_set_lr_scale: scale must be positive");
     g->lr_scale = scale;
     return CMI_OK;
 }
@@ -579,11 +567,13 @@ extern "C" int cmi_group_train_from(cmi_group_handle g, int first_iter, double p
                                     int bold_driver, double decay, int early_stop, double *losses, double *lrates, int *iters_run,
                                     double *final_lrate) {
     if (!g) return CMI_E_INVALID;
-    std::string err;
-    const int rc = cmi_train_loop([g](double lr, double *loss) { return cmi_group_train_epoch(g, lr, loss); }, err, first_iter, prev_loss, num_iters,
-                                  init_lrate, max_lrate, bold_driver, decay, early_stop, losses, lrates, iters_run, final_lrate);
-    if (rc != CMI_OK && !err.empty()) g->err = err;
-    return rc;
+    return abi_barrier(g->err, "group_train_from", [&] {
+        std::string err;
+        const int rc = cmi_train_loop([g](double lr, double *loss) { return cmi_group_train_epoch(g, lr, loss); }, err, first_iter, prev_loss, num_iters,
+                                      init_lrate, max_lrate, bold_driver, decay, early_stop, losses, lrates, iters_run, final_lrate);
+        if (rc != CMI_OK && !err.empty()) g->err = err;
+        return rc;
+    });
 }
 
 extern "C" int cmi_group_train(cmi_group_handle g, int num_iters, double init_lrate, double max_lrate, int bold_driver, double decay,
@@ -601,7 +591,7 @@ static int route(cmi_group *g, int64_t n, const int32_t *u, const int32_t *j, co
     const size_t W = g->inst.size();
     o.u.assign(W, {}), o.j.assign(W, {}), o.c.assign(W, {}), o.r.assign(W, {}), o.pos.assign(W, {});
     for (int64_t t = 0; t < n; ++t) {
-        if (u[t] < 0 || u[t] >= g->n_users) GRP_FAIL(g, CMI_E_INVALID, "eval: user id %d out of range at tuple %lld", u[t], (long long)t);
+        if (u[t] < 0 || u[t] >= g->n_users) CMI_FAIL(g, CMI_E_INVALID, "eval: user id %d out of range at tuple %lld", u[t], (long long)t);
         const size_t s = (size_t)shard_of(g->cut, u[t]);
         o.u[s].push_back(u[t] - g->cut[s]);
         o.j[s].push_back(j[t]);
@@ -615,49 +605,53 @@ static int route(cmi_group *g, int64_t n, const int32_t *u, const int32_t *j, co
 extern "C" int cmi_group_eval_ratings(cmi_group_handle g, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r,
                                       double min_rate, double max_rate, double *out, int64_t *count) {
     if (!g || !out) return CMI_E_INVALID;
-    if (int rc = need_ratings(g, "group_eval_ratings")) return rc;
-    if (n < 0 || (n > 0 && (!u || !j || !r))) GRP_FAIL(g, CMI_E_INVALID, "group_eval_ratings: null argument");
-    Routed ro;
-    if (int rc = route(g, n, u, j, ctx, r, ro)) return rc;
-    double tot[5] = {0, 0, 0, 0, 0};
-    for (size_t s = 0; s < g->inst.size(); ++s) {
-        double sums[5];
-        const int64_t m = (int64_t)ro.u[s].size();
-        GRP_MEMBER(g, s, cmi_eval_sums(g->inst[s], m, ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr, ro.r[s].data(), min_rate, max_rate, sums));
-        for (int c = 0; c < 5; ++c) tot[c] += sums[c];
-    }
-    const double cnt = tot[4], mae = tot[0] / cnt;
-    out[0] = mae;
-    out[1] = std::sqrt(tot[1] / cnt);
-    out[2] = mae / (max_rate - min_rate);
-    out[3] = tot[2] / cnt;
-    out[4] = std::sqrt(tot[3] / cnt);
-    if (count) *count = (int64_t)cnt;
-    return CMI_OK;
+    return abi_barrier(g->err, "group_eval_ratings", [&] {
+        if (int rc = need_ratings(g, "group_eval_ratings")) return rc;
+        if (n < 0 || (n > 0 && (!u || !j || !r))) CMI_FAIL(g, CMI_E_INVALID, "group_eval_ratings: null argument");
+        Routed ro;
+        if (int rc = route(g, n, u, j, ctx, r, ro)) return rc;
+        double tot[5] = {0, 0, 0, 0, 0};
+        for (size_t s = 0; s < g->inst.size(); ++s) {
+            double sums[5];
+            const int64_t m = (int64_t)ro.u[s].size();
+            GRP_MEMBER(g, s, cmi_eval_sums(g->inst[s], m, ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr, ro.r[s].data(), min_rate, max_rate, sums));
+            for (int c = 0; c < 5; ++c) tot[c] += sums[c];
+        }
+        const double cnt = tot[4], mae = tot[0] / cnt;
+        out[0] = mae;
+        out[1] = std::sqrt(tot[1] / cnt);
+        out[2] = mae / (max_rate - min_rate);
+        out[3] = tot[2] / cnt;
+        out[4] = std::sqrt(tot[3] / cnt);
+        if (count) *count = (int64_t)cnt;
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_group_predict_batch(cmi_group_handle g, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, int bound, double lo,
                                        double hi, double *out) {
     if (!g || !out) return CMI_E_INVALID;
-    if (int rc = need_ratings(g, "group_predict_batch")) return rc;
-    if (n < 0 || (n > 0 && (!u || !j))) GRP_FAIL(g, CMI_E_INVALID, "group_predict_batch: null argument");
-    Routed ro;
-    if (int rc = route(g, n, u, j, ctx, nullptr, ro)) return rc;
-    std::vector<double> tmp;
-    for (size_t s = 0; s < g->inst.size(); ++s) {
-        const int64_t m = (int64_t)ro.u[s].size();
-        if (m == 0) continue;
-        tmp.resize((size_t)m);
-        GRP_MEMBER(g, s, cmi_predict_batch(g->inst[s], m, ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr, bound, lo, hi, tmp.data()));
-        for (int64_t q = 0; q < m; ++q) out[ro.pos[s][(size_t)q]] = tmp[(size_t)q];
-    }
-    return CMI_OK;
+    return abi_barrier(g->err, "group_predict_batch", [&] {
+        if (int rc = need_ratings(g, "group_predict_batch")) return rc;
+        if (n < 0 || (n > 0 && (!u || !j))) CMI_FAIL(g, CMI_E_INVALID, "group_predict_batch: null argument");
+        Routed ro;
+        if (int rc = route(g, n, u, j, ctx, nullptr, ro)) return rc;
+        std::vector<double> tmp;
+        for (size_t s = 0; s < g->inst.size(); ++s) {
+            const int64_t m = (int64_t)ro.u[s].size();
+            if (m == 0) continue;
+            tmp.resize((size_t)m);
+            GRP_MEMBER(g, s, cmi_predict_batch(g->inst[s], m, ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr, bound, lo, hi, tmp.data()));
+            for (int64_t q = 0; q < m; ++q) out[ro.pos[s][(size_t)q]] = tmp[(size_t)q];
+        }
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_group_shard_info(cmi_group_handle g, int shard, int64_t info[6]) {
     if (!g || !info) return CMI_E_INVALID;
     if (int rc = need_ratings(g, "group_shard_info")) return rc;
-    if (shard < 0 || shard >= (int)g->inst.size()) GRP_FAIL(g, CMI_E_INVALID, "group_shard_info: shard %d out of range", shard);
+    if (shard < 0 || shard >= (int)g->inst.size()) CMI_FAIL(g, CMI_E_INVALID, "group_shard_info: shard %d out of range", shard);
     info[0] = g->cut[(size_t)shard];
     info[1] = g->cut[(size_t)shard + 1];
     info[2] = g->shard_n[(size_t)shard];
@@ -670,7 +664,7 @@ extern "C" int cmi_group_shard_info(cmi_group_handle g, int shard, int64_t info[
 extern "C" int cmi_group_member(cmi_group_handle g, int shard, cmi_handle *out) {
     if (!g || !out) return CMI_E_INVALID;
     if (int rc = need_ratings(g, "group_member")) return rc;
-    if (shard < 0 || shard >= (int)g->inst.size()) GRP_FAIL(g, CMI_E_INVALID, "group_member: shard %d out of range", shard);
+    if (shard < 0 || shard >= (int)g->inst.size()) CMI_FAIL(g, CMI_E_INVALID, "group_member: shard %d out of range", shard);
     *out = g->inst[(size_t)shard];
     return CMI_OK;
 }
@@ -679,14 +673,16 @@ extern "C" int cmi_group_member(cmi_group_handle g, int shard, cmi_handle *out) 
 // every epoch): the test tuples go to the shard that owns their user ONCE and stay on its device ----------------------------------------
 extern "C" int cmi_group_set_eval_ratings(cmi_group_handle g, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r) {
     if (!g) return CMI_E_INVALID;
-    if (int rc = need_ratings(g, "group_set_eval_ratings")) return rc;
-    if (n < 0 || (n > 0 && (!u || !j || !r))) GRP_FAIL(g, CMI_E_INVALID, "group_set_eval_ratings: null argument");
-    Routed ro;
-    if (int rc = route(g, n, u, j, ctx, r, ro)) return rc;
-    for (size_t s = 0; s < g->inst.size(); ++s)
-        GRP_MEMBER(g, s, cmi_set_eval_ratings(g->inst[s], (int64_t)ro.u[s].size(), ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr,
-                                              ro.r[s].data()));
-    return CMI_OK;
+    return abi_barrier(g->err, "group_set_eval_ratings", [&] {
+        if (int rc = need_ratings(g, "group_set_eval_ratings")) return rc;
+        if (n < 0 || (n > 0 && (!u || !j || !r))) CMI_FAIL(g, CMI_E_INVALID, "group_set_eval_ratings: null argument");
+        Routed ro;
+        if (int rc = route(g, n, u, j, ctx, r, ro)) return rc;
+        for (size_t s = 0; s < g->inst.size(); ++s)
+            GRP_MEMBER(g, s, cmi_set_eval_ratings(g->inst[s], (int64_t)ro.u[s].size(), ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr,
+                                                  ro.r[s].data()));
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_group_eval_resident(cmi_group_handle g, double min_rate, double max_rate, double out[5], int64_t *count) {
@@ -699,7 +695,7 @@ extern "C" int cmi_group_eval_resident(cmi_group_handle g, double min_rate, doub
         GRP_MEMBER(g, s, cmi_eval_resident_sums(g->inst[s], min_rate, max_rate, sums));
         for (int c = 0; c < 5; ++c) tot[c] += sums[c];
     }
-    if (!(tot[4] > 0)) GRP_FAIL(g, CMI_E_INVALID, "group_eval_resident: call cmi_group_set_eval_ratings first");
+    if (!(tot[4] > 0)) CMI_FAIL(g, CMI_E_INVALID, "group_eval_resident: call cmi_group_set_eval_ratings first");
     const double cnt = tot[4], mae = tot[0] / cnt;
     out[0] = mae;
     out[1] = std::sqrt(tot[1] / cnt);

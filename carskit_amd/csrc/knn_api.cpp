@@ -6,10 +6,12 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <strings.h>
 #include <numeric>
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "knn_kernels.hpp"
 
 using namespace cmi;
@@ -31,46 +33,20 @@ struct cmi_knn_instance {
 
 static thread_local std::string g_knn_create_err;
 
-#define KNN_FAIL(h, code, ...)                                                                          \
-    do {                                                                                                \
-        char buf_[512];                                                                                 \
-        snprintf(buf_, sizeof buf_, __VA_ARGS__);                                                       \
-        (h)->err = buf_;                                                                                \
-        return (code);                                                                                  \
-    } while (0)
-#define KNN_HIP(h, expr)                                                                                \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) KNN_FAIL(h, CMI_E_HIP, "%s failed: %s", #expr, hipGetErrorString(e_));   \
-    } while (0)
-
-static void knn_free(void *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-template <typename T>
-static void knn_free(T *&p) {
-    void *q = p;
-    knn_free(q);
-    p = nullptr;
-}
-
 extern "C" const char *cmi_knn_last_error(cmi_knn_handle h) { return h ? h->err.c_str() : g_knn_create_err.c_str(); }
 
 extern "C" int cmi_knn_measure(const char *name) {
-    std::string s = name ? name : "";
-    for (char &c : s) c = (char)std::tolower((unsigned char)c);
-    if (s == "cos") return CMI_SIM_COS;
-    if (s == "cos-binary") return CMI_SIM_COS_BINARY;
-    if (s == "msd") return CMI_SIM_MSD;
-    if (s == "cpc") return CMI_SIM_CPC;
-    if (s == "exjaccard") return CMI_SIM_EXJACCARD;
+    const char *s = name ? name : ""; // (compared without a copy: nothing here allocates)
+    if (!strcasecmp(s, "cos")) return CMI_SIM_COS;
+    if (!strcasecmp(s, "cos-binary")) return CMI_SIM_COS_BINARY;
+    if (!strcasecmp(s, "msd")) return CMI_SIM_MSD;
+    if (!strcasecmp(s, "cpc")) return CMI_SIM_CPC;
+    if (!strcasecmp(s, "exjaccard")) return CMI_SIM_EXJACCARD;
     return CMI_SIM_PCC; // "pcc" and Recommender.correlation's default: branch
 }
 
 static void knn_free_ratings(cmi_knn_instance *h) {
-    knn_free(h->d_rok), knn_free(h->d_rptr), knn_free(h->d_ridx), knn_free(h->d_lptr), knn_free(h->d_lidx);
-    knn_free(h->d_rval), knn_free(h->d_lval), knn_free(h->d_mean), knn_free(h->d_norm2), knn_free(h->d_S);
+    abi_free(h->d_rok, h->d_rptr, h->d_ridx, h->d_lptr, h->d_lidx, h->d_rval, h->d_lval, h->d_mean, h->d_norm2, h->d_S);
     h->have_ratings = h->built = false;
 }
 
@@ -88,38 +64,32 @@ extern "C" int cmi_knn_destroy(cmi_knn_handle h) {
 
 extern "C" int cmi_knn_create(int kind, int n_users, int n_items, int device, unsigned flags, cmi_knn_handle *out) {
     (void)flags;
-    if (out) *out = nullptr;
-    if (!out || (kind != CMI_KNN_USER && kind != CMI_KNN_ITEM) || n_users <= 0 || n_items <= 0) {
-        g_knn_create_err = "cmi_knn_create: invalid argument";
-        return CMI_E_INVALID;
-    }
-    const int ndev = cmi_device_count();
-    if (ndev <= 0) {
-        g_knn_create_err = "cmi_knn_create: no HIP device visible (libcarskit_mi355x has no CPU fallback)";
-        return CMI_E_NO_DEVICE;
-    }
-    if (device < 0 || device >= ndev) {
-        g_knn_create_err = "cmi_knn_create: device index out of range";
-        return CMI_E_INVALID;
-    }
-    cmi_knn_instance *h = new cmi_knn_instance();
-    h->kind = kind;
-    h->n_users = n_users;
-    h->n_items = n_items;
-    h->device = device;
-    h->n_ent = kind == CMI_KNN_ITEM ? n_items : n_users;
-    h->n_ctr = kind == CMI_KNN_ITEM ? n_users : n_items;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev0);
-    if (e == hipSuccess) e = hipEventCreate(&h->ev1);
-    if (e != hipSuccess) {
-        g_knn_create_err = std::string("cmi_knn_create: ") + hipGetErrorString(e);
-        cmi_knn_destroy(h);
-        return CMI_E_HIP;
-    }
-    *out = h;
-    return CMI_OK;
+    return abi_barrier(g_knn_create_err, "cmi_knn_create", [&] {
+        if (out) *out = nullptr;
+        if (!out || (kind != CMI_KNN_USER && kind != CMI_KNN_ITEM) || n_users <= 0 || n_items <= 0) {
+            g_knn_create_err = "cmi_knn_create: invalid argument";
+            return CMI_E_INVALID;
+        }
+        if (int rc = abi_check_device(g_knn_create_err, "cmi_knn_create", device)) return rc;
+        cmi_knn_instance *h = new cmi_knn_instance();
+        h->kind = kind;
+        h->n_users = n_users;
+        h->n_items = n_items;
+        h->device = device;
+        h->n_ent = kind == CMI_KNN_ITEM ? n_items : n_users;
+        h->n_ctr = kind == CMI_KNN_ITEM ? n_users : n_items;
+        hipError_t e = hipSetDevice(device);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipEventCreate(&h->ev0);
+        if (e == hipSuccess) e = hipEventCreate(&h->ev1);
+        if (e != hipSuccess) {
+            g_knn_create_err = std::string("cmi_knn_create: ") + hipGetErrorString(e);
+            cmi_knn_destroy(h);
+            return CMI_E_HIP;
+        }
+        *out = h;
+        return CMI_OK;
+    });
 }
 
 // CSR of (row, col, value) cells, rows ascending, columns ascending inside a row
@@ -136,20 +106,12 @@ static void knn_csr(int64_t n, int n_rows, const int32_t *row, const int32_t *co
     for (size_t k = 0; k < ord.size(); ++k) idx[k] = col[ord[k]], val[k] = r[ord[k]];
 }
 
-template <typename T>
-static hipError_t knn_up(T **dst, const std::vector<T> &v, hipStream_t s) {
-    *dst = nullptr;
-    hipError_t e = hipMalloc((void **)dst, std::max<size_t>(1, v.size()) * sizeof(T));
-    if (e == hipSuccess && !v.empty()) e = hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s);
-    return e;
-}
-
 static int knn_set_ratings_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r) {
-    if (n < 0 || (n > 0 && (!u || !i || !r))) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: null arrays");
-    if (n >= ((int64_t)1 << 31)) KNN_FAIL(h, CMI_E_UNSUPPORTED, "cmi_knn_set_ratings: more than 2^31-1 cells");
+    if (n < 0 || (n > 0 && (!u || !i || !r))) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: null arrays");
+    if (n >= ((int64_t)1 << 31)) CMI_FAIL(h, CMI_E_UNSUPPORTED, "cmi_knn_set_ratings: more than 2^31-1 cells");
     for (int64_t t = 0; t < n; ++t)
         if (u[t] < 0 || u[t] >= h->n_users || i[t] < 0 || i[t] >= h->n_items)
-            KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: id out of range at cell %lld", (long long)t);
+            CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: id out of range at cell %lld", (long long)t);
     const bool item = h->kind == CMI_KNN_ITEM;
     const int32_t *ent = item ? i : u, *ctr = item ? u : i;
     std::vector<int32_t> rptr, ridx, lptr, lidx;
@@ -158,7 +120,7 @@ static int knn_set_ratings_impl(cmi_knn_handle h, int64_t n, const int32_t *u, c
     for (int e = 0; e < h->n_ent; ++e)
         for (int32_t k = rptr[(size_t)e] + 1; k < rptr[(size_t)e + 1]; ++k)
             if (ridx[(size_t)k] == ridx[(size_t)k - 1])
-                KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: duplicate cell (user %d, item %d)", item ? ridx[(size_t)k] : e,
+                CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_set_ratings: duplicate cell (user %d, item %d)", item ? ridx[(size_t)k] : e,
                          item ? e : ridx[(size_t)k]);
     knn_csr(n, h->n_ctr, ctr, ent, r, lptr, lidx, lval);
     // librec SparseVector.contains: Arrays.binarySearch over the whole index array of a vector built by set() -- capacity the next
@@ -183,23 +145,23 @@ static int knn_set_ratings_impl(cmi_knn_handle h, int64_t n, const int32_t *u, c
             }
         }
     }
-    KNN_HIP(h, hipSetDevice(h->device));
-    KNN_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     knn_free_ratings(h);
-    hipError_t e = knn_up(&h->d_rptr, rptr, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_ridx, ridx, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_rval, rval, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_rok, rok, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_lptr, lptr, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_lidx, lidx, h->stream);
-    if (e == hipSuccess) e = knn_up(&h->d_lval, lval, h->stream);
+    hipError_t e = abi_upload(&h->d_rptr, rptr, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_ridx, ridx, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_rval, rval, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_rok, rok, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_lptr, lptr, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_lidx, lidx, h->stream, true);
+    if (e == hipSuccess) e = abi_upload(&h->d_lval, lval, h->stream, true);
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_mean, (size_t)h->n_ent * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void **)&h->d_norm2, (size_t)h->n_ent * sizeof(double));
     if (e == hipSuccess) e = knn_launch_row_stats(KnnCsr{h->d_rptr, h->d_ridx, h->d_rval, h->d_rok}, h->n_ent, h->d_mean, h->d_norm2, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) {
         knn_free_ratings(h);
-        KNN_FAIL(h, CMI_E_HIP, "cmi_knn_set_ratings: %s", hipGetErrorString(e));
+        CMI_FAIL(h, CMI_E_HIP, "cmi_knn_set_ratings: %s", hipGetErrorString(e));
     }
     h->list_len.resize((size_t)h->n_ctr);
     for (int c = 0; c < h->n_ctr; ++c) h->list_len[(size_t)c] = lptr[(size_t)c + 1] - lptr[(size_t)c];
@@ -209,77 +171,72 @@ static int knn_set_ratings_impl(cmi_knn_handle h, int64_t n, const int32_t *u, c
 
 extern "C" int cmi_knn_set_ratings(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r) {
     if (!h) return CMI_E_INVALID;
-    try {
-        return knn_set_ratings_impl(h, n, u, i, r);
-    } catch (const std::exception &e) {
-        knn_free_ratings(h);
-        KNN_FAIL(h, CMI_E_HOST, "cmi_knn_set_ratings: host-side failure: %s", e.what());
-    }
+    return abi_barrier(h->err, "cmi_knn_set_ratings", [&] { return knn_set_ratings_impl(h, n, u, i, r); }, [h] { knn_free_ratings(h); });
 }
 
 extern "C" int cmi_knn_build(cmi_knn_handle h, int measure, int shrinkage, double min_rate, double max_rate) {
     if (!h) return CMI_E_INVALID;
-    if (!h->have_ratings) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_build: no ratings (cmi_knn_set_ratings first)");
-    if (measure < CMI_SIM_PCC || measure > CMI_SIM_EXJACCARD) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_build: unknown measure %d", measure);
-    KNN_HIP(h, hipSetDevice(h->device));
-    KNN_HIP(h, hipStreamSynchronize(h->stream));
+    if (!h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_build: no ratings (cmi_knn_set_ratings first)");
+    if (measure < CMI_SIM_PCC || measure > CMI_SIM_EXJACCARD) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_build: unknown measure %d", measure);
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     const size_t bytes = (size_t)h->n_ent * (size_t)h->n_ent * sizeof(double);
     if (!h->d_S) { // the dense n x n matrix: refused up front when it cannot fit, so a build never fails half-way
         size_t free_b = 0, total_b = 0;
-        KNN_HIP(h, hipMemGetInfo(&free_b, &total_b));
+        CMI_HIP(h, hipMemGetInfo(&free_b, &total_b));
         if (bytes > free_b)
-            KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_build: the %d x %d similarity matrix needs %zu bytes of device memory, %zu are free",
+            CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_build: the %d x %d similarity matrix needs %zu bytes of device memory, %zu are free",
                      h->n_ent, h->n_ent, bytes, free_b);
         hipError_t e = hipMalloc((void **)&h->d_S, std::max<size_t>(bytes, 8));
         if (e != hipSuccess) {
             h->d_S = nullptr;
-            KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_build: the similarity matrix needs %zu bytes of device memory: %s", bytes,
+            CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_build: the similarity matrix needs %zu bytes of device memory: %s", bytes,
                      hipGetErrorString(e));
         }
     }
     h->built = false;
-    KNN_HIP(h, hipEventRecord(h->ev0, h->stream));
-    KNN_HIP(h, hipMemsetAsync(h->d_S, 0xff, bytes, h->stream)); // all-ones bits: NaN, "unset"
-    KNN_HIP(h, knn_launch_build(KnnCsr{h->d_rptr, h->d_ridx, h->d_rval, h->d_rok}, h->n_ent, h->d_norm2, measure, shrinkage,
+    CMI_HIP(h, hipEventRecord(h->ev0, h->stream));
+    CMI_HIP(h, hipMemsetAsync(h->d_S, 0xff, bytes, h->stream)); // all-ones bits: NaN, "unset"
+    CMI_HIP(h, knn_launch_build(KnnCsr{h->d_rptr, h->d_ridx, h->d_rval, h->d_rok}, h->n_ent, h->d_norm2, measure, shrinkage,
                                 (min_rate + max_rate) / 2.0, h->d_S, h->stream));
-    KNN_HIP(h, hipEventRecord(h->ev1, h->stream));
-    KNN_HIP(h, hipStreamSynchronize(h->stream));
-    KNN_HIP(h, hipEventElapsedTime(&h->build_ms, h->ev0, h->ev1));
+    CMI_HIP(h, hipEventRecord(h->ev1, h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipEventElapsedTime(&h->build_ms, h->ev0, h->ev1));
     h->built = true;
     return CMI_OK;
 }
 
 extern "C" int cmi_knn_get_similarity(cmi_knn_handle h, int32_t row0, int32_t nrows, double *dst) {
     if (!h) return CMI_E_INVALID;
-    if (!h->built) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_get_similarity: no similarity matrix (cmi_knn_build first)");
+    if (!h->built) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_get_similarity: no similarity matrix (cmi_knn_build first)");
     if (row0 < 0 || nrows < 0 || (int64_t)row0 + nrows > h->n_ent || (nrows > 0 && !dst))
-        KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_get_similarity: rows [%d, %d) out of range", row0, row0 + nrows);
-    KNN_HIP(h, hipSetDevice(h->device));
-    KNN_HIP(h, hipMemcpyAsync(dst, h->d_S + (size_t)row0 * h->n_ent, (size_t)nrows * h->n_ent * sizeof(double), hipMemcpyDeviceToHost,
+        CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_get_similarity: rows [%d, %d) out of range", row0, row0 + nrows);
+    CMI_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipMemcpyAsync(dst, h->d_S + (size_t)row0 * h->n_ent, (size_t)nrows * h->n_ent * sizeof(double), hipMemcpyDeviceToHost,
                               h->stream));
-    KNN_HIP(h, hipStreamSynchronize(h->stream));
+    CMI_HIP(h, hipStreamSynchronize(h->stream));
     return CMI_OK;
 }
 
 static int knn_predict_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *j, int knn, double gm, int bound, double lo,
                             double hi, double *out) {
-    if (!h->built) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: no similarity matrix (cmi_knn_build first)");
-    if (n < 0 || (n > 0 && (!u || !j || !out))) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: null arrays");
+    if (!h->built) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: no similarity matrix (cmi_knn_build first)");
+    if (n < 0 || (n > 0 && (!u || !j || !out))) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: null arrays");
     if (n == 0) return CMI_OK;
     for (int64_t t = 0; t < n; ++t)
         if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items)
-            KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: id out of range at tuple %lld", (long long)t);
+            CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_predict_batch: id out of range at tuple %lld", (long long)t);
     const bool item = h->kind == CMI_KNN_ITEM;
     const int32_t *owner = item ? u : j, *target = item ? j : u; // ItemKNN: the user's items scored against item j; UserKNN: the reverse
     int cap = 1;
     for (int64_t t = 0; t < n; ++t) {
         const int len = h->list_len[(size_t)owner[t]];
         if (len > CMI_KNN_MAX_CANDIDATES)
-            KNN_FAIL(h, CMI_E_UNSUPPORTED, "cmi_knn_predict_batch: tuple %lld has %d candidates, more than CMI_KNN_MAX_CANDIDATES (%d)",
+            CMI_FAIL(h, CMI_E_UNSUPPORTED, "cmi_knn_predict_batch: tuple %lld has %d candidates, more than CMI_KNN_MAX_CANDIDATES (%d)",
                      (long long)t, len, CMI_KNN_MAX_CANDIDATES);
         cap = std::max(cap, len);
     }
-    KNN_HIP(h, hipSetDevice(h->device));
+    CMI_HIP(h, hipSetDevice(h->device));
     // one wave per tuple in flight; every wave owns `cap` entries (the longest list of the batch) of each scratch array (32 bytes an
     // entry), at most ~1 GiB
     const int64_t by_mem = std::max<int64_t>(1, ((int64_t)1 << 30) / ((int64_t)cap * 32));
@@ -306,11 +263,10 @@ static int knn_predict_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const
     if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    void *ptrs[] = {d_owner, d_target, d_out, d_bad, s_key, s_pos, s_sel, s_sim, s_rate};
-    for (void *p : ptrs) knn_free(p);
-    if (e != hipSuccess) KNN_FAIL(h, CMI_E_HIP, "cmi_knn_predict_batch: %s", hipGetErrorString(e));
+    abi_free(d_owner, d_target, d_out, d_bad, s_key, s_pos, s_sel, s_sim, s_rate);
+    if (e != hipSuccess) CMI_FAIL(h, CMI_E_HIP, "cmi_knn_predict_batch: %s", hipGetErrorString(e));
     if (bad)
-        KNN_FAIL(h, CMI_E_UNSUPPORTED,
+        CMI_FAIL(h, CMI_E_UNSUPPORTED,
                  "cmi_knn_predict_batch: %d tuple(s) would treeify a java.util.HashMap bin, whose iteration order is not modelled", bad);
     return CMI_OK;
 }
@@ -318,16 +274,12 @@ static int knn_predict_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const
 extern "C" int cmi_knn_predict_batch(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *j, int knn, double global_mean,
                                      int bound, double lo, double hi, double *out) {
     if (!h) return CMI_E_INVALID;
-    try {
-        return knn_predict_impl(h, n, u, j, knn, global_mean, bound, lo, hi, out);
-    } catch (const std::exception &e) {
-        KNN_FAIL(h, CMI_E_HOST, "cmi_knn_predict_batch: host-side failure: %s", e.what());
-    }
+    return abi_barrier(h->err, "cmi_knn_predict_batch", [&] { return knn_predict_impl(h, n, u, j, knn, global_mean, bound, lo, hi, out); });
 }
 
 extern "C" int cmi_knn_last_build_ms(cmi_knn_handle h, float *ms) {
     if (!h || !ms) return CMI_E_INVALID;
-    if (!h->built) KNN_FAIL(h, CMI_E_INVALID, "cmi_knn_last_build_ms: nothing built yet");
+    if (!h->built) CMI_FAIL(h, CMI_E_INVALID, "cmi_knn_last_build_ms: nothing built yet");
     *ms = h->build_ms;
     return CMI_OK;
 }

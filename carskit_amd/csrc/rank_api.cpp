@@ -15,6 +15,7 @@
 
 #include <unistd.h>
 
+#include "abi.hpp"
 #include "cmi_instance.hpp"
 #include "host_pool.hpp"
 #include "rank_host.hpp"
@@ -585,12 +586,6 @@ void rank_average(const RankPlan &plan, int strategy, const int32_t *top_count, 
     if (strategy == CMI_RANK_UC) {
         rank_sum_queries(top_count, vals, f, nq); // (what the batches have not added yet)
     } else {
-        std::unique_ptr<double[]> own;
-        if (!umeans) { // a caller without a workspace buffer: at most one user per query
-            own.reset(new double[(size_t)nq * N_MEAS + 1]);
-            umeans = own.get();
-            f = RankFolded();
-        }
         if (f.q < nq) rank_fold_users(plan, top_count, vals, umeans, f, nq, true); // (also sums the users it folds)
     }
     MeanAcc total;
@@ -1107,142 +1102,119 @@ extern "C" int cmi_rank_plan(int32_t n_users, int32_t n_items, int64_t n_train, 
                              const int32_t *sctx, const double *sr, double bin_thold, int num_ignore, int64_t sizes[4],
                              int32_t *cand, int32_t *q_user, int32_t *q_ctx, int64_t *truth_ptr, int32_t *truth_items,
                              int64_t *excl_ptr, int32_t *excl_idx) {
-    if (!sizes || n_users <= 0 || n_items <= 0 || n_train < 0 || n_test < 0 || (n_train > 0 && (!tu || !tj || !tctx)) ||
-        (n_test > 0 && (!su || !sj || !sctx || !sr)))
-        return CMI_E_INVALID;
-    for (int64_t t = 0; t < n_train; ++t)
-        if (tu[t] < 0 || tu[t] >= n_users || tj[t] < 0 || tj[t] >= n_items || tctx[t] < 0) return CMI_E_INVALID;
-    for (int64_t t = 0; t < n_test; ++t)
-        if (su[t] < 0 || su[t] >= n_users || sj[t] < 0 || sj[t] >= n_items || sctx[t] < 0) return CMI_E_INVALID;
-    RankPlan plan;
-    rank_build_plan(n_users, n_items, RankTuples{n_train, tu, tj, tctx, tr}, RankTuples{n_test, su, sj, sctx, sr}, bin_thold,
-                    num_ignore, plan);
-    sizes[0] = (int64_t)plan.cand.size();
-    sizes[1] = (int64_t)plan.qu.size();
-    sizes[2] = (int64_t)plan.truth_items.size();
-    sizes[3] = (int64_t)plan.excl_idx.size();
-    if (cand) std::copy(plan.cand.begin(), plan.cand.end(), cand);
-    if (q_user) std::copy(plan.qu.begin(), plan.qu.end(), q_user);
-    if (q_ctx) std::copy(plan.qc.begin(), plan.qc.end(), q_ctx);
-    if (truth_ptr) std::copy(plan.truth_ptr.begin(), plan.truth_ptr.end(), truth_ptr);
-    if (truth_items) std::copy(plan.truth_items.begin(), plan.truth_items.end(), truth_items);
-    if (excl_ptr) std::copy(plan.excl_ptr.begin(), plan.excl_ptr.end(), excl_ptr);
-    if (excl_idx) std::copy(plan.excl_idx.begin(), plan.excl_idx.end(), excl_idx);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_rank_plan", [&] {
+        if (!sizes || n_users <= 0 || n_items <= 0 || n_train < 0 || n_test < 0 || (n_train > 0 && (!tu || !tj || !tctx)) ||
+            (n_test > 0 && (!su || !sj || !sctx || !sr)))
+            return CMI_E_INVALID;
+        for (int64_t t = 0; t < n_train; ++t)
+            if (tu[t] < 0 || tu[t] >= n_users || tj[t] < 0 || tj[t] >= n_items || tctx[t] < 0) return CMI_E_INVALID;
+        for (int64_t t = 0; t < n_test; ++t)
+            if (su[t] < 0 || su[t] >= n_users || sj[t] < 0 || sj[t] >= n_items || sctx[t] < 0) return CMI_E_INVALID;
+        RankPlan plan;
+        rank_build_plan(n_users, n_items, RankTuples{n_train, tu, tj, tctx, tr}, RankTuples{n_test, su, sj, sctx, sr}, bin_thold,
+                        num_ignore, plan);
+        sizes[0] = (int64_t)plan.cand.size();
+        sizes[1] = (int64_t)plan.qu.size();
+        sizes[2] = (int64_t)plan.truth_items.size();
+        sizes[3] = (int64_t)plan.excl_idx.size();
+        if (cand) std::copy(plan.cand.begin(), plan.cand.end(), cand);
+        if (q_user) std::copy(plan.qu.begin(), plan.qu.end(), q_user);
+        if (q_ctx) std::copy(plan.qc.begin(), plan.qc.end(), q_ctx);
+        if (truth_ptr) std::copy(plan.truth_ptr.begin(), plan.truth_ptr.end(), truth_ptr);
+        if (truth_items) std::copy(plan.truth_items.begin(), plan.truth_items.end(), truth_items);
+        if (excl_ptr) std::copy(plan.excl_ptr.begin(), plan.excl_ptr.end(), excl_ptr);
+        if (excl_idx) std::copy(plan.excl_idx.begin(), plan.excl_idx.end(), excl_idx);
+        return CMI_OK;
+    });
 }
 
 // host-only: the 18 measures of one ranked list, as cmi_eval_rankings computes them per query
 extern "C" int cmi_rank_list_measures(const int32_t *ranked, int len, const int32_t *truth_sorted, int n_truth, int num_dropped,
                                       int num_recs, double out[18]) {
-    if (len < 0 || n_truth <= 0 || num_recs < 1 || !truth_sorted || !out || (len > 0 && !ranked)) return CMI_E_INVALID;
-    for (int i = 1; i < n_truth; ++i)
-        if (truth_sorted[i - 1] >= truth_sorted[i]) return CMI_E_INVALID; // strictly ascending (binary search)
-    const Truth t{truth_sorted, n_truth};
-    list_measures(ranked, len, t, num_dropped, num_recs, out);
-    return CMI_OK;
+    return abi_barrier(cmi_thread_err(), "cmi_rank_list_measures", [&] {
+        if (len < 0 || n_truth <= 0 || num_recs < 1 || !truth_sorted || !out || (len > 0 && !ranked)) return CMI_E_INVALID;
+        for (int i = 1; i < n_truth; ++i)
+            if (truth_sorted[i - 1] >= truth_sorted[i]) return CMI_E_INVALID; // strictly ascending (binary search)
+        const Truth t{truth_sorted, n_truth};
+        list_measures(ranked, len, t, num_dropped, num_recs, out);
+        return CMI_OK;
+    });
 }
 
 extern "C" int cmi_java_int_hashset_order(int64_t n, const int32_t *values, int32_t *out, int64_t *n_out) {
-    if (n < 0 || (n > 0 && (!values || !out)) || !n_out) return CMI_E_INVALID;
-    std::vector<int32_t> first;
-    {
-        std::vector<int32_t> sorted(values, values + n);
-        std::sort(sorted.begin(), sorted.end());
-        sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
-        std::vector<char> seen(sorted.size(), 0);
-        for (int64_t i = 0; i < n; ++i) {
-            const size_t p = std::lower_bound(sorted.begin(), sorted.end(), values[i]) - sorted.begin();
-            if (!seen[p]) {
-                seen[p] = 1;
-                first.push_back(values[i]);
+    return abi_barrier(cmi_thread_err(), "cmi_java_int_hashset_order", [&] {
+        if (n < 0 || (n > 0 && (!values || !out)) || !n_out) return CMI_E_INVALID;
+        std::vector<int32_t> first;
+        {
+            std::vector<int32_t> sorted(values, values + n);
+            std::sort(sorted.begin(), sorted.end());
+            sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
+            std::vector<char> seen(sorted.size(), 0);
+            for (int64_t i = 0; i < n; ++i) {
+                const size_t p = std::lower_bound(sorted.begin(), sorted.end(), values[i]) - sorted.begin();
+                if (!seen[p]) {
+                    seen[p] = 1;
+                    first.push_back(values[i]);
+                }
             }
         }
-    }
-    const std::vector<int32_t> ord = java_int_hashset_order(first);
-    std::copy(ord.begin(), ord.end(), out);
-    *n_out = (int64_t)ord.size();
-    return CMI_OK;
+        const std::vector<int32_t> ord = java_int_hashset_order(first);
+        std::copy(ord.begin(), ord.end(), out);
+        *n_out = (int64_t)ord.size();
+        return CMI_OK;
+    });
 }
 
-static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj,
-                                 const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su,
-                                 const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
-                                 int num_recs, int num_ignore, int strategy, double out[CMI_RANK_MEASURES],
-                                 int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count,
-                                 int32_t *top_items, double *top_scores);
-extern "C" int cmi_eval_rankings(cmi_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj,
-                                 const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su,
-                                 const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
-                                 int num_recs, int num_ignore, int strategy, double out[CMI_RANK_MEASURES],
-                                 int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count,
-                                 int32_t *top_items, double *top_scores) {
-    if (!h) return CMI_E_INVALID;
-    try { // exception barrier: the plan and the measures allocate per-range vectors on the host pool
-        return eval_rankings_impl(h, n_train, tu, tj, tctx, tr, n_test, su, sj, sctx, sr, bin_thold, num_recs, num_ignore, strategy, out, n_queries,
-                                  q_user, q_ctx, q_count, top_items, top_scores);
-    } catch (const std::exception &e) {
-        CMI_FAIL(h, CMI_E_HOST, "eval_rankings: host-side failure: %s", e.what());
-    } catch (...) {
-        CMI_FAIL(h, CMI_E_HOST, "eval_rankings: host-side failure (unknown exception)");
-    }
-}
-
-static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj,
-                                 const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su,
-                                 const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
-                                 int num_recs, int num_ignore, int strategy, double out[CMI_RANK_MEASURES],
-                                 int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count,
-                                 int32_t *top_items, double *top_scores) {
-    if (!h) return CMI_E_INVALID;
-    if (!out) CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: null output");
-    if (int rc = cmi_sync_table_from_arena(h)) return rc;
-    if (n_train < 0 || n_test < 0 || (n_train > 0 && (!tu || !tj || !tctx)) || (n_test > 0 && (!su || !sj || !sctx || !sr)))
-        CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: null tuple arrays");
-    if (num_recs < 1)
-        CMI_FAIL(h, CMI_E_INVALID,
-                 "eval_rankings: -topN must be >= 1 (with -topN <= 0 the reference's cut-off list holds a non-positive n: "
-                 "carskit/eval/Measures.java:13-16 throws for n<0)");
-    if (strategy != CMI_RANK_UCU && strategy != CMI_RANK_UC) CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: strategy must be CMI_RANK_UCU or CMI_RANK_UC");
-    const bool ext = h->model >= CMI_MODEL_SVDPP && h->model <= CMI_MODEL_CAMF_MCS;
-    const bool contextual = h->model != CMI_MODEL_BIASEDMF && h->model != CMI_MODEL_PMF && h->model != CMI_MODEL_SVDPP;
-    if ((contextual || ext) && !h->have_ratings)
-        CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: the context table comes from cmi_set_ratings; call it first");
-    auto check = [&](int64_t n, const int32_t *u, const int32_t *j, const int32_t *c, const char *what) -> int {
+int cmi::rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, int n_users, int n_items, int64_t ctx_bound, const RankEvalIO &io,
+                       const std::function<int()> &ready, const std::function<hipError_t(const RankPlan &, const RankBatchFn &)> &score) {
+    const RankTuples &train = io.train, &test = io.test;
+    if (!io.out) return abi_fail(err, CMI_E_INVALID, "%s: null output", what);
+    if (train.n < 0 || test.n < 0 || (train.n > 0 && (!train.u || !train.j || !train.ctx)) || (test.n > 0 && (!test.u || !test.j || !test.ctx || !test.r)))
+        return abi_fail(err, CMI_E_INVALID, "%s: null tuple arrays", what);
+    if (io.num_recs < 1)
+        return abi_fail(err, CMI_E_INVALID,
+                        "%s: -topN must be >= 1 (with -topN <= 0 the reference's cut-off list holds a non-positive n: "
+                        "carskit/eval/Measures.java:13-16 throws for n<0)", what);
+    if (io.strategy != CMI_RANK_UCU && io.strategy != CMI_RANK_UC)
+        return abi_fail(err, CMI_E_INVALID, "%s: strategy must be CMI_RANK_UCU or CMI_RANK_UC", what);
+    if (int rc = ready()) return rc;
+    auto check = [&](const RankTuples &tt, const char *which) -> int {
+        const int64_t n = tt.n;
+        const int32_t *u = tt.u, *j = tt.j, *c = tt.ctx;
         const int nt = host_threads(n);
         std::vector<int64_t> bad((size_t)nt, -1); // first offending tuple of every range
         parallel_ranges(n, nt, [&](int part, int64_t b, int64_t e) {
             for (int64_t t = b; t < e; ++t)
-                if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || c[t] < 0 || (contextual && c[t] >= h->n_ctx)) {
+                if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items || c[t] < 0 || c[t] >= ctx_bound) {
                     bad[(size_t)part] = t;
                     return;
                 }
         });
         for (int64_t t : bad) {
             if (t < 0) continue;
-            if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items)
-                CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: %s user/item id out of range at tuple %lld", what, (long long)t);
-            CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: %s context id %d out of range at tuple %lld", what, c[t], (long long)t);
+            if (u[t] < 0 || u[t] >= n_users || j[t] < 0 || j[t] >= n_items)
+                return abi_fail(err, CMI_E_INVALID, "%s: %s user/item id out of range at tuple %lld", what, which, (long long)t);
+            return abi_fail(err, CMI_E_INVALID, "%s: %s context id %d out of range at tuple %lld", what, which, c[t], (long long)t);
         }
         return CMI_OK;
     };
-    if (int rc = check(n_train, tu, tj, tctx, "train")) return rc;
-    if (int rc = check(n_test, su, sj, sctx, "test")) return rc;
-    CMI_HIP(h, hipSetDevice(h->device));
-    if (n_queries) *n_queries = 0;
+    if (int rc = check(train, "train")) return rc;
+    if (int rc = check(test, "test")) return rc;
+    if (io.n_queries) *io.n_queries = 0;
 
     const auto t_all = std::chrono::steady_clock::now();
-    RankWorkspace &ws = h->rank_ws;
     RankPlan &plan = ws.plan; // its arrays keep their capacity between evaluations
     // the same tuples as the previous evaluation (an early-stop loop evaluates after every epoch): the plan is kept.  Identity = sizes +
     // a 64-bit hash of the arrays' CONTENT (ranges on the host's cores: half a millisecond for 2.5 M tuples against 4 ms for the plan)
     RankWorkspace::PlanKey key;
-    key.n_train = n_train, key.n_test = n_test, key.n_users = h->n_users, key.n_items = h->n_items, key.bin_thold = bin_thold, key.num_ignore = num_ignore;
+    key.n_train = train.n, key.n_test = test.n, key.n_users = n_users, key.n_items = n_items, key.bin_thold = io.bin_thold, key.num_ignore = io.num_ignore;
     {
         struct Arr {
             const void *p;
             size_t bytes;
-        } arrs[] = {{tu, (size_t)n_train * 4}, {tj, (size_t)n_train * 4}, {tctx, (size_t)n_train * 4}, {tr, tr ? (size_t)n_train * 8 : 0},
-                    {su, (size_t)n_test * 4},  {sj, (size_t)n_test * 4},  {sctx, (size_t)n_test * 4},  {sr, (size_t)n_test * 8}};
+        } arrs[] = {{train.u, (size_t)train.n * 4}, {train.j, (size_t)train.n * 4}, {train.ctx, (size_t)train.n * 4},
+                    {train.r, train.r ? (size_t)train.n * 8 : 0}, {test.u, (size_t)test.n * 4}, {test.j, (size_t)test.n * 4},
+                    {test.ctx, (size_t)test.n * 4}, {test.r, (size_t)test.n * 8}};
         // one pass of the host's cores over all eight arrays as one run of 32-bit words; every thread keeps four independent chains
         // (the multiply's latency is the pace of one)
         uint64_t hsh = 0x9E3779B97F4A7C15ull;
@@ -1279,8 +1251,7 @@ static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, 
     }
     if (!(ws.plan_valid && ws.plan_key == key)) {
         ws.plan_valid = false;
-        rank_build_plan(h->n_users, h->n_items, RankTuples{n_train, tu, tj, tctx, tr}, RankTuples{n_test, su, sj, sctx, sr}, bin_thold,
-                        num_ignore, plan);
+        rank_build_plan(n_users, n_items, train, test, io.bin_thold, io.num_ignore, plan);
         ws.plan_key = key;
         for (const void *&r : ws.resident) r = nullptr;
         ws.plan_valid = true;
@@ -1293,11 +1264,8 @@ static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, 
     std::vector<int32_t> no_lists;
     const int32_t *top_count = nullptr;
     RankFolded folded;  // ucu: queries / users whose means are already taken
-    double *umeans = ws.umeans.need((size_t)std::min<int64_t>(nq, h->n_users) * N_MEAS + 1);
+    double *umeans = ws.umeans.need((size_t)std::min<int64_t>(nq, n_users) * N_MEAS + 1);
     if (nq > 0 && !plan.cand.empty()) {
-        const bool ic_used = h->state[CMI_STATE_IC_BIAS] != nullptr;
-        const int k_logical = ext ? h->k + (h->model == CMI_MODEL_SVDPP ? 1 : 0)
-                                  : h->k + 1 + (ic_used ? h->n_conds : 0); // [factors | 1 or itemBias | one-hot conditions or icBias row]
         const bool times = getenv("CMI_PLAN_TIMES") != nullptr;
         auto on_batch = [&](int64_t q0, int64_t q1) {
             const auto tb = std::chrono::steady_clock::now();
@@ -1309,20 +1277,62 @@ static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, 
                     if (on) fprintf(stderr, "rank batch of %lld queries: measures + user means %.3f ms on the host\n", (long long)n, ms_since(t0));
                 }
             } lap{times, tb, q1 - q0};
-            rank_measures_range(plan, num_recs, (const int32_t *)ws.h_top.p, (const double *)ws.h_score.p, (const int32_t *)ws.h_count.p, q0, q1,
-                                vals, q_user, q_ctx, q_count, top_items, top_scores);
+            rank_measures_range(plan, io.num_recs, (const int32_t *)ws.h_top.p, (const double *)ws.h_score.p, (const int32_t *)ws.h_count.p, q0,
+                                q1, vals, io.q_user, io.q_ctx, io.q_count, io.top_items, io.top_scores);
             // the batches arrive in query order: the users they complete are averaged here, behind the device
-            if (strategy == CMI_RANK_UCU) rank_fold_users(plan, (const int32_t *)ws.h_count.p, vals, umeans, folded, q1, q1 >= nq);
+            if (io.strategy == CMI_RANK_UCU) rank_fold_users(plan, (const int32_t *)ws.h_count.p, vals, umeans, folded, q1, q1 >= nq);
             else rank_sum_queries((const int32_t *)ws.h_count.p, vals, folded, q1); // uc: the serial sum over the queries, behind the device
         };
-        hipError_t e;
-        if (ext && h->f64) e = rank_run_device<double>(h->stream, ws, plan, ext_operands<double>(h, k_logical), bin_thold, num_recs, on_batch,
-                                                       &h->last_rank_ms, &h->last_rank_flops);
-        else if (ext) e = rank_run_device<float>(h->stream, ws, plan, ext_operands<float>(h, k_logical), bin_thold, num_recs, on_batch,
-                                                 &h->last_rank_ms, &h->last_rank_flops);
-        else if (h->f64) e = rank_run_device<double>(h->stream, ws, plan, mf_operands<double>(h, k_logical, contextual, ic_used), bin_thold,
-                                                     num_recs, on_batch, &h->last_rank_ms, &h->last_rank_flops);
-        else if (rank_split_usable(plan, num_recs, ws)) {
+        const hipError_t e = score(plan, on_batch);
+        if (e != hipSuccess) return abi_fail(err, CMI_E_HIP, "e failed: %s", hipGetErrorString(e));
+        top_count = (const int32_t *)ws.h_count.p;
+    } else {
+        no_lists.assign((size_t)nq, 0);
+        top_count = no_lists.data();
+        rank_measures_range(plan, io.num_recs, nullptr, nullptr, top_count, 0, nq, vals, io.q_user, io.q_ctx, io.q_count, io.top_items,
+                            io.top_scores);
+    }
+    const auto t_avg = std::chrono::steady_clock::now();
+    rank_average(plan, io.strategy, top_count, vals, umeans, folded, io.out);
+    if (getenv("CMI_PLAN_TIMES")) fprintf(stderr, "rank last batch's measures %.3f ms, averages %.3f ms\n", ws.host_ms[3], ms_since(t_avg));
+    ws.host_ms[3] += ms_since(t_avg);
+    ws.host_ms[4] = ms_since(t_all);
+    if (io.n_queries) *io.n_queries = (int64_t)plan.qu.size();
+    return CMI_OK;
+}
+
+extern "C" int cmi_eval_rankings(cmi_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj,
+                                 const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su,
+                                 const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
+                                 int num_recs, int num_ignore, int strategy, double out[CMI_RANK_MEASURES],
+                                 int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count,
+                                 int32_t *top_items, double *top_scores) {
+    if (!h) return CMI_E_INVALID;
+    return abi_barrier(h->err, "eval_rankings", [&] {
+        const bool ext = h->model >= CMI_MODEL_SVDPP && h->model <= CMI_MODEL_CAMF_MCS;
+        const bool contextual = h->model != CMI_MODEL_BIASEDMF && h->model != CMI_MODEL_PMF && h->model != CMI_MODEL_SVDPP;
+        auto ready = [&]() -> int {
+            if (int rc = cmi_sync_table_from_arena(h)) return rc;
+            if ((contextual || ext) && !h->have_ratings)
+                CMI_FAIL(h, CMI_E_INVALID, "eval_rankings: the context table comes from cmi_set_ratings; call it first");
+            CMI_HIP(h, hipSetDevice(h->device));
+            return CMI_OK;
+        };
+        auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
+            RankWorkspace &ws = h->rank_ws;
+            float *ms = &h->last_rank_ms;
+            double *flops = &h->last_rank_flops;
+            const bool ic_used = h->state[CMI_STATE_IC_BIAS] != nullptr;
+            const int k_logical = ext ? h->k + (h->model == CMI_MODEL_SVDPP ? 1 : 0)
+                                      : h->k + 1 + (ic_used ? h->n_conds : 0); // [factors | 1 or itemBias | one-hot conditions or icBias row]
+            if (ext && h->f64) return rank_run_device<double>(h->stream, ws, plan, ext_operands<double>(h, k_logical), bin_thold, num_recs, on_batch, ms, flops);
+            if (ext) return rank_run_device<float>(h->stream, ws, plan, ext_operands<float>(h, k_logical), bin_thold, num_recs, on_batch, ms, flops);
+            if (h->f64)
+                return rank_run_device<double>(h->stream, ws, plan, mf_operands<double>(h, k_logical, contextual, ic_used), bin_thold, num_recs,
+                                               on_batch, ms, flops);
+            if (!rank_split_usable(plan, num_recs, ws))
+                return rank_run_device<float>(h->stream, ws, plan, mf_operands<float>(h, k_logical, contextual, ic_used), bin_thold, num_recs,
+                                              on_batch, ms, flops);
             RankSplitArgs sa{};
             sa.P = (const float *)h->state[CMI_STATE_P];
             sa.Q = (const float *)h->state[CMI_STATE_Q];
@@ -1336,21 +1346,10 @@ static int eval_rankings_impl(cmi_handle h, int64_t n_train, const int32_t *tu, 
             sa.gm = h->hp.gm;
             sa.k = h->k;
             sa.n_conds = h->n_conds;
-            e = rank_run_device_split(h->stream, ws, plan, sa, bin_thold, num_recs, on_batch, &h->last_rank_ms, &h->last_rank_flops);
-        } else e = rank_run_device<float>(h->stream, ws, plan, mf_operands<float>(h, k_logical, contextual, ic_used), bin_thold, num_recs,
-                                          on_batch, &h->last_rank_ms, &h->last_rank_flops);
-        CMI_HIP(h, e);
-        top_count = (const int32_t *)ws.h_count.p;
-    } else {
-        no_lists.assign((size_t)nq, 0);
-        top_count = no_lists.data();
-        rank_measures_range(plan, num_recs, nullptr, nullptr, top_count, 0, nq, vals, q_user, q_ctx, q_count, top_items, top_scores);
-    }
-    const auto t_avg = std::chrono::steady_clock::now();
-    rank_average(plan, strategy, top_count, vals, umeans, folded, out);
-    if (getenv("CMI_PLAN_TIMES")) fprintf(stderr, "rank last batch's measures %.3f ms, averages %.3f ms\n", ws.host_ms[3], ms_since(t_avg));
-    ws.host_ms[3] += ms_since(t_avg);
-    ws.host_ms[4] = ms_since(t_all);
-    if (n_queries) *n_queries = (int64_t)plan.qu.size();
-    return CMI_OK;
+            return rank_run_device_split(h->stream, ws, plan, sa, bin_thold, num_recs, on_batch, ms, flops);
+        };
+        const RankEvalIO io{{n_train, tu, tj, tctx, tr}, {n_test, su, sj, sctx, sr}, bin_thold, num_recs, num_ignore, strategy, out, n_queries,
+                            q_user, q_ctx, q_count, top_items, top_scores};
+        return rank_evaluate(h->err, "eval_rankings", h->rank_ws, h->n_users, h->n_items, contextual ? h->n_ctx : INT64_MAX, io, ready, score);
+    });
 }

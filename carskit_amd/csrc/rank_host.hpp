@@ -121,7 +121,7 @@ void rank_measures_range(const RankPlan &plan, int num_recs, const int32_t *top_
                          double *top_scores);
 // averaged per strategy, in query order (Recommender.java:850-960).  ucu: rank_fold_users writes every user's mean over its contexts
 // into `umeans` (18 doubles per user, user order) and may run batch by batch behind the device for the users a batch completes;
-// rank_average folds what is left and sums over the users (umeans == nullptr: it allocates its own and folds everything).
+// rank_average folds what is left and sums over the users.
 struct RankFolded {
     int64_t q = 0, u = 0; // first query not folded yet; users folded so far
     // the serial sum over users (ucu) / queries (uc), advanced batch by batch behind the device in the order rank_average would take
@@ -134,5 +134,24 @@ void rank_sum_queries(const int32_t *top_count, const double *vals, RankFolded &
 void rank_fold_users(const RankPlan &plan, const int32_t *top_count, const double *vals, double *umeans, RankFolded &f, int64_t q_to, bool last);
 void rank_average(const RankPlan &plan, int strategy, const int32_t *top_count, const double *vals, double *umeans, RankFolded f,
                   double *out /*[21]*/);
+
+// the arguments of cmi_eval_rankings / cmi_fm_eval_rankings (include/carskit_mi355x.h)
+struct RankEvalIO {
+    RankTuples train, test;
+    double bin_thold;
+    int num_recs, num_ignore, strategy;
+    double *out;
+    int64_t *n_queries;
+    int32_t *q_user, *q_ctx, *q_count, *top_items;
+    double *top_scores;
+};
+using RankBatchFn = std::function<void(int64_t, int64_t)>;
+// Recommender.evalRankings around a model's scorer, shared by cmi_eval_rankings and cmi_fm_eval_rankings: the argument checks, the id
+// checks (context ids below ctx_bound; INT64_MAX: any non-negative id), the plan (kept while the tuples are the same, by content hash),
+// the measures and the users' means folded batch by batch behind the device, the averages.  `ready` checks the model's preconditions
+// and makes its device current; `score` runs the device loop over the plan and hands every batch of lists to on_batch.  Messages go
+// to `err`, prefixed "<what>: ".
+int rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, int n_users, int n_items, int64_t ctx_bound, const RankEvalIO &io,
+                  const std::function<int()> &ready, const std::function<hipError_t(const RankPlan &, const RankBatchFn &)> &score);
 
 } // namespace cmi

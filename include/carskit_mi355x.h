@@ -134,7 +134,8 @@ int cmi_measure_hbm(int device, int64_t bytes, double out[2]);
 int cmi_create(int model, int k, int n_users, int n_items, int n_conds, int device, unsigned flags,
                cmi_handle *out);
 int cmi_destroy(cmi_handle h);
-/* message of the last failure on this handle; h == NULL: last cmi_create failure on this thread */
+/* message of the last failure on this handle; h == NULL: the last failure on this thread of cmi_create or of a handle-less cmi_*
+ * function */
 const char *cmi_last_error(cmi_handle h);
 
 /* The training matrix: what `for (MatrixEntry me : trainMatrix)` yields, flattened
@@ -495,6 +496,8 @@ int cmi_dao_read(const char *path, cmi_dao_handle *out);
  * tables are those of the union (what rateDao.numUsers() etc. return afterwards); its matrix is the test matrix. */
 int cmi_dao_read_shared(const char *path, cmi_dao_handle train, cmi_dao_handle *out);
 int cmi_dao_destroy(cmi_dao_handle h);
+/* h == NULL: the last failure on this thread of cmi_dao_read(_shared) or of a handle-less data function (cmi_java_hashmap_order,
+ * cmi_transform*, cmi_validate_data_format) */
 const char *cmi_dao_last_error(cmi_dao_handle h);
 /* out: numUsers, numItems, numUserItems, numContexts, numConditions, numContextDims, numRatings (lines), matrix entries */
 int cmi_dao_counts(cmi_dao_handle h, int64_t out[8]);

@@ -157,3 +157,39 @@ def test_conflict_free_blocks_properties():
             assert len(set(u[b:e].tolist())) == e - b and len(set(j[b:e].tolist())) == e - b      # conflict-free
             if e < n and e - b < 64:                                                              # maximal: the next tuple conflicts
                 assert u[e] in set(u[b:e].tolist()) or j[e] in set(j[b:e].tolist())
+
+
+# A child that loads the library (and never initialises HIP), then caps its address space a little above its current size: the
+# host-only builders must then fail inside the library, and the failure has to come back as CMI_E_HOST, not as a C++ exception
+# that terminates the process.  (One host thread: a thread started under the cap could not get its thread-local block, which glibc
+# answers with an abort of its own.)
+_OOM_CHILD = r"""
+import resource
+import numpy as np
+from carskit_amd import capi
+rng = np.random.default_rng(7)
+n, nu, ni = 1 << 23, 1 << 20, 1 << 16
+u, j = rng.integers(0, nu, n, dtype=np.int32), rng.integers(0, ni, n, dtype=np.int32)
+c, r = np.zeros(n, np.int32), np.full(n, 4.0)
+capi.lib()
+vm = int(next(l for l in open("/proc/self/status") if l.startswith("VmSize:")).split()[1]) * 1024
+resource.setrlimit(resource.RLIMIT_AS, (vm + (64 << 20), resource.getrlimit(resource.RLIMIT_AS)[1]))
+for call in (lambda: capi.rank_plan(nu, ni, (u, j, c, r), (u, j, c, r)), lambda: capi.level_schedule(u, j, nu, ni)):
+    try:
+        call()
+    except capi.CmiError as e:
+        assert e.code == capi.E_HOST, e
+        msg = capi.lib().cmi_last_error(None).decode()
+        assert "host-side failure" in msg, msg
+    else:
+        raise AssertionError("no failure under the address-space cap")
+print("barrier ok")
+"""
+
+
+def test_host_failure_is_a_status_not_an_abort():
+    import subprocess
+    import sys
+    env = dict(os.environ, CMI_HOST_THREADS="1")
+    p = subprocess.run([sys.executable, "-c", _OOM_CHILD], capture_output=True, text=True, cwd=ROOT, env=env, timeout=300)
+    assert p.returncode == 0 and "barrier ok" in p.stdout, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])

@@ -189,6 +189,11 @@ def test_fm_rankings_match_oracle(k, strategy):
     res, lists = g.eval_rankings(_arrays(train), _arrays(test), bin_thold=-5.0, num_recs=10, strategy=strategy, with_lists=True)
     assert len(ref_lists) > 20    # (the reference's FM regularises with size*reg: its scores sit far below the rating scale)
     _assert_same(res, lists, ref, ref_lists, 1e-9, 1e-8)
+    # the same tuples again (the cached plan), then batches of 7 queries (users folded batch by batch): the same bits
+    again = lambda: g.eval_rankings(_arrays(train), _arrays(test), bin_thold=-5.0, num_recs=10, strategy=strategy, with_lists=True)
+    for r2, l2 in (again(), _with_env({"CMI_RANK_BATCH": "7"}, again)):
+        assert r2.keys() == res.keys() and all(np.float64(r2[m]).tobytes() == np.float64(res[m]).tobytes() for m in res), (r2, res)
+        assert l2 == lists
 
 
 def _with_env(env, fn):
