@@ -170,7 +170,10 @@ __global__ __launch_bounds__(256) void rank_gemm(const T *__restrict__ A, const 
 // 64x64 patch = 2x2 MFMA tiles (64 accumulator VGPRs).  A/B tiles go through LDS k-major ([k][row]) so that the MFMA
 // operand read (lane l: row l&31, k-slot l>>5) is one conflict-light ds_read_b32; the next tile's global loads are in
 // flight while the current one is multiplied (register double-buffer, two LDS buffers, one barrier per BK step).
-// Operands are padded by the builders: kp_pad % 32 == 0 (zero columns), row counts rounded up to 128.
+// Operands are padded by the builders: kp_pad % RG_BK == 0 (the host rounds the operand length up to 16; zero columns), row counts
+// rounded up to 128.
+// tests/test_gpu_ranking_f32_anchor.py holds this kernel to the fp64 oracle at 1 to 16 steps of the k loop: bit for bit on inputs whose
+// fp32 sums are exact, and within the forward error bound of an fp32 sum on arbitrary ones.
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
