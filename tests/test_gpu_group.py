@@ -28,9 +28,9 @@ def _problem(model, k, seed=5, n_users=600, n_items=150, n=12000):
     return train, test, gm, state
 
 
-def _group(model, k, train, gm, state, shards, flags=0):
+def _group(model, k, train, gm, state, shards, flags=0, regs=None):
     g = capi.Group(model, k, train.n_users, train.n_items, train.n_conds, shards, devices=[0] * shards, flags=flags)
-    g.set_hparams(util.REG, util.REG, util.REG, util.REGC, gm)
+    g.set_hparams(*(regs or (util.REG, util.REG, util.REG, util.REGC)), gm)
     u, j, ctx, r = util.tuples_for(model, train)
     g.set_ratings(u, j, ctx, r, train.ctx_ptr, train.ctx_conds)
     g.set_states(state)
@@ -149,18 +149,18 @@ def test_group_of_one_is_the_plain_instance_and_matches_the_oracle():
     assert abs(eo["RMSE"] - eg["RMSE"]) <= 1e-5 and abs(eo["MAE"] - eg["MAE"]) <= 1e-5
 
 
-def test_group_fp64_shards_equal_merged_oracles():
+def check_fp64_shards_equal_merged_oracles(regs):
     """W = 2 in fp64: every shard is an order-exact pass over its users, so the merged model equals two CPU oracles (one per shard)
     merged the same way on the host, to fp64 rounding -- the multi-GPU algorithm checked against the reference's arithmetic."""
     model, k, world = "CAMF_CI", 32, 2
     train, test, gm, state32 = _problem(model, k, seed=13, n_users=300, n_items=90, n=6000)
     state = {n: a.astype(np.float64) for n, a in state32.items()}
-    g = _group(model, k, train, gm, state, world, flags=capi.FLAG_STATE_F64)
+    g = _group(model, k, train, gm, state, world, flags=capi.FLAG_STATE_F64, regs=regs)
     oracles, cuts = [], []
     for rank in range(world):
         shard, (lo, hi) = cdist.shard_by_user(train, rank, world)
         st = {n: (a[lo:hi] if n in ("P", "userBias") else a) for n, a in state.items()}
-        oracles.append(util.c_oracle(model, shard, k, st, gm))
+        oracles.append(util.c_oracle(model, shard, k, st, gm, *regs))
         cuts.append((lo, hi))
     for _ in range(3):
         lg = g.train_epoch(util.LR)
@@ -175,6 +175,10 @@ def test_group_fp64_shards_equal_merged_oracles():
     np.testing.assert_allclose(got["Q"].ravel(), oracles[0].state["Q"].ravel(), rtol=0, atol=1e-11)
     np.testing.assert_allclose(got["icBias"].ravel(), oracles[0].state["icBias"].ravel(), rtol=0, atol=1e-11)
     np.testing.assert_allclose(got["P"].ravel(), np.concatenate([o.state["P"].ravel() for o in oracles]), rtol=0, atol=1e-11)
+
+
+def test_group_fp64_shards_equal_merged_oracles():
+    check_fp64_shards_equal_merged_oracles((util.REG, util.REG, util.REG, util.REGC))
 
 
 def test_group_rejects_serial_chain_models_and_bad_calls():

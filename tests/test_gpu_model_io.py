@@ -24,7 +24,7 @@ def test_resume_equals_continuous_training(model, flags, tmp_path):
     saved = b.get_states()
     b.close()
     _, c = make_pair(model, data, 64, flags, seed=99)                    # ... a fresh handle with a DIFFERENT initial model
-    c.set_hparams(0.5, 0.5, 0.5, 0.5, 1.0)                               # and wrong hyper-parameters: the file restores both
+    c.set_hparams(0.5, 0.25, 0.125, 0.0625, 1.0)                         # and wrong hyper-parameters, each its own number: the file restores all
     lr, last, done = c.load_model(path)
     assert done == 3 and last == lb1[-1]
     for name, arr in c.get_states().items():                            # all containers, context tables included

@@ -20,22 +20,7 @@ pytestmark = pytest.mark.gpu
 OWNER, F64 = capi.FLAG_SCHED_OWNER, capi.FLAG_STATE_F64
 LEVEL_MODELS = [m for m in util.MODELS if m != "CAMF_C"]
 
-
-def _env(fn, **kv):
-    old = {k: os.environ.get(k) for k in kv}
-    for k, v in kv.items():
-        if v is None:
-            os.environ.pop(k, None)
-        else:
-            os.environ[k] = str(v)
-    try:
-        return fn()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+_env = util.with_env
 
 
 def _run(model, data, k, flags, hub, waves, epochs=3, loss_tol=1e-10, exact=False, atol=1e-11, team=None):

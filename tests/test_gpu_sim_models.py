@@ -14,47 +14,19 @@ from tests import util
 pytestmark = pytest.mark.gpu
 F64, SERIAL, STRICT = capi.FLAG_STATE_F64, capi.FLAG_SCHED_SERIAL, capi.FLAG_STRICT
 MODELS = ["SVD++", "CAMF_ICS", "CAMF_LCS", "CAMF_MCS"]
-NUM_F = 7
+NUM_F = util.SIM_NUM_F
+
+_data, _state, make_oracle = util.sim_data, util.sim_state, util.sim_oracle
 
 
-def _data(seed=81, n=1500):
-    """every dimension's last condition plays its ':na' condition (EmptyContextConditions, DataDAO.java:213-214)"""
-    d = util.small_data(n_users=70, n_items=30, n_dims=3, conds_per_dim=4, n=n, seed=seed)
-    empty = np.array([dim * 4 + 3 for dim in range(3)], dtype=np.int32)
-    return d, empty
-
-
-def _state(model, d, k, seed=7):
-    rng = np.random.default_rng(seed)
-    st = {"P": rng.random((d.n_users, k)), "Q": rng.random((d.n_items, k))}      # isRankingPred: P.init(), Q.init() (CAMF_ICS.java:40-46)
-    if model == "SVD++":
-        st = {"P": 0.1 * rng.standard_normal((d.n_users, k)), "Q": 0.1 * rng.standard_normal((d.n_items, k)),
-              "userBias": 0.1 * rng.standard_normal(d.n_users), "itemBias": 0.1 * rng.standard_normal(d.n_items),
-              "Y": 0.1 * rng.standard_normal((d.n_items, k))}
-    elif model == "CAMF_ICS":
-        st["P"] *= 0.3
-        st["ccMatrix"] = np.ones((d.n_conds, d.n_conds))
-    elif model == "CAMF_LCS":
-        st["P"] *= 0.3
-        st["cfMatrix"] = rng.random((d.n_conds, NUM_F))
-    else:
-        st["P"] *= 0.02      # small e * dot; at LR the positions still reach a bound within the first epoch
-        st["cVector"] = (0.2 + 0.6 * rng.random(d.n_conds)) / np.sqrt(d.n_dims)
-    return st
-
-
-def make(model, d, empty, k, flags, lr_state_seed=7):
+def make(model, d, empty, k, flags, lr_state_seed=7, regs=None):
+    regs = regs or (util.REG, util.REG, util.REG, util.REGC)
     st = _state(model, d, k, lr_state_seed)
     gm = oracle_c.global_mean(d.r)
-    if model == "SVD++":
-        u, j, r = synth.to_2d(d)
-        ctx = None
-    else:
-        u, j, ctx, r = d.u, d.j, d.ctx, d.r
-    orc = oracle_c.SimOracle(model, k, d.n_users, d.n_items, d.n_conds, u, j, ctx, r, d.ctx_ptr, d.ctx_conds, empty,
-                             {n_: a.copy() for n_, a in st.items()}, gm, util.REG, util.REG, util.REG, util.REGC, n_ctx_dims=d.n_dims)
+    u, j, ctx, r = util.sim_tuples(model, d)
+    orc = make_oracle(model, d, empty, k, lr_state_seed, regs)
     inst = capi.Instance(model, k, d.n_users, d.n_items, d.n_conds, flags=flags | SERIAL)
-    inst.set_hparams(util.REG, util.REG, util.REG, util.REGC, gm)
+    inst.set_hparams(*regs, gm)
     inst.set_sim_params(NUM_F, d.n_dims, empty)
     if model == "SVD++":
         inst.set_ratings(u, j, None, r)

@@ -15,37 +15,19 @@ from tests import util
 pytestmark = pytest.mark.gpu
 F64, SERIAL = capi.FLAG_STATE_F64, capi.FLAG_SCHED_SERIAL
 
-
-def _state(nu, ni, k, seed=3):
-    rng = np.random.default_rng(seed)
-    return {"P": 0.1 * rng.standard_normal((nu, k)), "Q": 0.1 * rng.standard_normal((ni, k)), "userBias": 0.1 * rng.standard_normal(nu),
-            "itemBias": 0.1 * rng.standard_normal(ni), "Y": 0.1 * rng.standard_normal((ni, k))}
+_state, _oracle, _matrix = util.svdpp_state, util.svdpp_oracle, util.svdpp_matrix
 
 
-def _pair(u, j, r, nu, ni, k, flags):
+def _pair(u, j, r, nu, ni, k, flags, regs=None):
+    regs = regs or (util.REG, util.REG, util.REG, util.REGC)
     st = _state(nu, ni, k)
     gm = float(r.mean())
-    z = np.zeros(1, np.int32)
-    orc = oracle_c.SimOracle("SVD++", k, nu, ni, 1, u, j, None, r, z, np.zeros(0, np.int32), np.zeros(0, np.int32),
-                             {n: a.copy() for n, a in st.items()}, gm, util.REG, util.REG, util.REG, util.REGC, n_ctx_dims=1)
+    orc = _oracle(u, j, r, nu, ni, k, regs)
     inst = capi.Instance("SVD++", k, nu, ni, 1, flags=flags | SERIAL)
-    inst.set_hparams(util.REG, util.REG, util.REG, util.REGC, gm)
+    inst.set_hparams(*regs, gm)
     inst.set_ratings(u, j, None, r)
     inst.set_states(st)
     return orc, inst
-
-
-def _matrix(nu, ni, per_user, seed, heavy=()):
-    """a 2-D train matrix in row-major order; users in `heavy` rate `heavy[u]` items"""
-    rng = np.random.default_rng(seed)
-    u, j = [], []
-    for x in range(nu):
-        m = heavy[x] if x in heavy else int(rng.integers(1, per_user + 1))
-        items = np.sort(rng.choice(ni, size=min(m, ni), replace=False))
-        u += [x] * len(items)
-        j += items.tolist()
-    r = rng.integers(1, 6, size=len(u)).astype(np.float64)
-    return np.array(u, np.int32), np.array(j, np.int32), r
 
 
 def _check(orc, inst, flags, epochs=3, lr=util.LR / 4):
