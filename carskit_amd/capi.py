@@ -169,6 +169,14 @@ SYMBOLS = [
     ("cmi_knn_get_similarity", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
     ("cmi_knn_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_knn_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_slope_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_slope_destroy", C.c_int, [_vp]),
+    ("cmi_slope_last_error", C.c_char_p, [_vp]),
+    ("cmi_slope_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_slope_build", C.c_int, [_vp]),
+    ("cmi_slope_get_deviation", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
+    ("cmi_slope_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _dbl, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_slope_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -956,4 +964,45 @@ class KNNInstance(_Handle):
     def last_build_ms(self):
         ms = C.c_float()
         self._chk(self.L.cmi_knn_last_build_ms(self.h, C.byref(ms)))
+        return ms.value
+
+
+class SlopeOneInstance(_Handle):
+    """The reference's SlopeOne on one GPU (a `cmi_slope_handle`)."""
+
+    _api = ("cmi_slope_create", "cmi_slope_destroy", "cmi_slope_last_error")
+
+    def __init__(self, n_users, n_items, device=0, flags=0):
+        self.n_users, self.n_items = n_users, n_items
+        super().__init__(n_users, n_items, device, flags)
+
+    def set_ratings(self, u, i, r):
+        """the 2-D train matrix as cells (user, item, value)"""
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        i = np.ascontiguousarray(i, dtype=np.int32)
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        self._chk(self.L.cmi_slope_set_ratings(self.h, len(r), _p(u), _p(i), _p(r)))
+
+    def build(self):
+        self._chk(self.L.cmi_slope_build(self.h))
+
+    def deviation(self, row0=0, nrows=None):
+        """rows of the dense deviation (fp64) and cardinality (int32) matrices: (dev, card)"""
+        nrows = self.n_items - row0 if nrows is None else nrows
+        dev = np.empty((max(nrows, 0), self.n_items))
+        card = np.empty((max(nrows, 0), self.n_items), np.int32)
+        self._chk(self.L.cmi_slope_get_deviation(self.h, int(row0), int(nrows), _p(dev), _p(card)))
+        return dev, card
+
+    def predict(self, u, j, global_mean, bound=False, lo=1.0, hi=5.0):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_slope_predict_batch(self.h, len(u), _p(u), _p(j), float(global_mean), 1 if bound else 0, float(lo),
+                                                 float(hi), _p(out)))
+        return out
+
+    def last_build_ms(self):
+        ms = C.c_float()
+        self._chk(self.L.cmi_slope_last_build_ms(self.h, C.byref(ms)))
         return ms.value

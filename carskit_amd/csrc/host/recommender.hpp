@@ -695,6 +695,40 @@ class UserKNN : public KNNRecommender {
         : KNNRecommender(CMI_KNN_USER, "UserKNN", tr, te, fold, c, log) {}
 };
 
+// src/carskit/alg/baseline/cf/SlopeOne.java: the deviation and cardinality matrices of the 2-D train matrix (buildModel) and
+// predict(u, j), rating prediction only; evaluation through the generic evalRatings recipe on bounded predictions.  No parameters.
+class SlopeOne : public IterativeRecommender {
+  public:
+    SlopeOne(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : IterativeRecommender(-1, "SlopeOne", false, tr, te, fold, c, log) {}
+    ~SlopeOne() override {
+        if (slope_) cmi_slope_destroy(slope_);
+    }
+    void initModel() override {}
+    void buildModel() override {
+        if (cmi_slope_create(trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &slope_) != CMI_OK)
+            throw std::runtime_error(std::string("cmi_slope_create: ") + cmi_slope_last_error(nullptr));
+        std::vector<int32_t> u2, j2;
+        std::vector<double> r2;
+        to2d(trainMatrix, u2, j2, r2);
+        scheck(cmi_slope_set_ratings(slope_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), "cmi_slope_set_ratings");
+        scheck(cmi_slope_build(slope_), "cmi_slope_build");
+    }
+    Measures evalRatings() override { // Recommender.java:504-594 (numeric part)
+        std::vector<double> pred((size_t)testMatrix.n());
+        scheck(cmi_slope_predict_batch(slope_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), globalMean, 1,
+                                       trainMatrix.min_rate, trainMatrix.max_rate, pred.data()), "cmi_slope_predict_batch");
+        return evalPredictions(pred);
+    }
+    void saveModel() override {} // the reference's SlopeOne inherits Recommender's empty saveModel()
+
+  private:
+    void scheck(int rc, const char *what) {
+        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_slope_last_error(slope_));
+    }
+    cmi_slope_handle slope_ = nullptr;
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -712,7 +746,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "camf_mcs") return std::unique_ptr<IterativeRecommender>(new CAMF_MCS(tr, te, fold, c, log));   // CARSKit.java:712
     if (n == "itemknn") return std::unique_ptr<IterativeRecommender>(new ItemKNN(tr, te, fold, c, log));
     if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn)");
+    if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn, slopeone)");
 }
 
 } // namespace carskit

@@ -616,6 +616,29 @@ int cmi_knn_predict_batch(cmi_knn_handle h, int64_t n, const int32_t *u, const i
                           double lo, double hi, double *out);
 int cmi_knn_last_build_ms(cmi_knn_handle h, float *ms);
 
+/* ---- SlopeOne (src/carskit/alg/baseline/cf/SlopeOne.java; slopeone_api.cpp, slopeone_kernels.hip) ----------------------------
+ * Rating prediction of the third memory-based baseline over the same 2-D train matrix as ItemKNN.  cmi_slope_build computes
+ * SlopeOne.buildModel on the device into two dense n_items x n_items matrices: dev[i][j] is the sum over the users who rated both
+ * items, in ascending user order from +0.0 in fp64, of r_ui - r_uj, divided by their count card[i][j] (fp64 and int32: 12 bytes a
+ * cell); cells without a common user, the diagonal included, are 0.0 / 0.  cmi_slope_predict_batch is the model's predict(u, j):
+ * over the user's items i != j with card[j][i] > 0, in ascending item order, preds += (dev[j][i] + r_ui) * card[j][i] and
+ * cards += card[j][i]; preds / cards, or global_mean when nothing was added.  Bit-exact to the reference.  No CPU fallback: without
+ * a device cmi_slope_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_slope_instance *cmi_slope_handle;
+int cmi_slope_create(int n_users, int n_items, int device, unsigned flags, cmi_slope_handle *out);
+int cmi_slope_destroy(cmi_slope_handle h);
+const char *cmi_slope_last_error(cmi_slope_handle h);
+/* the 2-D train matrix as n cells; a duplicate (u, i) or an id out of range -> CMI_E_INVALID; n >= 2^31 -> CMI_E_UNSUPPORTED */
+int cmi_slope_set_ratings(cmi_slope_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* The two n x n matrices must fit in free device memory, else CMI_E_INVALID with the bytes needed (nothing is built) */
+int cmi_slope_build(cmi_slope_handle h);
+/* rows [row0, row0 + nrows) of the deviation and the cardinality matrix, dense; either destination may be NULL */
+int cmi_slope_get_deviation(cmi_slope_handle h, int32_t row0, int32_t nrows, double *dev, int32_t *card);
+/* predict(u, j) of n tuples; bound: clamp to [lo, hi] as Recommender.predict(u, j, c, true).  A user's list may be any length */
+int cmi_slope_predict_batch(cmi_slope_handle h, int64_t n, const int32_t *u, const int32_t *j, double global_mean, int bound,
+                            double lo, double hi, double *out);
+int cmi_slope_last_build_ms(cmi_slope_handle h, float *ms);
+
 #ifdef __cplusplus
 }
 #endif
