@@ -165,10 +165,11 @@ def source_dao(ref, vm, prob):
 
 
 def run_model(ref, model, prob, k, iters, seed, lrate=0.02, reg=1e-4, reg_c=1e-3, bold=True, test_cells=None, rank=None, drop_in=None,
-              init_override=None, early_stop=None):
+              init_override=None, early_stop=None, min_rate=1.0, max_rate=5.0):
     """drop_in: (path of a *_GPU.java drop-in class of THIS repository, {simple class name: This / natives object}, make(vm) that fills
     that map) -- the drop-in is put in front of the reference's class chain, so its buildModel() override runs
-    (oracle/check_java_binding.py); init_override: the initial containers of a minted case instead of fresh draws"""
+    (oracle/check_java_binding.py); init_override: the initial containers of a minted case instead of fresh draws; min_rate / max_rate:
+    the `minRate` / `maxRate` fields evalRatings() bounds and rounds with (oracle/mint_reference_evalratings_scales.py)"""
     vm = VM([os.path.join(ref, "lib", "librec-v1.4-alpha.jar"), os.path.join(ref, "lib", "happy.coding.utils-1.2.6.jar")] if rank else
             os.path.join(ref, "lib", "librec-v1.4-alpha.jar"))
     rng = np.random.default_rng(seed)
@@ -219,7 +220,7 @@ def run_model(ref, model, prob, k, iters, seed, lrate=0.02, reg=1e-4, reg_c=1e-3
               "numConditions": nc, "lRate": float(f32(lrate)), "initLRate": f32(lrate), "maxLRate": f32(-1.0), "decay": f32(-1.0),
               "isBoldDriver": bool(bold), "regU": f32(reg), "regI": f32(reg), "regB": f32(reg), "regC": f32(reg_c),
               "globalMean": gm, "loss": 0.0, "last_loss": 0.0, "measure": 0.0, "last_measure": 0.0, "earlyStopMeasure": None,
-              "verbose": False, "isResultsOut": False, "minRate": 1.0, "maxRate": 5.0, "isUserSplitting": False, "isItemSplitting": False,
+              "verbose": False, "isResultsOut": False, "minRate": float(min_rate), "maxRate": float(max_rate), "isUserSplitting": False, "isItemSplitting": False,
               "algoName": model, "foldInfo": "", "trainMatrix": train_ctx, "train": train2 if two_d else None,
               "rateDao": RateDao(prob["ui_user"], prob["ui_item"], prob["ctx_keys"]), "__enums__": ("Measure",)})
     # EmptyContextConditions: one ":na" condition per dimension, in header order (ContextRecommender.java:43) -- here the first of each
