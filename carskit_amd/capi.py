@@ -924,23 +924,46 @@ def knn_measure(name):
     return lib().cmi_knn_measure(name.encode())
 
 
-class KNNInstance(_Handle):
-    """The reference's ItemKNN (kind="item") or UserKNN (kind="user") on one GPU (a `cmi_knn_handle`)."""
+class _PairModel(_Handle):
+    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*)."""
 
-    _api = ("cmi_knn_create", "cmi_knn_destroy", "cmi_knn_last_error")
+    _prefix = ""
 
-    def __init__(self, kind, n_users, n_items, device=0, flags=0):
-        k = {"user": KNN_USER, "item": KNN_ITEM}.get(kind, kind)
-        self.kind, self.n_users, self.n_items = k, n_users, n_items
-        self.n = n_items if k == KNN_ITEM else n_users
-        super().__init__(k if isinstance(k, int) else -1, n_users, n_items, device, flags)
+    def _fn(self, name):
+        return getattr(self.L, self._prefix + name)
 
     def set_ratings(self, u, i, r):
         """the 2-D train matrix as cells (user, item, value)"""
         u = np.ascontiguousarray(u, dtype=np.int32)
         i = np.ascontiguousarray(i, dtype=np.int32)
         r = np.ascontiguousarray(r, dtype=np.float64)
-        self._chk(self.L.cmi_knn_set_ratings(self.h, len(r), _p(u), _p(i), _p(r)))
+        self._chk(self._fn("_set_ratings")(self.h, len(r), _p(u), _p(i), _p(r)))
+
+    def _predict(self, u, j, *mid, global_mean, bound, lo, hi):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self._fn("_predict_batch")(self.h, len(u), _p(u), _p(j), *mid, float(global_mean), 1 if bound else 0, float(lo),
+                                             float(hi), _p(out)))
+        return out
+
+    def last_build_ms(self):
+        ms = C.c_float()
+        self._chk(self._fn("_last_build_ms")(self.h, C.byref(ms)))
+        return ms.value
+
+
+class KNNInstance(_PairModel):
+    """The reference's ItemKNN (kind="item") or UserKNN (kind="user") on one GPU (a `cmi_knn_handle`)."""
+
+    _api = ("cmi_knn_create", "cmi_knn_destroy", "cmi_knn_last_error")
+    _prefix = "cmi_knn"
+
+    def __init__(self, kind, n_users, n_items, device=0, flags=0):
+        k = {"user": KNN_USER, "item": KNN_ITEM}.get(kind, kind)
+        self.kind, self.n_users, self.n_items = k, n_users, n_items
+        self.n = n_items if k == KNN_ITEM else n_users
+        super().__init__(k if isinstance(k, int) else -1, n_users, n_items, device, flags)
 
     def build(self, measure="pcc", shrinkage=-1, min_rate=1.0, max_rate=5.0):
         m = knn_measure(measure) if isinstance(measure, str) else int(measure)
@@ -954,34 +977,18 @@ class KNNInstance(_Handle):
         return out
 
     def predict(self, u, j, knn, global_mean, bound=False, lo=1.0, hi=5.0):
-        u = np.ascontiguousarray(u, dtype=np.int32)
-        j = np.ascontiguousarray(j, dtype=np.int32)
-        out = np.empty(len(u))
-        self._chk(self.L.cmi_knn_predict_batch(self.h, len(u), _p(u), _p(j), int(knn), float(global_mean), 1 if bound else 0,
-                                               float(lo), float(hi), _p(out)))
-        return out
-
-    def last_build_ms(self):
-        ms = C.c_float()
-        self._chk(self.L.cmi_knn_last_build_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._predict(u, j, int(knn), global_mean=global_mean, bound=bound, lo=lo, hi=hi)
 
 
-class SlopeOneInstance(_Handle):
+class SlopeOneInstance(_PairModel):
     """The reference's SlopeOne on one GPU (a `cmi_slope_handle`)."""
 
     _api = ("cmi_slope_create", "cmi_slope_destroy", "cmi_slope_last_error")
+    _prefix = "cmi_slope"
 
     def __init__(self, n_users, n_items, device=0, flags=0):
         self.n_users, self.n_items = n_users, n_items
         super().__init__(n_users, n_items, device, flags)
-
-    def set_ratings(self, u, i, r):
-        """the 2-D train matrix as cells (user, item, value)"""
-        u = np.ascontiguousarray(u, dtype=np.int32)
-        i = np.ascontiguousarray(i, dtype=np.int32)
-        r = np.ascontiguousarray(r, dtype=np.float64)
-        self._chk(self.L.cmi_slope_set_ratings(self.h, len(r), _p(u), _p(i), _p(r)))
 
     def build(self):
         self._chk(self.L.cmi_slope_build(self.h))
@@ -995,14 +1002,4 @@ class SlopeOneInstance(_Handle):
         return dev, card
 
     def predict(self, u, j, global_mean, bound=False, lo=1.0, hi=5.0):
-        u = np.ascontiguousarray(u, dtype=np.int32)
-        j = np.ascontiguousarray(j, dtype=np.int32)
-        out = np.empty(len(u))
-        self._chk(self.L.cmi_slope_predict_batch(self.h, len(u), _p(u), _p(j), float(global_mean), 1 if bound else 0, float(lo),
-                                                 float(hi), _p(out)))
-        return out
-
-    def last_build_ms(self):
-        ms = C.c_float()
-        self._chk(self.L.cmi_slope_last_build_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._predict(u, j, global_mean=global_mean, bound=bound, lo=lo, hi=hi)

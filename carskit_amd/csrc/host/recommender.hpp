@@ -644,45 +644,64 @@ class FM : public IterativeRecommender {
     cmi_fm_handle fm_ = nullptr;
 };
 
-// src/carskit/alg/baseline/cf/{ItemKNN,UserKNN}.java: the similarity matrix of the 2-D train matrix (buildCorrs) and the
-// neighbourhood predict(u, j), rating prediction only; evaluation through the generic evalRatings recipe on bounded predictions.
-// num.neighbors (default 20) and similarity (default PCC) as Recommender.java:244-245 reads them; num.shrinkage as correlation() reads it
-// (Recommender.java:426: cf.getInt(key) = Integer.parseInt(value), so a missing or non-integer value fails the model there and here).
-class KNNRecommender : public IterativeRecommender {
+// What ItemKNN, UserKNN and SlopeOne share: a model of the 2-D train matrix behind a handle H of the C ABI, rating prediction only,
+// nothing to initialise and nothing to save (the reference's saveModel() of these models is empty); evaluation through the generic
+// evalRatings recipe on bounded predictions.
+template <typename H, int (*destroy)(H), const char *(*last_error)(H),
+          int (*set_ratings)(H, int64_t, const int32_t *, const int32_t *, const double *)>
+class PairRecommender : public IterativeRecommender {
   public:
-    KNNRecommender(int kind, const char *name, const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log)
-        : IterativeRecommender(-1, name, false, tr, te, fold, c, log), kind_(kind) {}
-    ~KNNRecommender() override {
-        if (knn_) cmi_knn_destroy(knn_);
+    PairRecommender(const char *name, const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log)
+        : IterativeRecommender(-1, name, false, tr, te, fold, c, log) {}
+    ~PairRecommender() override {
+        if (h_) destroy(h_);
     }
     void initModel() override {}
+    Measures evalRatings() override { // Recommender.java:504-594 (numeric part); NaN predictions are skipped
+        std::vector<double> pred((size_t)testMatrix.n());
+        predictBounded(pred.data());
+        return evalPredictions(pred);
+    }
+    void saveModel() override {}
+
+  protected:
+    virtual void predictBounded(double *pred) = 0; // the test tuples, bounded to the train matrix's rating scale
+    void setRatings(const char *what) {
+        std::vector<int32_t> u2, j2;
+        std::vector<double> r2;
+        to2d(trainMatrix, u2, j2, r2);
+        check(set_ratings(h_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), what);
+    }
+    void check(int rc, const char *what) { // (a failed create leaves h_ null: the thread's message)
+        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + last_error(h_));
+    }
+    H h_ = nullptr;
+};
+
+// src/carskit/alg/baseline/cf/{ItemKNN,UserKNN}.java: the similarity matrix of the 2-D train matrix (buildCorrs) and the
+// neighbourhood predict(u, j).
+// num.neighbors (default 20) and similarity (default PCC) as Recommender.java:244-245 reads them; num.shrinkage as correlation() reads it
+// (Recommender.java:426: cf.getInt(key) = Integer.parseInt(value), so a missing or non-integer value fails the model there and here).
+class KNNRecommender : public PairRecommender<cmi_knn_handle, cmi_knn_destroy, cmi_knn_last_error, cmi_knn_set_ratings> {
+  public:
+    KNNRecommender(int kind, const char *name, const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log)
+        : PairRecommender(name, tr, te, fold, c, log), kind_(kind) {}
     void buildModel() override {
         if (!conf_.knnShrinkageSet) // the reference: Integer.parseInt(null) -> "null", Integer.parseInt("x") -> For input string: "x"
             throw std::runtime_error(!conf_.knnShrinkagePresent ? std::string("null (num.shrinkage is not set)")
                                                                      : "For input string: \"" + conf_.knnShrinkageRaw + "\" (num.shrinkage)");
-        if (cmi_knn_create(kind_, trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &knn_) != CMI_OK)
-            throw std::runtime_error(std::string("cmi_knn_create: ") + cmi_knn_last_error(nullptr));
-        std::vector<int32_t> u2, j2;
-        std::vector<double> r2;
-        to2d(trainMatrix, u2, j2, r2);
-        kcheck(cmi_knn_set_ratings(knn_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), "cmi_knn_set_ratings");
-        kcheck(cmi_knn_build(knn_, cmi_knn_measure(conf_.similarity.c_str()), conf_.knnShrinkage, trainMatrix.min_rate,
-                             trainMatrix.max_rate), "cmi_knn_build");
+        check(cmi_knn_create(kind_, trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &h_), "cmi_knn_create");
+        setRatings("cmi_knn_set_ratings");
+        check(cmi_knn_build(h_, cmi_knn_measure(conf_.similarity.c_str()), conf_.knnShrinkage, trainMatrix.min_rate,
+                            trainMatrix.max_rate), "cmi_knn_build");
     }
-    Measures evalRatings() override { // Recommender.java:504-594 (numeric part); NaN predictions are skipped
-        std::vector<double> pred((size_t)testMatrix.n());
-        kcheck(cmi_knn_predict_batch(knn_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), conf_.knn, globalMean, 1,
-                                     trainMatrix.min_rate, trainMatrix.max_rate, pred.data()), "cmi_knn_predict_batch");
-        return evalPredictions(pred);
-    }
-    void saveModel() override {} // the reference's saveModel() of these two models is empty
 
   private:
-    void kcheck(int rc, const char *what) {
-        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_knn_last_error(knn_));
+    void predictBounded(double *pred) override {
+        check(cmi_knn_predict_batch(h_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), conf_.knn, globalMean, 1,
+                                    trainMatrix.min_rate, trainMatrix.max_rate, pred), "cmi_knn_predict_batch");
     }
     int kind_;
-    cmi_knn_handle knn_ = nullptr;
 };
 class ItemKNN : public KNNRecommender {
   public:
@@ -696,37 +715,22 @@ class UserKNN : public KNNRecommender {
 };
 
 // src/carskit/alg/baseline/cf/SlopeOne.java: the deviation and cardinality matrices of the 2-D train matrix (buildModel) and
-// predict(u, j), rating prediction only; evaluation through the generic evalRatings recipe on bounded predictions.  No parameters.
-class SlopeOne : public IterativeRecommender {
+// predict(u, j).  No parameters.
+class SlopeOne : public PairRecommender<cmi_slope_handle, cmi_slope_destroy, cmi_slope_last_error, cmi_slope_set_ratings> {
   public:
     SlopeOne(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
-        : IterativeRecommender(-1, "SlopeOne", false, tr, te, fold, c, log) {}
-    ~SlopeOne() override {
-        if (slope_) cmi_slope_destroy(slope_);
-    }
-    void initModel() override {}
+        : PairRecommender("SlopeOne", tr, te, fold, c, log) {}
     void buildModel() override {
-        if (cmi_slope_create(trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &slope_) != CMI_OK)
-            throw std::runtime_error(std::string("cmi_slope_create: ") + cmi_slope_last_error(nullptr));
-        std::vector<int32_t> u2, j2;
-        std::vector<double> r2;
-        to2d(trainMatrix, u2, j2, r2);
-        scheck(cmi_slope_set_ratings(slope_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), "cmi_slope_set_ratings");
-        scheck(cmi_slope_build(slope_), "cmi_slope_build");
+        check(cmi_slope_create(trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &h_), "cmi_slope_create");
+        setRatings("cmi_slope_set_ratings");
+        check(cmi_slope_build(h_), "cmi_slope_build");
     }
-    Measures evalRatings() override { // Recommender.java:504-594 (numeric part)
-        std::vector<double> pred((size_t)testMatrix.n());
-        scheck(cmi_slope_predict_batch(slope_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), globalMean, 1,
-                                       trainMatrix.min_rate, trainMatrix.max_rate, pred.data()), "cmi_slope_predict_batch");
-        return evalPredictions(pred);
-    }
-    void saveModel() override {} // the reference's SlopeOne inherits Recommender's empty saveModel()
 
   private:
-    void scheck(int rc, const char *what) {
-        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_slope_last_error(slope_));
+    void predictBounded(double *pred) override {
+        check(cmi_slope_predict_batch(h_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), globalMean, 1, trainMatrix.min_rate,
+                                      trainMatrix.max_rate, pred), "cmi_slope_predict_batch");
     }
-    cmi_slope_handle slope_ = nullptr;
 };
 
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names

@@ -8,23 +8,18 @@
 namespace cmi {
 
 // ---- similarity build ----------------------------------------------------------------------------------------------------------
-// A workgroup owns an anchor row a and its partners b > a, one per lane (chunks of KNN_BUILD_BLOCK).  The anchor's vector is
-// scattered into LDS one tile of KNN_TILE contracted indices at a time (only tiles where the anchor has entries: no common entry lies
-// elsewhere); every lane walks its partner's entries of that tile in ascending order and probes the tile, so the common entries are
-// met in ascending order and the running sums stay in the lane's registers across tiles.  pcc sweeps the tiles twice (the means of
-// the common lists first, then the centred sums), as Sims.pcc does.  A tile entry is valid when its tag equals the current generation,
-// so a tile is never cleared.
+// A workgroup owns an anchor row a and its partners b > a, one per lane (chunks of PAIR_BUILD_BLOCK), and meets every pair's common
+// entries in ascending order by the shared walk (pair_walk.hpp); the measure's running sums stay in the lane's registers.  pcc sweeps
+// the anchor's tiles twice (the means of the common lists first, then the centred sums), as Sims.pcc does.
 template <int M>
-__global__ __launch_bounds__(KNN_BUILD_BLOCK) void knn_build_kernel(KnnCsr R, int n, const double *norm2, int shrinkage, double median,
-                                                                    double *S) {
-    __shared__ double lv[KNN_TILE];
-    __shared__ int32_t tag[KNN_TILE];
-    __shared__ uint8_t okA[M == CMI_SIM_COS_BINARY ? KNN_TILE : 1];
-    __shared__ int32_t s_qb;
+__global__ __launch_bounds__(PAIR_BUILD_BLOCK) void knn_build_kernel(PairCsr R, int n, const double *norm2, int shrinkage, double median,
+                                                                     double *S) {
+    // correlation(): iv.contains(idx) misses an anchor entry; cos-binary counts those entries and keeps the byte beside the value
+    __shared__ PairTile<M == CMI_SIM_COS_BINARY ? PairOk::BESIDE : PairOk::FOUND> T;
     const int a = blockIdx.x;
     const int a0 = R.ptr[a], a1 = R.ptr[a + 1];
     if (a0 == a1 || a + 1 >= n) return; // Recommender.buildCorrs skips empty rows
-    for (int i = threadIdx.x; i < KNN_TILE; i += blockDim.x) tag[i] = -1;
+    pair_tile_init(T);
     int gen = 0;
     constexpr int PASSES = M == CMI_SIM_PCC ? 2 : 1;
     for (int c = a + 1; c < n; c += blockDim.x) {
@@ -39,75 +34,39 @@ __global__ __launch_bounds__(KNN_BUILD_BLOCK) void knn_build_kernel(KnnCsr R, in
                 mub = x2 / (double)k;
                 x1 = x2 = 0.0;
             }
-            int cur = b0;
-            for (int qa = a0; qa < a1;) {
-                const int lo = R.idx[qa] / KNN_TILE * KNN_TILE, hi = lo + KNN_TILE;
-                __syncthreads(); // the previous tile's readers are done
-                if (threadIdx.x == 0) { // the anchor's entries of this tile: [qa, qb)
-                    int l = qa, r = a1;
-                    while (l < r) {
-                        const int m = (l + r) >> 1;
-                        if (R.idx[m] < hi) l = m + 1;
-                        else r = m;
+            // va, vb: is.add(iv.get(idx)), js.add(jv.get(idx))
+            pair_sweep(R, a0, a1, b0, b1, act, T, gen, [&](double va, double vb, int slot, int cur) {
+                if (M == CMI_SIM_PCC) {
+                    if (pass == 0) {
+                        x1 += va;
+                        x2 += vb;
+                        ++k;
+                    } else {
+                        const double da = va - mua, db = vb - mub;
+                        x1 += da * db;
+                        x2 += da * da;
+                        x3 += db * db;
                     }
-                    s_qb = l;
+                } else if (M == CMI_SIM_MSD) {
+                    const double d = va - vb; // Math.pow(d, 2.0) == d * d
+                    x1 += d * d;
+                    ++k;
+                } else if (M == CMI_SIM_CPC) {
+                    const double da = va - median, db = vb - median;
+                    x1 += da * db;
+                    x2 += da * da;
+                    x3 += db * db;
+                    ++k;
+                } else if (M == CMI_SIM_COS_BINARY) {
+                    if (R.ok[cur]) x1 += va * vb; // iv.inner(jv): jv.contains(idx)
+                    k += T.ok[slot];              // n = is.size(): the entries iv.contains finds
+                } else { // cos, exjaccard
+                    x1 += va * vb;
+                    x2 += va * va;
+                    x3 += vb * vb;
+                    ++k;
                 }
-                __syncthreads();
-                const int qb = s_qb;
-                for (int q = qa + (int)threadIdx.x; q < qb; q += blockDim.x) {
-                    if (M != CMI_SIM_COS_BINARY && !R.ok[q]) continue; // correlation(): iv.contains(idx) misses this entry
-                    lv[R.idx[q] - lo] = R.val[q];
-                    tag[R.idx[q] - lo] = gen;
-                    if (M == CMI_SIM_COS_BINARY) okA[R.idx[q] - lo] = R.ok[q];
-                }
-                __syncthreads();
-                if (act) {
-                    int l = cur, r = b1; // skip the partner's entries below the tile
-                    while (l < r) {
-                        const int m = (l + r) >> 1;
-                        if (R.idx[m] < lo) l = m + 1;
-                        else r = m;
-                    }
-                    for (cur = l; cur < b1; ++cur) {
-                        const int x = R.idx[cur];
-                        if (x >= hi) break;
-                        if (tag[x - lo] != gen) continue;
-                        const double va = lv[x - lo], vb = R.val[cur]; // is.add(iv.get(idx)), js.add(jv.get(idx))
-                        if (M == CMI_SIM_PCC) {
-                            if (pass == 0) {
-                                x1 += va;
-                                x2 += vb;
-                                ++k;
-                            } else {
-                                const double da = va - mua, db = vb - mub;
-                                x1 += da * db;
-                                x2 += da * da;
-                                x3 += db * db;
-                            }
-                        } else if (M == CMI_SIM_MSD) {
-                            const double d = va - vb; // Math.pow(d, 2.0) == d * d
-                            x1 += d * d;
-                            ++k;
-                        } else if (M == CMI_SIM_CPC) {
-                            const double da = va - median, db = vb - median;
-                            x1 += da * db;
-                            x2 += da * da;
-                            x3 += db * db;
-                            ++k;
-                        } else if (M == CMI_SIM_COS_BINARY) {
-                            if (R.ok[cur]) x1 += va * vb; // iv.inner(jv): jv.contains(idx)
-                            k += okA[x - lo];             // n = is.size(): the entries iv.contains finds
-                        } else { // cos, exjaccard
-                            x1 += va * vb;
-                            x2 += va * va;
-                            x3 += vb * vb;
-                            ++k;
-                        }
-                    }
-                }
-                ++gen;
-                qa = qb;
-            }
+            });
         }
         if (!act) continue;
         double sim;
@@ -125,10 +84,10 @@ __global__ __launch_bounds__(KNN_BUILD_BLOCK) void knn_build_kernel(KnnCsr R, in
     }
 }
 
-hipError_t knn_launch_build(KnnCsr rows, int n, const double *norm2, int measure, int shrinkage, double median, double *S,
+hipError_t knn_launch_build(PairCsr rows, int n, const double *norm2, int measure, int shrinkage, double median, double *S,
                             hipStream_t s) {
     if (n <= 1) return hipSuccess;
-    const dim3 g(n), b(KNN_BUILD_BLOCK);
+    const dim3 g(n), b(PAIR_BUILD_BLOCK);
     switch (measure) {
     case CMI_SIM_COS: knn_build_kernel<CMI_SIM_COS><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
     case CMI_SIM_COS_BINARY: knn_build_kernel<CMI_SIM_COS_BINARY><<<g, b, 0, s>>>(rows, n, norm2, shrinkage, median, S); break;
@@ -140,7 +99,7 @@ hipError_t knn_launch_build(KnnCsr rows, int n, const double *norm2, int measure
     return hipGetLastError();
 }
 
-__global__ void knn_row_stats_kernel(KnnCsr R, int n, double *mean, double *norm2) {
+__global__ void knn_row_stats_kernel(PairCsr R, int n, double *mean, double *norm2) {
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= n) return;
     double s = 0.0, q = 0.0;
@@ -153,7 +112,7 @@ __global__ void knn_row_stats_kernel(KnnCsr R, int n, double *mean, double *norm
     norm2[v] = q;
 }
 
-hipError_t knn_launch_row_stats(KnnCsr rows, int n, double *mean, double *norm2, hipStream_t s) {
+hipError_t knn_launch_row_stats(PairCsr rows, int n, double *mean, double *norm2, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     knn_row_stats_kernel<<<(n + 255) / 256, 256, 0, s>>>(rows, n, mean, norm2);
     return hipGetLastError();
@@ -221,7 +180,7 @@ __device__ void hm_grow(K kat, int n, int &cap, int &thr, int &tree, int32_t *cn
     tree |= __any(flag) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(64) void knn_predict_kernel(KnnCsr L, const double *S, int n_ent, const double *mean, int64_t n,
+__global__ __launch_bounds__(64) void knn_predict_kernel(PairCsr L, const double *S, int n_ent, const double *mean, int64_t n,
                                                          const int32_t *owner, const int32_t *target, int knn, double gm, int bound,
                                                          double lo, double hi, double *out, int cap_entries, int32_t *s_key,
                                                          double *s_sim, double *s_rate, int32_t *s_pos, int32_t *s_sel, int32_t *bad) {
@@ -308,10 +267,7 @@ __global__ __launch_bounds__(64) void knn_predict_kernel(KnnCsr L, const double 
             }
         }
         if (lane == 0) {
-            if (bound) {
-                if (pred > hi) pred = hi;
-                if (pred < lo) pred = lo;
-            }
+            pred = pair_bound(pred, bound, lo, hi);
             if (tree) {
                 atomicAdd(bad, 1);
                 pred = __builtin_nan("");
@@ -322,7 +278,7 @@ __global__ __launch_bounds__(64) void knn_predict_kernel(KnnCsr L, const double 
     }
 }
 
-hipError_t knn_launch_predict(KnnCsr lists, const double *S, int n_ent, const double *mean, int64_t n, const int32_t *owner,
+hipError_t knn_launch_predict(PairCsr lists, const double *S, int n_ent, const double *mean, int64_t n, const int32_t *owner,
                               const int32_t *target, int knn, double global_mean, int bound, double lo, double hi, double *out,
                               int nwaves, int cap, int32_t *s_key, double *s_sim, double *s_rate, int32_t *s_pos, int32_t *s_sel,
                               int32_t *bad, hipStream_t s) {

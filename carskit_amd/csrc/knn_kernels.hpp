@@ -3,31 +3,20 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "pair_walk.hpp"
+
 namespace cmi {
-
-// rows of the compared side ("entities": items for ItemKNN, users for UserKNN) over the contracted index, CSR, ascending
-struct KnnCsr {
-    const int32_t *ptr = nullptr; // n + 1
-    const int32_t *idx = nullptr;
-    const double *val = nullptr;
-    // rows only: does librec's SparseVector.contains find the entry in its own row?  contains() binary-searches the whole index array,
-    // which set() grows to the next power of two with a zero tail, so some entries of the upper half are never found.
-    const uint8_t *ok = nullptr;
-};
-
-constexpr int KNN_TILE = 4096;    // contracted indices per LDS tile of the anchor's vector (48 KiB of LDS with the tags)
-constexpr int KNN_BUILD_BLOCK = 256;
 
 // Recommender.buildCorrs: S[a][b] = S[b][a] = correlation(row a, row b) for a < b, both rows non-empty; NaN stays where it is unset
 // (S must be NaN-filled before).  norm2: inner(v, v) of every row (cos-binary).
-hipError_t knn_launch_build(KnnCsr rows, int n, const double *norm2, int measure, int shrinkage, double median, double *S,
+hipError_t knn_launch_build(PairCsr rows, int n, const double *norm2, int measure, int shrinkage, double median, double *S,
                             hipStream_t s);
 // SparseVector.mean() (and inner(v, v)) of every row; empty rows get NaN
-hipError_t knn_launch_row_stats(KnnCsr rows, int n, double *mean, double *norm2, hipStream_t s);
+hipError_t knn_launch_row_stats(PairCsr rows, int n, double *mean, double *norm2, hipStream_t s);
 // predict(u, j) of n tuples (one wave each).  owner[t] names the list the candidates come from (ItemKNN: the user's items, UserKNN:
 // the item's users: a row of `lists`), target[t] the row of S they are scored against.  scratch: nwaves * cap entries of each array.
 // bad[0] counts tuples whose HashMap would treeify a bin.
-hipError_t knn_launch_predict(KnnCsr lists, const double *S, int n_ent, const double *mean, int64_t n, const int32_t *owner,
+hipError_t knn_launch_predict(PairCsr lists, const double *S, int n_ent, const double *mean, int64_t n, const int32_t *owner,
                               const int32_t *target, int knn, double global_mean, int bound, double lo, double hi, double *out,
                               int nwaves, int cap, int32_t *s_key, double *s_sim, double *s_rate, int32_t *s_pos, int32_t *s_sel,
                               int32_t *bad, hipStream_t s);

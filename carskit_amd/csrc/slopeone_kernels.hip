@@ -7,19 +7,14 @@
 namespace cmi {
 
 // ---- deviation build -----------------------------------------------------------------------------------------------------------
-// A workgroup owns an anchor column a and its partners b > a, one per lane (chunks of SLOPE_BUILD_BLOCK).  The anchor's column is
-// scattered into LDS one tile of SLOPE_TILE users at a time (only tiles where the anchor has entries: no common user lies elsewhere);
-// every lane walks its partner's entries of that tile in ascending order and probes the tile, so the common users are met in ascending
-// order and the running sum stays in the lane's registers across tiles.  A tile entry is valid when its tag equals the current
-// generation, so a tile is never cleared.
-__global__ __launch_bounds__(SLOPE_BUILD_BLOCK) void slope_build_kernel(SlopeCsr C, int n, double *dev, int32_t *card) {
-    __shared__ double lv[SLOPE_TILE];
-    __shared__ int32_t tag[SLOPE_TILE];
-    __shared__ int32_t s_qb;
+// A workgroup owns an anchor column a and its partners b > a, one per lane (chunks of PAIR_BUILD_BLOCK), and meets every pair's common
+// users in ascending order by the shared walk (pair_walk.hpp); the running sum stays in the lane's registers.
+__global__ __launch_bounds__(PAIR_BUILD_BLOCK) void slope_build_kernel(PairCsr C, int n, double *dev, int32_t *card) {
+    __shared__ PairTile<PairOk::ALL> T;
     const int a = blockIdx.x;
     const int a0 = C.ptr[a], a1 = C.ptr[a + 1];
     if (a0 == a1 || a + 1 >= n) return; // no user rated a: no pair of a has a common user
-    for (int i = threadIdx.x; i < SLOPE_TILE; i += blockDim.x) tag[i] = -1;
+    pair_tile_init(T);
     int gen = 0;
     for (int c = a + 1; c < n; c += blockDim.x) {
         const int b = c + (int)threadIdx.x;
@@ -27,44 +22,10 @@ __global__ __launch_bounds__(SLOPE_BUILD_BLOCK) void slope_build_kernel(SlopeCsr
         const bool act = b0 < b1;
         int k = 0;
         double sum = 0.0;
-        int cur = b0;
-        for (int qa = a0; qa < a1;) {
-            const int lo = C.idx[qa] / SLOPE_TILE * SLOPE_TILE, hi = lo + SLOPE_TILE;
-            __syncthreads(); // the previous tile's readers are done
-            if (threadIdx.x == 0) { // the anchor's entries of this tile: [qa, qb)
-                int l = qa, r = a1;
-                while (l < r) {
-                    const int m = (l + r) >> 1;
-                    if (C.idx[m] < hi) l = m + 1;
-                    else r = m;
-                }
-                s_qb = l;
-            }
-            __syncthreads();
-            const int qb = s_qb;
-            for (int q = qa + (int)threadIdx.x; q < qb; q += blockDim.x) {
-                lv[C.idx[q] - lo] = C.val[q];
-                tag[C.idx[q] - lo] = gen;
-            }
-            __syncthreads();
-            if (act) {
-                int l = cur, r = b1; // skip the partner's entries below the tile
-                while (l < r) {
-                    const int m = (l + r) >> 1;
-                    if (C.idx[m] < lo) l = m + 1;
-                    else r = m;
-                }
-                for (cur = l; cur < b1; ++cur) {
-                    const int x = C.idx[cur];
-                    if (x >= hi) break;
-                    if (tag[x - lo] != gen) continue;
-                    sum += lv[x - lo] - C.val[cur]; // devMatrix.add(a, b, r_ua - r_ub)
-                    ++k;
-                }
-            }
-            ++gen;
-            qa = qb;
-        }
+        pair_sweep(C, a0, a1, b0, b1, act, T, gen, [&](double va, double vb, int, int) {
+            sum += va - vb; // devMatrix.add(a, b, r_ua - r_ub)
+            ++k;
+        });
         if (!act || k == 0) continue;
         const double d = sum / (double)k;
         dev[(int64_t)a * n + b] = d;
@@ -75,9 +36,9 @@ __global__ __launch_bounds__(SLOPE_BUILD_BLOCK) void slope_build_kernel(SlopeCsr
     }
 }
 
-hipError_t slope_launch_build(SlopeCsr cols, int n, double *dev, int32_t *card, hipStream_t s) {
+hipError_t slope_launch_build(PairCsr cols, int n, double *dev, int32_t *card, hipStream_t s) {
     if (n <= 1) return hipSuccess;
-    slope_build_kernel<<<dim3(n), dim3(SLOPE_BUILD_BLOCK), 0, s>>>(cols, n, dev, card);
+    slope_build_kernel<<<dim3(n), dim3(PAIR_BUILD_BLOCK), 0, s>>>(cols, n, dev, card);
     return hipGetLastError();
 }
 
@@ -85,7 +46,7 @@ hipError_t slope_launch_build(SlopeCsr cols, int n, double *dev, int32_t *card, 
 // A wave per tuple (u, j).  The user's items are taken 64 at a time: every lane loads its item's rating and the entries of row j of dev
 // and card, and forms its own term (dev + r) * card; then the whole wave adds the valid terms (card > 0, i != j) lane after lane, i.e.
 // in item order, in one chain that is carried from chunk to chunk.
-__global__ __launch_bounds__(64) void slope_predict_kernel(SlopeCsr R, const double *dev, const int32_t *card, int n_items, int64_t n,
+__global__ __launch_bounds__(64) void slope_predict_kernel(PairCsr R, const double *dev, const int32_t *card, int n_items, int64_t n,
                                                            const int32_t *tu, const int32_t *tj, double gm, int bound, double lo,
                                                            double hi, double *out) {
     const int lane = threadIdx.x;
@@ -113,17 +74,12 @@ __global__ __launch_bounds__(64) void slope_predict_kernel(SlopeCsr R, const dou
             }
         }
         if (lane == 0) {
-            double pred = cards > 0.0 ? preds / cards : gm;
-            if (bound) {
-                if (pred > hi) pred = hi;
-                if (pred < lo) pred = lo;
-            }
-            out[t] = pred;
+            out[t] = pair_bound(cards > 0.0 ? preds / cards : gm, bound, lo, hi);
         }
     }
 }
 
-hipError_t slope_launch_predict(SlopeCsr rows, const double *dev, const int32_t *card, int n_items, int64_t n, const int32_t *u,
+hipError_t slope_launch_predict(PairCsr rows, const double *dev, const int32_t *card, int n_items, int64_t n, const int32_t *u,
                                 const int32_t *j, double global_mean, int bound, double lo, double hi, double *out, int nwaves,
                                 hipStream_t s) {
     if (n <= 0) return hipSuccess;

@@ -3,24 +3,17 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "pair_walk.hpp"
+
 namespace cmi {
-
-// one side of the 2-D train matrix, CSR, ascending: columns (item -> users) for the build, rows (user -> items) for the prediction
-struct SlopeCsr {
-    const int32_t *ptr = nullptr; // n + 1
-    const int32_t *idx = nullptr;
-    const double *val = nullptr;
-};
-
-constexpr int SLOPE_TILE = 4096; // users per LDS tile of the anchor's column (48 KiB of LDS with the tags)
-constexpr int SLOPE_BUILD_BLOCK = 256;
 
 // SlopeOne.buildModel: for every pair a < b of columns with a common user, dev[a][b] = (sum over the common users, ascending, of
 // r_ua - r_ub) / k, dev[b][a] its mirror (+0.0 where the sum is zero) and card[a][b] = card[b][a] = k.  dev and card (n x n) must be
 // zero-filled before.
-hipError_t slope_launch_build(SlopeCsr cols, int n, double *dev, int32_t *card, hipStream_t s);
+// cols: item -> users, for the build; rows: user -> items, for the prediction
+hipError_t slope_launch_build(PairCsr cols, int n, double *dev, int32_t *card, hipStream_t s);
 // SlopeOne.predict(u, j) of n tuples, a wave each (nwaves waves take the tuples in turn)
-hipError_t slope_launch_predict(SlopeCsr rows, const double *dev, const int32_t *card, int n_items, int64_t n, const int32_t *u,
+hipError_t slope_launch_predict(PairCsr rows, const double *dev, const int32_t *card, int n_items, int64_t n, const int32_t *u,
                                 const int32_t *j, double global_mean, int bound, double lo, double hi, double *out, int nwaves,
                                 hipStream_t s);
 

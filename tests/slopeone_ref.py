@@ -112,8 +112,3 @@ def golden_runs():
                      "dev": unhex(run["dev"]), "card": np.array(run["card"], np.int32), "predict": unhex(run["predict"]),
                      "predict_bounded": unhex(run["predict_bounded"])})
     return runs
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all(a.view(np.int64) == b.view(np.int64)))

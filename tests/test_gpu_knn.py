@@ -16,31 +16,13 @@ import pytest
 from carskit_amd import capi, dao
 from tests import knn_ref
 from tests.frappe import write_ratings
+from tests.util import global_mean, same_bits, synth_chunks_by_tiles, to2d
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "carskit_amd", "bin", "carskit-mi355x")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-
-
-def same_bits(a, b):
-    """identical doubles, any NaN equal to any NaN (NaN marks "unset" in both)"""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
-
-
-def to2d(u, j, r):
-    """DataDAO.toTraditionalSparseMatrix: each (user, item) cell's mean over its tuples, summed in tuple order"""
-    order = np.lexsort((np.arange(len(r)), j, u))
-    cells = {}
-    for t in order.tolist():
-        key = (int(u[t]), int(j[t]))
-        s, c = cells.get(key, (0.0, 0))
-        cells[key] = (s + float(r[t]), c + 1)
-    keys = sorted(cells)
-    return (np.array([k[0] for k in keys], np.int32), np.array([k[1] for k in keys], np.int32),
-            np.array([cells[k][0] / cells[k][1] for k in keys]))
 
 
 def read(tmp_path, src):
@@ -75,33 +57,6 @@ def synth_multitile(seed=3, n_items=90, n_users=3 * 4096 + 500, cells=9000):
     i = np.array([c[1] for c in uniq], np.int32)
     r = rng.integers(1, 6, len(uniq)) / rng.integers(1, 4, len(uniq))
     return n_users, n_items, u, i, r
-
-
-def synth_chunks_by_tiles(seed=4, n_rows=640, n_ctr=3 * 4096 + 600):
-    """640 compared rows (3 chunks of 256 partners) over a contracted dimension of 4 tiles: by row mod 8, empty rows; rows only in the
-    first tile; rows only in the last tile; rows with entries in every tile; rows spread over all of it with half their entries in
-    the busy ranges, so pairs share entries in every tile"""
-    rng = np.random.default_rng(seed)
-    busy = [np.arange(t * 4096, t * 4096 + 300) for t in range(4)]
-    cells = []
-    for e in range(n_rows):
-        kind, cnt = e % 8, int(rng.integers(1, 60))
-        if kind == 0:
-            continue
-        if kind == 1:
-            c = rng.choice(busy[0], min(cnt, 300), replace=False)
-        elif kind == 2:
-            c = rng.choice(busy[3], min(cnt, 300), replace=False)
-        elif kind == 3:
-            c = np.concatenate([rng.choice(b, max(cnt // 4, 1), replace=False) for b in busy])
-        else:
-            c = np.concatenate([rng.choice(np.concatenate(busy), cnt // 2 + 1, replace=False), rng.integers(0, n_ctr, cnt // 2)])
-        for x in np.unique(c).tolist():
-            cells.append((e, x, float(rng.integers(1, 6)) / float(rng.integers(1, 3))))
-    ent = np.array([c[0] for c in cells], np.int32)
-    ctr = np.array([c[1] for c in cells], np.int32)
-    r = np.array([c[2] for c in cells])
-    return n_rows, n_ctr, ent, ctr, r
 
 
 def handmade():
@@ -226,14 +181,6 @@ def predict_case(kind, nu, ni, u, i, r, tu, tj, measure, gm, lo, hi):
         got = h.predict(tu, tj, knn, gm, True, lo, hi)
         assert same_bits(got, want), (kind, knn, np.nonzero(~((got == want) | (np.isnan(got) & np.isnan(want))))[0][:5])
     h.close()
-
-
-def global_mean(r):
-    """SparseMatrix.getGlobalAvg of the contextual train matrix: a sequential sum over the entries / the non-zero count"""
-    s = 0.0
-    for v in np.asarray(r, dtype=np.float64).tolist():
-        s += v
-    return s / np.count_nonzero(r)
 
 
 def test_predictions_match_the_reference_run():

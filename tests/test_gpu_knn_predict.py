@@ -15,15 +15,11 @@ import pytest
 
 from carskit_amd import capi
 from tests import knn_ref
+from tests.util import same_bits
 
 pytestmark = pytest.mark.gpu
 
 LIMIT = 16384  # CMI_KNN_MAX_CANDIDATES
-
-
-def same_bits(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(np.all((a.view(np.int64) == b.view(np.int64)) | (np.isnan(a) & np.isnan(b))))
 
 
 class Case:

@@ -14,6 +14,7 @@ from carskit_amd import capi, dao
 from tests import slopeone_ref as sref
 from tests.hostmirror import splitter
 from tests.knn_ref import eval_ratings
+from tests.util import global_mean, same_bits_exact, synth_chunks_by_tiles, to2d
 
 pytestmark = pytest.mark.gpu
 
@@ -21,7 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "carskit_amd", "bin", "carskit-mi355x")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
-TILE = 4096  # SLOPE_TILE: users per LDS tile of the anchor's column
+TILE = 4096  # PAIR_TILE: users per LDS tile of the anchor's column
 
 
 def all_tuples(nu, ni):
@@ -41,16 +42,16 @@ def test_golden_matrices_match_the_reference_run():
         h = built(nu, ni, run["u"], run["i"], run["r"])
         dev, card = h.deviation()
         assert np.array_equal(card, run["card"]), run["name"]
-        assert sref.same_bits(dev, run["dev"]), (run["name"], np.argwhere(dev.view(np.int64) != run["dev"].view(np.int64))[:5])
+        assert same_bits_exact(dev, run["dev"]), (run["name"], np.argwhere(dev.view(np.int64) != run["dev"].view(np.int64))[:5])
         tu, tj = all_tuples(nu, ni)
         gm, lo, hi = run["global_mean"], run["min_rate"], run["max_rate"]
-        assert sref.same_bits(h.predict(tu, tj, gm).reshape(nu, ni), run["predict"]), run["name"]
-        assert sref.same_bits(h.predict(tu, tj, gm, True, lo, hi).reshape(nu, ni), run["predict_bounded"]), run["name"]
+        assert same_bits_exact(h.predict(tu, tj, gm).reshape(nu, ni), run["predict"]), run["name"]
+        assert same_bits_exact(h.predict(tu, tj, gm, True, lo, hi).reshape(nu, ni), run["predict_bounded"]), run["name"]
         d1, c1 = h.deviation(1, 2)                                       # a row range; one destination only
-        assert sref.same_bits(d1, run["dev"][1:3]) and np.array_equal(c1, run["card"][1:3])
+        assert same_bits_exact(d1, run["dev"][1:3]) and np.array_equal(c1, run["card"][1:3])
         out = np.empty((2, ni))
         h._chk(h.L.cmi_slope_get_deviation(h.h, 1, 2, capi._p(out), None))
-        assert sref.same_bits(out, run["dev"][1:3])
+        assert same_bits_exact(out, run["dev"][1:3])
         outc = np.empty((2, ni), np.int32)
         h._chk(h.L.cmi_slope_get_deviation(h.h, 1, 2, None, capi._p(outc)))
         assert np.array_equal(outc, run["card"][1:3])
@@ -94,7 +95,7 @@ def test_build_two_lds_tiles_and_two_partner_chunks():
     h = built(nu, ni, u, i, r)
     dev, card = h.deviation()
     assert np.array_equal(card, want_card)
-    assert sref.same_bits(dev, want_dev), np.argwhere(dev.view(np.int64) != want_dev.view(np.int64))[:5]
+    assert same_bits_exact(dev, want_dev), np.argwhere(dev.view(np.int64) != want_dev.view(np.int64))[:5]
     assert card[7, 8] == len(cols[7]) and dev[7, 8] == 0 and not np.signbit(dev[7, 8]) and not np.signbit(dev[8, 7])
     assert card[40, 41] == 0 and not card[30].any() and not card[:, 30].any()
     assert card[20, 0] > 0 and card[20].max() <= 4
@@ -104,9 +105,31 @@ def test_build_two_lds_tiles_and_two_partner_chunks():
     gm = 3.125
     for bound in (False, True):
         want = [sref.predict(want_dev, want_card, rows, a, b, gm, bound, 1.0, 5.0) for a, b in zip(tu.tolist(), tj.tolist())]
-        assert sref.same_bits(h.predict(tu, tj, gm, bound, 1.0, 5.0), want), bound
+        assert same_bits_exact(h.predict(tu, tj, gm, bound, 1.0, 5.0), want), bound
     assert h.last_build_ms() > 0.0
     h.close()
+
+
+def test_build_partner_chunks_by_tiles():
+    """the matrix of test_gpu_knn's test of the same name, its 640 compared rows as items and its 12 888 contracted indices as users:
+    three 256-partner chunks of one anchor, each sweeping up to four 4 096-user tiles, anchors with nothing in the middle tiles (a tile
+    is skipped, the generation runs on into the next chunk) and empty columns between; the CPU restates the same subsample of anchors"""
+    ni, nu, i, u, r = synth_chunks_by_tiles()
+    anchors = sorted({0, 1, 2, 3, 4, 8, 11, 255, 256, 257, 511, 512, ni - 9, ni - 3, ni - 2, ni - 1} |
+                     set(np.random.default_rng(1).integers(0, ni, 24).tolist()))
+    cols = sref.cols_of(u, i, r, ni)
+    assert (ni, nu) == (640, 3 * TILE + 600) and 16000 <= len(r) <= 18000 and ni - 1 > 2 * 256
+    assert not any(cols[a] for a in range(0, ni, 8)) and {a % 8 for a in anchors} >= set(range(8))
+    tiles = [{x // TILE for x, _ in cols[a]} for a in anchors]
+    assert any(t == {0, 1, 2, 3} for t in tiles) and any(min(t) == 0 and max(t) == 3 and len(t) < 4 for t in tiles if t)
+    want = sref.build_rows(cols, anchors)
+    h = built(nu, ni, u, i, r)
+    dev, card = h.deviation()
+    h.close()
+    for a in anchors:
+        assert np.array_equal(card[a], want[a][1]), a
+        assert same_bits_exact(dev[a], want[a][0]), (a, np.nonzero(dev[a].view(np.int64) != want[a][0].view(np.int64))[0][:5])
+    assert np.array_equal(card, card.T) and card.any()
 
 
 def long_lists_matrix():
@@ -129,7 +152,7 @@ def test_predict_chunks_of_64_carry_the_sum():
     want_dev, want_card = sref.build(rows, ni)
     h = built(nu, ni, u, i, r)
     dev, card = h.deviation()
-    assert np.array_equal(card, want_card) and sref.same_bits(dev, want_dev)
+    assert np.array_equal(card, want_card) and same_bits_exact(dev, want_dev)
     tu, tj = all_tuples(nu, ni)   # every j: the user's own items of every chunk (i == j at positions 0..149) and the unrated ones
     own0 = [j for j, _ in rows[0]]
     assert set(own0[64:]) and len(set(range(ni)) - set(own0)) == 50
@@ -137,7 +160,7 @@ def test_predict_chunks_of_64_carry_the_sum():
     for bound in (False, True):
         want = [sref.predict(want_dev, want_card, rows, a, b, gm, bound, 1.0, 5.0) for a, b in zip(tu.tolist(), tj.tolist())]
         got = h.predict(tu, tj, gm, bound, 1.0, 5.0)
-        assert sref.same_bits(got, want), (bound, np.nonzero(got != np.array(want))[0][:5])
+        assert same_bits_exact(got, want), (bound, np.nonzero(got != np.array(want))[0][:5])
     assert (h.predict(tu, tj, gm).reshape(nu, ni)[5] == gm).all()
     h.close()
 
@@ -189,27 +212,6 @@ def test_refusals():
         capi.SlopeOneInstance(0, 3)
     assert e.value.code == capi.E_INVALID
     h.close()
-
-
-def to2d(u, j, r):
-    """DataDAO.toTraditionalSparseMatrix: each (user, item) cell's mean over its tuples, summed in tuple order"""
-    order = np.lexsort((np.arange(len(r)), j, u))
-    cells = {}
-    for t in order.tolist():
-        key = (int(u[t]), int(j[t]))
-        s, c = cells.get(key, (0.0, 0))
-        cells[key] = (s + float(r[t]), c + 1)
-    keys = sorted(cells)
-    return (np.array([k[0] for k in keys], np.int32), np.array([k[1] for k in keys], np.int32),
-            np.array([cells[k][0] / cells[k][1] for k in keys]))
-
-
-def global_mean(r):
-    """SparseMatrix.getGlobalAvg of the contextual train matrix: a sequential sum over the entries / the non-zero count"""
-    s = 0.0
-    for v in np.asarray(r, dtype=np.float64).tolist():
-        s += v
-    return s / np.count_nonzero(r)
 
 
 def test_driver_parity_depaul(tmp_path):

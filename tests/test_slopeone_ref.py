@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import slopeone_ref as sref
+from tests.util import same_bits_exact
 
 RUNS = sref.golden_runs()
 
@@ -20,12 +21,12 @@ def test_restatement_equals_the_reference_run(run):
     rows = sref.rows_of(run["u"], run["i"], run["r"], nu)
     dev, card = sref.build(rows, ni)
     assert np.array_equal(card, run["card"])
-    assert sref.same_bits(dev, run["dev"]), np.argwhere(dev.view(np.int64) != run["dev"].view(np.int64))[:5]
+    assert same_bits_exact(dev, run["dev"]), np.argwhere(dev.view(np.int64) != run["dev"].view(np.int64))[:5]
     gm, lo, hi = run["global_mean"], run["min_rate"], run["max_rate"]
     free = [[sref.predict(dev, card, rows, u, j, gm) for j in range(ni)] for u in range(nu)]
     bounded = [[sref.predict(dev, card, rows, u, j, gm, True, lo, hi) for j in range(ni)] for u in range(nu)]
-    assert sref.same_bits(free, run["predict"])
-    assert sref.same_bits(bounded, run["predict_bounded"])
+    assert same_bits_exact(free, run["predict"])
+    assert same_bits_exact(bounded, run["predict_bounded"])
 
 
 def test_golden_file_holds_the_cases_it_is_for():
@@ -54,7 +55,7 @@ def test_pair_walk_equals_the_user_loop():
                 assert (bits(dab), bits(dba), k) == (bits(dev[a, b]), bits(dev[b, a]), card[a, b]) and card[b, a] == k
         part = sref.build_rows(cols, [0, run["n_items"] - 1])
         for a, (d, c) in part.items():
-            assert sref.same_bits(d, dev[a]) and np.array_equal(c, card[a])
+            assert same_bits_exact(d, dev[a]) and np.array_equal(c, card[a])
 
 
 def test_two_users_two_items():
