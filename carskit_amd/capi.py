@@ -306,6 +306,22 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _c32(a):
+    return None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _tuples(u, j, ctx, r=None):
+    """(u, j, ctx[, r]) as the C ABI takes them: contiguous int32 ids (ctx may be None), float64 ratings"""
+    ids = (_c32(u), _c32(j), _c32(ctx))
+    return ids if r is None else ids + (np.ascontiguousarray(r, dtype=np.float64),)
+
+
+def _measures(out, cnt):
+    res = dict(zip(("MAE", "RMSE", "NMAE", "rMAE", "rRMSE"), out.tolist()))
+    res["n"] = cnt.value
+    return res
+
+
 def measure_hbm(device=0, nbytes=4 << 30):
     """(copy GB/s, random-512-B-row read-modify-write GB/s) measured on the device right now (cmi_measure_hbm)."""
     out = (C.c_double * 2)()
@@ -485,9 +501,7 @@ class Group(_Handle):
         self._chk(self.L.cmi_group_set_hparams(self.h, regU, regI, regB, regC, global_mean))
 
     def set_ratings(self, u, j, ctx, r, ctx_ptr=None, ctx_conds=None):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx, ctx_ptr, ctx_conds = c32(u), c32(j), c32(ctx), c32(ctx_ptr), c32(ctx_conds)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        (u, j, ctx, r), ctx_ptr, ctx_conds = _tuples(u, j, ctx, r), _c32(ctx_ptr), _c32(ctx_conds)
         n_ctx = 0 if ctx_ptr is None else len(ctx_ptr) - 1
         self._chk(self.L.cmi_group_set_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r), n_ctx, _p(ctx_ptr), _p(ctx_conds)))
 
@@ -528,32 +542,23 @@ class Group(_Handle):
         return losses[:n.value], lrs[:n.value]
 
     def eval_ratings(self, u, j, ctx, r, min_rate, max_rate):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        u, j, ctx, r = _tuples(u, j, ctx, r)
         out, cnt = np.zeros(5), _i64()
         self._chk(self.L.cmi_group_eval_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r), min_rate, max_rate, _p(out), C.byref(cnt)))
-        res = dict(zip(("MAE", "RMSE", "NMAE", "rMAE", "rRMSE"), out.tolist()))
-        res["n"] = cnt.value
-        return res
+        return _measures(out, cnt)
 
     def set_eval_ratings(self, u, j, ctx, r):
         """Test tuples routed once to the shards that own their users and kept on the devices (`--early-stop MAE|RMSE`)."""
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        u, j, ctx, r = _tuples(u, j, ctx, r)
         self._chk(self.L.cmi_group_set_eval_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r)))
 
     def eval_resident(self, min_rate, max_rate):
         out, cnt = np.zeros(5), _i64()
         self._chk(self.L.cmi_group_eval_resident(self.h, min_rate, max_rate, _p(out), C.byref(cnt)))
-        res = dict(zip(("MAE", "RMSE", "NMAE", "rMAE", "rRMSE"), out.tolist()))
-        res["n"] = cnt.value
-        return res
+        return _measures(out, cnt)
 
     def predict_batch(self, u, j, ctx, bound=False, lo=0.0, hi=0.0):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
+        u, j, ctx = _tuples(u, j, ctx)
         out = np.empty(len(u))
         self._chk(self.L.cmi_group_predict_batch(self.h, len(u), _p(u), _p(j), _p(ctx), int(bound), lo, hi, _p(out)))
         return out
@@ -607,9 +612,7 @@ class Instance(_Handle):
         self.num_f = int(num_f)
 
     def set_ratings(self, u, j, ctx, r, ctx_ptr=None, ctx_conds=None):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx, ctx_ptr, ctx_conds = c32(u), c32(j), c32(ctx), c32(ctx_ptr), c32(ctx_conds)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        (u, j, ctx, r), ctx_ptr, ctx_conds = _tuples(u, j, ctx, r), _c32(ctx_ptr), _c32(ctx_conds)
         n_ctx = 0 if ctx_ptr is None else len(ctx_ptr) - 1
         self._chk(self.L.cmi_set_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r), n_ctx, _p(ctx_ptr),
                                          _p(ctx_conds)))
@@ -763,37 +766,28 @@ class Instance(_Handle):
 
     # -- inference ----------------------------------------------------------------------------------
     def predict(self, u, j, ctx=None, bound=None):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
+        u, j, ctx = _tuples(u, j, ctx)
         out = np.empty(len(u))
         lo, hi = bound if bound else (0.0, 0.0)
         self._chk(self.L.cmi_predict_batch(self.h, len(u), _p(u), _p(j), _p(ctx), 1 if bound else 0, lo, hi, _p(out)))
         return out
 
     def eval_ratings(self, u, j, ctx, r, min_rate, max_rate):
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        u, j, ctx, r = _tuples(u, j, ctx, r)
         out, cnt = np.zeros(5), _i64()
         self._chk(self.L.cmi_eval_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r), min_rate, max_rate, _p(out),
                                           C.byref(cnt)))
-        res = dict(zip(("MAE", "RMSE", "NMAE", "rMAE", "rRMSE"), out.tolist()))
-        res["n"] = cnt.value
-        return res
+        return _measures(out, cnt)
 
     def set_eval_ratings(self, u, j, ctx, r):
         """Keep the test tuples on the device for per-epoch evaluation (`--early-stop MAE|RMSE`)."""
-        c32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        u, j, ctx, r = _tuples(u, j, ctx, r)
         self._chk(self.L.cmi_set_eval_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r)))
 
     def eval_resident(self, min_rate, max_rate):
         out, cnt = np.zeros(5), _i64()
         self._chk(self.L.cmi_eval_resident(self.h, min_rate, max_rate, _p(out), C.byref(cnt)))
-        res = dict(zip(("MAE", "RMSE", "NMAE", "rMAE", "rRMSE"), out.tolist()))
-        res["n"] = cnt.value
-        return res
+        return _measures(out, cnt)
 
     def last_rank_ms(self):
         ms, fl = C.c_float(), _dbl()
@@ -831,9 +825,7 @@ class FMInstance(_Handle):
         self._chk(self.L.cmi_fm_set_hparams(self.h, regLw, regLf, global_size))
 
     def set_ratings(self, u, j, ctx, r):
-        c32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
-        r = np.ascontiguousarray(r, dtype=np.float64)
+        u, j, ctx, r = _tuples(u, j, ctx, r)
         self._chk(self.L.cmi_fm_set_ratings(self.h, len(r), _p(u), _p(j), _p(ctx), _p(r)))
 
     def set_model(self, w0, w, V):
@@ -907,8 +899,7 @@ class FMInstance(_Handle):
         return p.value
 
     def predict(self, u, j, ctx, bound=None):
-        c32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-        u, j, ctx = c32(u), c32(j), c32(ctx)
+        u, j, ctx = _tuples(u, j, ctx)
         out = np.empty(len(u))
         lo, hi = bound if bound else (0.0, 0.0)
         self._chk(self.L.cmi_fm_predict_batch(self.h, len(u), _p(u), _p(j), _p(ctx), 1 if bound else 0, lo, hi, _p(out)))

@@ -1,5 +1,5 @@
 // abi.hpp -- the C-ABI boundary shared by every handle kind of libcarskit_mi355x.so (instance, FM, KNN, group, DAO): error
-// messages, the exception barrier, the create-time device check and the device-buffer helpers.  Internal.
+// messages, the exception barrier, the create-time device check, the device-buffer helpers and the prediction batch.  Internal.
 #pragma once
 #include "../../include/carskit_mi355x.h"
 
@@ -104,4 +104,62 @@ void abi_free(T *&...p) {
         q = nullptr;
     };
     (one(p), ...);
+}
+
+// a HIP status as a C-ABI status: on a failure "<fn>: <HIP's message>" in err
+inline int abi_hip(std::string &err, const char *fn, hipError_t e) {
+    return e == hipSuccess ? CMI_OK : abi_fail(err, CMI_E_HIP, "%s: %s", fn, hipGetErrorString(e));
+}
+
+// Validated tuples on the device: two id arrays, for a contextual model the context ids, and for an evaluation the ratings and room for
+// the kernel's block partials.  The transient set of a predict_batch / eval_ratings call, or the resident set of cmi_set_eval_ratings.
+struct AbiTuples {
+    int32_t *a = nullptr, *b = nullptr, *c = nullptr; // user, item (KNN: owner, target), context: n each; c may be null
+    double *r = nullptr, *part = nullptr;             // n ratings and part_doubles partials, or both null
+    int64_t n = 0;
+    AbiTuples() = default;
+    AbiTuples(const AbiTuples &) = delete; // the buffers have one owner, which calls release()
+    AbiTuples &operator=(const AbiTuples &) = delete;
+    // count > 0 tuples; the copies are enqueued on s, which the caller drains before the host arrays go.  hc and hr may be null: no
+    // buffer.  Every buffer (out too: n doubles for the predictions, null: none) is allocated before the first copy is enqueued
+    hipError_t upload(int64_t count, const int32_t *ha, const int32_t *hb, const int32_t *hc, const double *hr, size_t part_doubles,
+                      double **out, hipStream_t s) {
+        n = count;
+        const size_t ids = (size_t)n * sizeof(int32_t), vals = (size_t)n * sizeof(double);
+        hipError_t e = hipMalloc((void **)&a, ids);
+        if (e == hipSuccess) e = hipMalloc((void **)&b, ids);
+        if (e == hipSuccess && hc) e = hipMalloc((void **)&c, ids);
+        if (e == hipSuccess && hr) e = hipMalloc((void **)&r, vals);
+        if (e == hipSuccess && out) e = hipMalloc((void **)out, vals);
+        if (e == hipSuccess && hr) e = hipMalloc((void **)&part, part_doubles * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpyAsync(a, ha, ids, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(b, hb, ids, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && hc) e = hipMemcpyAsync(c, hc, ids, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess && hr) e = hipMemcpyAsync(r, hr, vals, hipMemcpyHostToDevice, s);
+        return e;
+    }
+    void release() {
+        abi_free(a, b, c, r, part);
+        n = 0;
+    }
+};
+
+// predict_batch (and eval_ratings) of n > 0 checked tuples, for every handle kind (a struct with err, device and stream): the tuples
+// uploaded, launch(tuples, d_out) -- a C-ABI status -- enqueued on h->stream, out (n doubles; null: no d_out) copied back.  The stream is
+// drained before anything is freed, whatever failed: the uploads read the host arrays until then.
+template <typename H, typename Launch>
+int abi_predict(H *h, const char *fn, int64_t n, const int32_t *a, const int32_t *b, const int32_t *c, const double *r, size_t part_doubles,
+                double *out, Launch &&launch) {
+    if (int rc = abi_hip(h->err, fn, hipSetDevice(h->device))) return rc;
+    AbiTuples t;
+    double *d_out = nullptr;
+    int rc = CMI_OK;
+    hipError_t e = t.upload(n, a, b, c, r, part_doubles, out ? &d_out : nullptr, h->stream);
+    if (e == hipSuccess) rc = launch(t, d_out);
+    if (e == hipSuccess && rc == CMI_OK && out) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    if (e == hipSuccess) e = es;
+    t.release();
+    abi_free(d_out);
+    return rc != CMI_OK ? rc : abi_hip(h->err, fn, e);
 }

@@ -83,11 +83,6 @@ extern "C" int cmi_device_count(void) {
 
 extern "C" const char *cmi_last_error(cmi_handle h) { return h ? h->err.c_str() : cmi_thread_err().c_str(); }
 
-static void free_eval_set(cmi_instance *h) {
-    abi_free(h->d_eu, h->d_ej, h->d_ectx, h->d_er, h->d_epart);
-    h->n_eval = 0;
-}
-
 // the spoke arena and its position lists; the model table is the master copy again
 static void release_arena(cmi_instance *h) {
     abi_free(h->d_arena, h->d_next, h->d_first);
@@ -100,7 +95,7 @@ static void free_ratings(cmi_instance *h) {
     if (h->arena_on && h->arena_valid && !h->table_valid) cmi_sync_table_from_arena(h); // the live rows are in the arena: bring them home first
     release_arena(h);
     h->arena_probe = false;
-    free_eval_set(h);
+    h->eval_set.release();
     if (h->graph_exec) {
         hipGraphExecDestroy(h->graph_exec);
         h->graph_exec = nullptr;
@@ -1685,9 +1680,12 @@ extern "C" int cmi_last_epoch_ms(cmi_handle h, float *ms) {
 
 // ---- predict / evalRatings -------------------------------------------------------------------------
 
+EvalIO cmi_eval_io(cmi_instance *h, const AbiTuples &t, double *dpreds, int bound, double lo, double hi, double min_rate) {
+    return EvalIO{t.a, t.b, t.c, t.r, dpreds, t.part, h->hp.gm, lo, hi, min_rate, bound};
+}
+
 template <typename T>
-cmi::ExtEvalArgs<T> cmi_ext_eval_args(cmi_instance *h, const int32_t *du, const int32_t *dj, const int32_t *dctx, const double *dr,
-                                      double *dpreds, double *dpart, int bound, double lo, double hi, double min_rate) {
+cmi::ExtEvalArgs<T> cmi_ext_eval_args(cmi_instance *h, const EvalIO &io) {
     ExtEvalArgs<T> x;
     x.P = (const T *)h->state[CMI_STATE_P];
     x.Q = (const T *)h->state[CMI_STATE_Q];
@@ -1697,38 +1695,25 @@ cmi::ExtEvalArgs<T> cmi_ext_eval_args(cmi_instance *h, const int32_t *du, const 
     x.cc = (const T *)h->state[CMI_STATE_CC_MATRIX];
     x.cf = (const T *)h->state[CMI_STATE_CF_MATRIX];
     x.cv = (const T *)h->state[CMI_STATE_C_VECTOR];
-    x.u = du;
-    x.j = dj;
-    x.ctx = dctx;
-    x.r = dr;
     x.ctx_ptr = h->d_ctx_ptr;
     x.ctx_conds = h->d_ctx_conds;
     x.empty_conds = h->d_empty;
     x.ui_ptr = h->d_ui_ptr;
     x.ui_items = h->d_ui_items;
-    x.preds = dpreds;
-    x.part = dpart;
-    x.gm = h->hp.gm;
-    x.lo = lo;
-    x.hi = hi;
-    x.min_rate = min_rate;
+    x.io = io;
     x.k = h->k;
     x.n_conds = h->n_conds;
     x.num_f = h->num_f;
     x.n_empty = (int32_t)h->empty_conds.size();
-    x.bound = bound;
     x.model = h->model;
     return x;
 }
-template cmi::ExtEvalArgs<float> cmi_ext_eval_args<float>(cmi_instance *, const int32_t *, const int32_t *, const int32_t *, const double *, double *, double *, int, double, double, double);
-template cmi::ExtEvalArgs<double> cmi_ext_eval_args<double>(cmi_instance *, const int32_t *, const int32_t *, const int32_t *, const double *, double *, double *, int, double, double, double);
+template cmi::ExtEvalArgs<float> cmi_ext_eval_args<float>(cmi_instance *, const EvalIO &);
+template cmi::ExtEvalArgs<double> cmi_ext_eval_args<double>(cmi_instance *, const EvalIO &);
 
 template <typename T>
-static hipError_t run_eval(cmi_instance *h, int64_t n, const int32_t *du, const int32_t *dj, const int32_t *dctx,
-                           const double *dr, double *dpreds, double *dpart, int bound, double lo, double hi,
-                           double min_rate) {
-    if (is_ext_model(h->model))
-        return launch_ext_eval<T>(cmi_ext_eval_args<T>(h, du, dj, dctx, dr, dpreds, dpart, bound, lo, hi, min_rate), n, h->stream);
+static hipError_t launch_eval_model(cmi_instance *h, const EvalIO &io, int64_t n) {
+    if (is_ext_model(h->model)) return launch_ext_eval<T>(cmi_ext_eval_args<T>(h, io), n, h->stream);
     EvalArgs<T> a;
     a.P = (const T *)h->state[CMI_STATE_P];
     a.Q = (const T *)h->state[CMI_STATE_Q];
@@ -1737,23 +1722,47 @@ static hipError_t run_eval(cmi_instance *h, int64_t n, const int32_t *du, const 
     a.condBias = (const T *)h->state[CMI_STATE_COND_BIAS];
     a.ucBias = (const T *)h->state[CMI_STATE_UC_BIAS];
     a.icBias = (const T *)h->state[CMI_STATE_IC_BIAS];
-    a.u = du;
-    a.j = dj;
-    a.ctx = dctx;
-    a.r = dr;
     a.ctx_ptr = h->d_ctx_ptr;
     a.ctx_conds = h->d_ctx_conds;
-    a.preds = dpreds;
-    a.part = dpart;
-    a.gm = h->hp.gm;
-    a.lo = lo;
-    a.hi = hi;
-    a.min_rate = min_rate;
+    a.io = io;
     a.k = h->k;
     a.n_conds = h->n_conds;
-    a.bound = bound;
     a.model = h->model;
     return launch_eval<T>(a, n, h->stream);
+}
+
+// One evaluation over tuples on the device, for `fn`: the model table made current, eval_kernel / ext_eval_kernel, and where the tuples
+// carry ratings the block partials copied back and folded into sums in block order (the stream is drained for that).  Predictions, where
+// asked for, stay on the device in dpreds.
+static int eval_run(cmi_instance *h, const char *fn, const AbiTuples &t, double *dpreds, int bound, double lo, double hi, double min_rate,
+                    double sums[5]) {
+    if (int rc = abi_hip(h->err, fn, hipSetDevice(h->device))) return rc;
+    if (int rc = cmi_sync_table_from_arena(h)) return rc;
+    const EvalIO io = cmi_eval_io(h, t, dpreds, bound, lo, hi, min_rate);
+    hipError_t e = h->f64 ? launch_eval_model<double>(h, io, t.n) : launch_eval_model<float>(h, io, t.n);
+    if (!t.part) return abi_hip(h->err, fn, e);
+    const int blocks = eval_blocks(t.n);
+    std::vector<double> part((size_t)blocks * 5);
+    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), t.part, part.size() * 8, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream); // whatever failed: the copy writes into part until then
+    if (int rc = abi_hip(h->err, fn, e == hipSuccess ? es : e)) return rc;
+    for (int b = 0; b < blocks; ++b)
+        for (int c = 0; c < 5; ++c) sums[c] += part[(size_t)b * 5 + c];
+    return CMI_OK;
+}
+
+// the tuples of `fn` (the caller has seen the arrays it needs): a contextual model has its context table, and every id is inside the
+// handle's sizes
+static int check_tuples(cmi_instance *h, const char *fn, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx) {
+    const bool contextual = !is_2d_model(h->model);
+    if (contextual && !h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "%s: the context table comes from cmi_set_ratings; call it first", fn);
+    for (int64_t t = 0; t < n; ++t) {
+        if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items)
+            CMI_FAIL(h, CMI_E_INVALID, "%s: user/item id out of range at tuple %lld", fn, (long long)t);
+        if (contextual && (ctx[t] < 0 || ctx[t] >= h->n_ctx))
+            CMI_FAIL(h, CMI_E_INVALID, "%s: context id %d out of range at tuple %lld", fn, ctx[t], (long long)t);
+    }
+    return CMI_OK;
 }
 
 static int eval_common(cmi_instance *h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
@@ -1763,45 +1772,12 @@ static int eval_common(cmi_instance *h, int64_t n, const int32_t *u, const int32
     if (h->model == CMI_MODEL_SVDPP && !h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "eval: SVD++ predicts with the users' training items; call cmi_set_ratings first");
     if (n < 0 || (n > 0 && (!u || !j))) CMI_FAIL(h, CMI_E_INVALID, "eval: null tuple arrays");
     if (contextual && n > 0 && !ctx) CMI_FAIL(h, CMI_E_INVALID, "eval: ctx required for model %d", h->model);
-    if (contextual && !h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "eval: the context table comes from cmi_set_ratings; call it first");
-    for (int64_t t = 0; t < n; ++t) {
-        if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items)
-            CMI_FAIL(h, CMI_E_INVALID, "eval: user/item id out of range at tuple %lld", (long long)t);
-        if (contextual && (ctx[t] < 0 || ctx[t] >= h->n_ctx))
-            CMI_FAIL(h, CMI_E_INVALID, "eval: context id %d out of range at tuple %lld", ctx[t], (long long)t);
-    }
+    if (int rc = check_tuples(h, "eval", n, u, j, ctx)) return rc;
     for (int c = 0; c < 5; ++c) sums[c] = 0.0;
     if (n == 0) return CMI_OK;
-    CMI_HIP(h, hipSetDevice(h->device));
-    if (int rc = cmi_sync_table_from_arena(h)) return rc;
-    int32_t *du = nullptr, *dj = nullptr, *dctx = nullptr;
-    double *dr = nullptr, *dpreds = nullptr, *dpart = nullptr;
-    const int blocks = eval_blocks(n);
-    std::vector<double> part((size_t)blocks * 5);
-    hipError_t e = hipMalloc((void **)&du, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dj, (size_t)n * 4);
-    if (e == hipSuccess && contextual) e = hipMalloc((void **)&dctx, (size_t)n * 4);
-    if (e == hipSuccess && r) e = hipMalloc((void **)&dr, (size_t)n * 8);
-    if (e == hipSuccess && preds_out) e = hipMalloc((void **)&dpreds, (size_t)n * 8);
-    if (e == hipSuccess && r) e = hipMalloc((void **)&dpart, part.size() * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(du, u, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dj, j, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && contextual) e = hipMemcpyAsync(dctx, ctx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && r) e = hipMemcpyAsync(dr, r, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess)
-        e = h->f64 ? run_eval<double>(h, n, du, dj, dctx, dr, dpreds, dpart, bound, lo, hi, min_rate)
-                   : run_eval<float>(h, n, du, dj, dctx, dr, dpreds, dpart, bound, lo, hi, min_rate);
-    if (e == hipSuccess && preds_out) e = hipMemcpyAsync(preds_out, dpreds, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && r) e = hipMemcpyAsync(part.data(), dpart, part.size() * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    void *ptrs[] = {du, dj, dctx, dr, dpreds, dpart};
-    for (void *p : ptrs)
-        if (p) hipFree(p);
-    CMI_HIP(h, e);
-    if (r)
-        for (int b = 0; b < blocks; ++b)
-            for (int c = 0; c < 5; ++c) sums[c] += part[(size_t)b * 5 + c];
-    return CMI_OK;
+    return abi_predict(h, "eval", n, u, j, contextual ? ctx : nullptr, r, (size_t)eval_blocks(n) * 5, preds_out, [&](const AbiTuples &t, double *dpreds) {
+        return eval_run(h, "eval", t, dpreds, bound, lo, hi, min_rate, sums);
+    });
 }
 
 extern "C" int cmi_predict_batch(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
@@ -1814,32 +1790,23 @@ extern "C" int cmi_predict_batch(cmi_handle h, int64_t n, const int32_t *u, cons
     });
 }
 
-extern "C" int cmi_eval_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
-                                const double *r, double min_rate, double max_rate, double *out, int64_t *count) {
-    if (!h) return CMI_E_INVALID;
-    return abi_barrier(h->err, "eval_ratings", [&] {
-        if (!out || (n > 0 && !r)) CMI_FAIL(h, CMI_E_INVALID, "eval_ratings: null argument");
-        double sums[5];
-        if (int rc = eval_common(h, n, u, j, ctx, r, 1, min_rate, max_rate, min_rate, nullptr, sums)) return rc;
-        const double cnt = sums[4];
-        const double mae = sums[0] / cnt;
-        out[0] = mae;
-        out[1] = std::sqrt(sums[1] / cnt);
-        out[2] = mae / (max_rate - min_rate);
-        out[3] = sums[2] / cnt;
-        out[4] = std::sqrt(sums[3] / cnt);
-        if (count) *count = (int64_t)cnt;
-        return CMI_OK;
-    });
-}
-
 // the five sums behind cmi_eval_ratings (sum|e|, sum e^2, rounded forms, count), so that cmi_group_eval_ratings can merge shards exactly
 int cmi_eval_sums(cmi_instance *h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r, double min_rate,
                   double max_rate, double sums[5]) {
     return eval_common(h, n, u, j, ctx, r, 1, min_rate, max_rate, min_rate, nullptr, sums);
 }
 
-// ---- host-only schedule export ------------------------------------------------------------------------
+extern "C" int cmi_eval_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
+                                const double *r, double min_rate, double max_rate, double *out, int64_t *count) {
+    if (!h) return CMI_E_INVALID;
+    return abi_barrier(h->err, "eval_ratings", [&] {
+        if (!out || (n > 0 && !r)) CMI_FAIL(h, CMI_E_INVALID, "eval_ratings: null argument");
+        double sums[5];
+        if (int rc = cmi_eval_sums(h, n, u, j, ctx, r, min_rate, max_rate, sums)) return rc;
+        cmi_eval_measures(sums, min_rate, max_rate, out, count);
+        return CMI_OK;
+    });
+}
 
 // ---- resident test tuples: `--early-stop MAE|RMSE` evaluates the test set after EVERY epoch (IterativeRecommender.java:
 // 156-161); uploading it once instead of per call keeps that loop on the device
@@ -1847,53 +1814,26 @@ int cmi_eval_sums(cmi_instance *h, int64_t n, const int32_t *u, const int32_t *j
 extern "C" int cmi_set_eval_ratings(cmi_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                     const double *r) {
     if (!h) return CMI_E_INVALID;
-    const bool contextual = !is_2d_model(h->model);
-    if (n < 0 || (n > 0 && (!u || !j || !r || (contextual && !ctx)))) CMI_FAIL(h, CMI_E_INVALID, "set_eval_ratings: null arrays");
-    if (contextual && !h->have_ratings) CMI_FAIL(h, CMI_E_INVALID, "set_eval_ratings: the context table comes from cmi_set_ratings; call it first");
-    for (int64_t t = 0; t < n; ++t) {
-        if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items)
-            CMI_FAIL(h, CMI_E_INVALID, "set_eval_ratings: user/item id out of range at tuple %lld", (long long)t);
-        if (contextual && (ctx[t] < 0 || ctx[t] >= h->n_ctx))
-            CMI_FAIL(h, CMI_E_INVALID, "set_eval_ratings: context id %d out of range at tuple %lld", ctx[t], (long long)t);
-    }
-    CMI_HIP(h, hipSetDevice(h->device));
-    CMI_HIP(h, hipStreamSynchronize(h->stream));
-    free_eval_set(h);
-    if (n == 0) return CMI_OK;
-    hipError_t e = hipMalloc((void **)&h->d_eu, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_ej, (size_t)n * 4);
-    if (e == hipSuccess && contextual) e = hipMalloc((void **)&h->d_ectx, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_er, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->d_epart, (size_t)eval_blocks(n) * 5 * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_eu, u, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_ej, j, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && contextual) e = hipMemcpyAsync(h->d_ectx, ctx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(h->d_er, r, (size_t)n * 8, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        free_eval_set(h);
-        CMI_FAIL(h, CMI_E_HIP, "set_eval_ratings: %s", hipGetErrorString(e));
-    }
-    h->n_eval = n;
-    return CMI_OK;
+    return abi_barrier(h->err, "set_eval_ratings", [&] {
+        const bool contextual = !is_2d_model(h->model);
+        if (n < 0 || (n > 0 && (!u || !j || !r || (contextual && !ctx)))) CMI_FAIL(h, CMI_E_INVALID, "set_eval_ratings: null arrays");
+        if (int rc = check_tuples(h, "set_eval_ratings", n, u, j, ctx)) return rc;
+        CMI_HIP(h, hipSetDevice(h->device));
+        CMI_HIP(h, hipStreamSynchronize(h->stream));
+        h->eval_set.release();
+        if (n == 0) return CMI_OK;
+        hipError_t e = h->eval_set.upload(n, u, j, contextual ? ctx : nullptr, r, (size_t)eval_blocks(n) * 5, nullptr, h->stream);
+        const hipError_t es = hipStreamSynchronize(h->stream);
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) h->eval_set.release();
+        return abi_hip(h->err, "set_eval_ratings", e);
+    });
 }
 
 int cmi_eval_resident_sums(cmi_instance *h, double min_rate, double max_rate, double sums[5]) {
-    if (h->n_eval <= 0) CMI_FAIL(h, CMI_E_INVALID, "eval_resident: call cmi_set_eval_ratings first");
-    CMI_HIP(h, hipSetDevice(h->device));
-    if (int rc = cmi_sync_table_from_arena(h)) return rc;
-    const int64_t n = h->n_eval;
-    const int blocks = eval_blocks(n);
-    std::vector<double> part((size_t)blocks * 5);
-    hipError_t e = h->f64 ? run_eval<double>(h, n, h->d_eu, h->d_ej, h->d_ectx, h->d_er, nullptr, h->d_epart, 1, min_rate, max_rate, min_rate)
-                          : run_eval<float>(h, n, h->d_eu, h->d_ej, h->d_ectx, h->d_er, nullptr, h->d_epart, 1, min_rate, max_rate, min_rate);
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), h->d_epart, part.size() * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    CMI_HIP(h, e);
+    if (h->eval_set.n <= 0) CMI_FAIL(h, CMI_E_INVALID, "eval_resident: call cmi_set_eval_ratings first");
     for (int c = 0; c < 5; ++c) sums[c] = 0.0;
-    for (int b = 0; b < blocks; ++b)
-        for (int c = 0; c < 5; ++c) sums[c] += part[(size_t)b * 5 + c];
-    return CMI_OK;
+    return eval_run(h, "eval_resident", h->eval_set, nullptr, 1, min_rate, max_rate, min_rate, sums);
 }
 
 extern "C" int cmi_eval_resident(cmi_handle h, double min_rate, double max_rate, double out[5], int64_t *count) {
@@ -1901,17 +1841,12 @@ extern "C" int cmi_eval_resident(cmi_handle h, double min_rate, double max_rate,
     return abi_barrier(h->err, "eval_resident", [&] {
         double sums[5];
         if (int rc = cmi_eval_resident_sums(h, min_rate, max_rate, sums)) return rc;
-        const double cnt = sums[4];
-        const double mae = sums[0] / cnt;
-        out[0] = mae;
-        out[1] = std::sqrt(sums[1] / cnt);
-        out[2] = mae / (max_rate - min_rate);
-        out[3] = sums[2] / cnt;
-        out[4] = std::sqrt(sums[3] / cnt);
-        if (count) *count = (int64_t)cnt;
+        cmi_eval_measures(sums, min_rate, max_rate, out, count);
         return CMI_OK;
     });
 }
+
+// ---- host-only schedule export ------------------------------------------------------------------------
 
 extern "C" int cmi_level_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items,
                                   int order, int32_t *perm, int64_t *level_off, int64_t level_cap,

@@ -5,11 +5,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <functional>
 #include <string>
 #include <vector>
 
+#include "abi.hpp"
 #include "mf_sgd_kernels.hpp"
 
 // The epoch form cmi_set_ratings chose (the caller's request stays in cmi_instance::flags, CMI_FLAG_SCHED_*)
@@ -86,10 +88,7 @@ struct cmi_instance {
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool have_ratings = false, epoch_timed = false;
     double last_loss = 0.0;
-    // resident test tuples (cmi_set_eval_ratings)
-    int32_t *d_eu = nullptr, *d_ej = nullptr, *d_ectx = nullptr;
-    double *d_er = nullptr, *d_epart = nullptr;
-    int64_t n_eval = 0;
+    AbiTuples eval_set; // resident test tuples (cmi_set_eval_ratings); n == 0: none
     // multi-GPU exchange of the item-side containers (cmi_exchange_*): bucket and snapshot share one layout
     void *d_xbucket = nullptr, *d_xsnap = nullptr;
     int64_t x_count = 0;
@@ -110,10 +109,12 @@ struct cmi_instance {
 };
 
 bool cmi_model_has(int model, int which); // which containers a model owns (cmi_api.cpp)
-// evaluation-side view of an SVD++ / CAMF_*CS instance (cmi_api.cpp); the tuple / output pointers may be null for the ranking operands
+// the tuple / output / scale side of an evaluation launch (cmi_api.cpp).  The ranking operands take the defaults: no tuples, gm alone
+cmi::EvalIO cmi_eval_io(cmi_instance *h, const AbiTuples &t = {}, double *dpreds = nullptr, int bound = 0, double lo = 0, double hi = 0,
+                        double min_rate = 1);
+// evaluation-side view of an SVD++ / CAMF_*CS instance (cmi_api.cpp)
 template <typename T>
-cmi::ExtEvalArgs<T> cmi_ext_eval_args(cmi_instance *h, const int32_t *du, const int32_t *dj, const int32_t *dctx, const double *dr,
-                                      double *dpreds, double *dpart, int bound, double lo, double hi, double min_rate);
+cmi::ExtEvalArgs<T> cmi_ext_eval_args(cmi_instance *h, const cmi::EvalIO &io);
 
 // IterativeRecommender.isConverged + updateLRate around an epoch function (cmi_api.cpp; shared by cmi_train_from and cmi_group_train_from)
 int cmi_train_loop(const std::function<int(double, double *)> &epoch, std::string &err, int first_iter, double prev_loss, int num_iters,
@@ -121,9 +122,20 @@ int cmi_train_loop(const std::function<int(double, double *)> &epoch, std::strin
                    int *iters_run, double *final_lrate);
 int cmi_eval_sums(cmi_instance *h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx, const double *r, double min_rate,
                   double max_rate, double sums[5]);
-
 // the sums of cmi_eval_resident before they are turned into measures (a group adds them over its shards)
 int cmi_eval_resident_sums(cmi_instance *h, double min_rate, double max_rate, double sums[5]);
+// Recommender.evalRatings' end (Recommender.java:548-560): the sums (sum|e|, sum e^2, their rounded forms, count) as MAE, RMSE, NMAE, rMAE,
+// rRMSE and the count.  No tuple counted: 0 / 0, as in the Java
+inline void cmi_eval_measures(const double sums[5], double min_rate, double max_rate, double out[5], int64_t *count) {
+    const double cnt = sums[4];
+    const double mae = sums[0] / cnt;
+    out[0] = mae;
+    out[1] = std::sqrt(sums[1] / cnt);
+    out[2] = mae / (max_rate - min_rate);
+    out[3] = sums[2] / cnt;
+    out[4] = std::sqrt(sums[3] / cnt);
+    if (count) *count = (int64_t)cnt;
+}
 // cmi_comm_* (group_api.cpp, which owns the RCCL types): destroy the handle's communicator, if any
 void cmi_comm_release(cmi_instance *h);
 

@@ -330,13 +330,12 @@ __global__ __launch_bounds__(64) void ext_serial_wave(ExtArgs<T> a, int64_t n, d
 
 template <typename T>
 __global__ __launch_bounds__(256) void ext_eval_kernel(ExtEvalArgs<T> a, int64_t n) {
-    __shared__ double s_part[4][5];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * 4;
-    double s_abs = 0, s_sq = 0, s_rabs = 0, s_rsq = 0, s_cnt = 0;
+    EvalSums sums;
     const int k = a.k;
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < n; t += stride) {
-        const int uu = a.u[t], jj = a.j[t];
+        const int uu = a.io.u[t], jj = a.io.j[t];
         const T *pu = a.P + (size_t)uu * k, *qj = a.Q + (size_t)jj * k;
         double part = 0.0;
         for (int f = lane; f < k; f += 64) part += (double)pu[f] * (double)qj[f];
@@ -349,9 +348,9 @@ __global__ __launch_bounds__(256) void ext_eval_kernel(ExtEvalArgs<T> a, int64_t
                 const T *y = a.Y + (size_t)a.ui_items[q] * k;
                 for (int f = lane; f < k; f += 64) yq += (double)y[f] * (double)qj[f];
             }
-            pred = ((a.gm + (double)a.userBias[uu]) + (double)a.itemBias[jj]) + pred + (e > b ? wave_sum64(yq) / w : 0.0);
+            pred = ((a.io.gm + (double)a.userBias[uu]) + (double)a.itemBias[jj]) + pred + (e > b ? wave_sum64(yq) / w : 0.0);
         } else {
-            const int c = a.ctx[t];
+            const int c = a.io.ctx[t];
             const int32_t b = a.ctx_ptr[c], e = a.ctx_ptr[c + 1];
             double dist = 0.0;
             for (int32_t q = b; q < e && q - b < a.n_empty; ++q) {
@@ -368,36 +367,9 @@ __global__ __launch_bounds__(256) void ext_eval_kernel(ExtEvalArgs<T> a, int64_t
             }
             if (a.model == CAMF_MCS) pred *= 1.0 - sqrt(dist);
         }
-        if (a.bound) {
-            if (pred > a.hi) pred = a.hi;
-            if (pred < a.lo) pred = a.lo;
-        }
-        if (a.preds && lane == 0) a.preds[t] = pred;
-        if (a.r && !isnan(pred)) {
-            const double rate = a.r[t];
-            const double rpred = floor(pred / a.min_rate + 0.5) * a.min_rate;
-            const double err = fabs(rate - pred), rerr = fabs(rate - rpred);
-            s_abs += err;
-            s_sq += err * err;
-            s_rabs += rerr;
-            s_rsq += rerr * rerr;
-            s_cnt += 1.0;
-        }
+        eval_tuple(a.io, t, lane, pred, sums);
     }
-    if (a.part) {
-        if (lane == 0) {
-            s_part[wave][0] = s_abs;
-            s_part[wave][1] = s_sq;
-            s_part[wave][2] = s_rabs;
-            s_part[wave][3] = s_rsq;
-            s_part[wave][4] = s_cnt;
-        }
-        __syncthreads();
-        if (threadIdx.x < 5) {
-            const int c = threadIdx.x;
-            a.part[(size_t)blockIdx.x * 5 + c] = ((s_part[0][c] + s_part[1][c]) + s_part[2][c]) + s_part[3][c];
-        }
-    }
+    eval_block_store(a.io, wave, lane, sums);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -459,7 +431,7 @@ __global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int3
         }
         dst[f] = (T)v;
     }
-    if (threadIdx.x == 0) row_const[blockIdx.x] = a.model == SVDPP ? (T)(a.gm + (double)a.userBias[u]) : (T)0;
+    if (threadIdx.x == 0) row_const[blockIdx.x] = a.model == SVDPP ? (T)(a.io.gm + (double)a.userBias[u]) : (T)0;
 }
 
 template <typename T>

@@ -1009,30 +1009,18 @@ extern "C" int cmi_fm_synchronize(cmi_fm_handle h) {
 extern "C" int cmi_fm_predict_batch(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                                     int bound, double lo, double hi, double *out) {
     if (!h) return CMI_E_INVALID;
-    if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
-    if (n < 0 || (n > 0 && (!u || !j || !ctx || !out))) CMI_FAIL(h, CMI_E_INVALID, "fm_predict: null arrays");
-    for (int64_t t = 0; t < n; ++t)
-        if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || ctx[t] < 0)
-            CMI_FAIL(h, CMI_E_INVALID, "fm_predict: id out of range at tuple %lld", (long long)t);
-    if (n == 0) return CMI_OK;
-    CMI_HIP(h, hipSetDevice(h->device));
-    if (int rc = fm_sync_V(h)) return rc;
-    int32_t *du = nullptr, *dj = nullptr, *dc = nullptr;
-    double *dout = nullptr;
-    hipError_t e = hipMalloc((void **)&du, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dj, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dc, (size_t)n * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&dout, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMemcpyAsync(du, u, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dj, j, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dc, ctx, (size_t)n * 4, hipMemcpyHostToDevice, h->stream);
-    FmArgs a = fm_args(h);
-    if (e == hipSuccess) e = fm_launch_predict(a, n, du, dj, dc, bound, lo, hi, dout, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, dout, (size_t)n * 8, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    abi_free(du, dj, dc, dout);
-    CMI_HIP(h, e);
-    return CMI_OK;
+    return abi_barrier(h->err, "fm_predict_batch", [&] {
+        if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
+        if (n < 0 || (n > 0 && (!u || !j || !ctx || !out))) CMI_FAIL(h, CMI_E_INVALID, "fm_predict: null arrays");
+        for (int64_t t = 0; t < n; ++t)
+            if (u[t] < 0 || u[t] >= h->n_users || j[t] < 0 || j[t] >= h->n_items || ctx[t] < 0)
+                CMI_FAIL(h, CMI_E_INVALID, "fm_predict: id out of range at tuple %lld", (long long)t);
+        if (n == 0) return CMI_OK;
+        return abi_predict(h, "fm_predict", n, u, j, ctx, nullptr, 0, out, [&](const AbiTuples &t, double *d_out) {
+            if (int rc = fm_sync_V(h)) return rc;
+            return abi_hip(h->err, "fm_predict", fm_launch_predict(fm_args(h), n, t.a, t.b, t.c, bound, lo, hi, d_out, h->stream));
+        });
+    });
 }
 
 // Recommender.evalRankings for the FM recommender (Recommender.java:668-964 with FM.predict, FM.java:93-113): the driver of

@@ -45,6 +45,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eval_device.hpp"
 #include "fm_kernels.hpp"
 
 namespace cmi {
@@ -615,11 +616,7 @@ __global__ __launch_bounds__(256) void fm_predict_kernel(FmArgs a, int64_t n, co
             pred += a.w[a.n_users + j];
             if (has_c) pred += a.w[a.n_users + a.n_items + c] * a.xc;
             pred += 0.5 * pair;
-            if (bound) {
-                if (pred > hi) pred = hi;
-                if (pred < lo) pred = lo;
-            }
-            out[i] = pred;
+            out[i] = bound_to_scale(pred, bound, lo, hi);
         }
     }
 }

@@ -617,13 +617,7 @@ extern "C" int cmi_group_eval_ratings(cmi_group_handle g, int64_t n, const int32
             GRP_MEMBER(g, s, cmi_eval_sums(g->inst[s], m, ro.u[s].data(), ro.j[s].data(), ctx ? ro.c[s].data() : nullptr, ro.r[s].data(), min_rate, max_rate, sums));
             for (int c = 0; c < 5; ++c) tot[c] += sums[c];
         }
-        const double cnt = tot[4], mae = tot[0] / cnt;
-        out[0] = mae;
-        out[1] = std::sqrt(tot[1] / cnt);
-        out[2] = mae / (max_rate - min_rate);
-        out[3] = tot[2] / cnt;
-        out[4] = std::sqrt(tot[3] / cnt);
-        if (count) *count = (int64_t)cnt;
+        cmi_eval_measures(tot, min_rate, max_rate, out, count);
         return CMI_OK;
     });
 }
@@ -687,23 +681,19 @@ extern "C" int cmi_group_set_eval_ratings(cmi_group_handle g, int64_t n, const i
 
 extern "C" int cmi_group_eval_resident(cmi_group_handle g, double min_rate, double max_rate, double out[5], int64_t *count) {
     if (!g || !out) return CMI_E_INVALID;
-    if (int rc = need_ratings(g, "group_eval_resident")) return rc;
-    double tot[5] = {0, 0, 0, 0, 0};
-    for (size_t s = 0; s < g->inst.size(); ++s) { // sums in shard order: deterministic
-        if (g->inst[s]->n_eval <= 0) continue;    // a shard that owns none of the test users
-        double sums[5];
-        GRP_MEMBER(g, s, cmi_eval_resident_sums(g->inst[s], min_rate, max_rate, sums));
-        for (int c = 0; c < 5; ++c) tot[c] += sums[c];
-    }
-    if (!(tot[4] > 0)) CMI_FAIL(g, CMI_E_INVALID, "group_eval_resident: call cmi_group_set_eval_ratings first");
-    const double cnt = tot[4], mae = tot[0] / cnt;
-    out[0] = mae;
-    out[1] = std::sqrt(tot[1] / cnt);
-    out[2] = mae / (max_rate - min_rate);
-    out[3] = tot[2] / cnt;
-    out[4] = std::sqrt(tot[3] / cnt);
-    if (count) *count = (int64_t)cnt;
-    return CMI_OK;
+    return abi_barrier(g->err, "group_eval_resident", [&] {
+        if (int rc = need_ratings(g, "group_eval_resident")) return rc;
+        double tot[5] = {0, 0, 0, 0, 0};
+        for (size_t s = 0; s < g->inst.size(); ++s) {    // sums in shard order: deterministic
+            if (g->inst[s]->eval_set.n <= 0) continue; // a shard that owns none of the test users
+            double sums[5];
+            GRP_MEMBER(g, s, cmi_eval_resident_sums(g->inst[s], min_rate, max_rate, sums));
+            for (int c = 0; c < 5; ++c) tot[c] += sums[c];
+        }
+        if (!(tot[4] > 0)) CMI_FAIL(g, CMI_E_INVALID, "group_eval_resident: call cmi_group_set_eval_ratings first");
+        cmi_eval_measures(tot, min_rate, max_rate, out, count);
+        return CMI_OK;
+    });
 }
 
 // ---- cmi_comm_*: the same exchange for the one-process-per-GPU form (carskit_amd/dist.py, bench.py --gpus N under

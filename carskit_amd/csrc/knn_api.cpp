@@ -166,7 +166,7 @@ static int knn_predict_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const
     double *s_sim = nullptr, *s_rate = nullptr;
     const size_t ns = (size_t)nwaves * cap;
     int32_t bad = 0;
-    const int rc = pair_predict(h, "cmi_knn_predict_batch", n, owner, target, out, [&](int32_t *d_owner, int32_t *d_target, double *d_out) {
+    const int rc = abi_predict(h, "cmi_knn_predict_batch", n, owner, target, nullptr, nullptr, 0, out, [&](const AbiTuples &t, double *d_out) {
         hipError_t e = hipMalloc((void **)&d_bad, 4);
         if (e == hipSuccess) e = hipMalloc((void **)&s_key, ns * 4);
         if (e == hipSuccess) e = hipMalloc((void **)&s_pos, ns * 4);
@@ -175,10 +175,10 @@ static int knn_predict_impl(cmi_knn_handle h, int64_t n, const int32_t *u, const
         if (e == hipSuccess) e = hipMalloc((void **)&s_rate, ns * 8);
         if (e == hipSuccess) e = hipMemsetAsync(d_bad, 0, 4, h->stream);
         if (e == hipSuccess)
-            e = knn_launch_predict(PairCsr{h->d_lptr, h->d_lidx, h->d_lval}, h->d_S, h->n_ent, h->d_mean, n, d_owner, d_target, knn, gm,
+            e = knn_launch_predict(PairCsr{h->d_lptr, h->d_lidx, h->d_lval}, h->d_S, h->n_ent, h->d_mean, n, t.a, t.b, knn, gm,
                                    bound, lo, hi, d_out, nwaves, cap, s_key, s_sim, s_rate, s_pos, s_sel, d_bad, h->stream);
         if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, h->stream);
-        return e;
+        return abi_hip(h->err, "cmi_knn_predict_batch", e);
     });
     abi_free(d_bad, s_key, s_pos, s_sel, s_sim, s_rate); // the stream is drained
     if (rc != CMI_OK) return rc;

@@ -3,6 +3,7 @@
 // every per-pair sum runs sequentially in one lane along the ascending contracted index (no lane-split reductions, no FMA:
 // -ffp-contract=off), and division / sqrt are the correctly rounded IEEE operations Java uses.
 #include "knn_kernels.hpp"
+#include "eval_device.hpp"
 #include "../../include/carskit_mi355x.h"
 
 namespace cmi {
@@ -267,7 +268,7 @@ __global__ __launch_bounds__(64) void knn_predict_kernel(PairCsr L, const double
             }
         }
         if (lane == 0) {
-            pred = pair_bound(pred, bound, lo, hi);
+            pred = bound_to_scale(pred, bound, lo, hi);
             if (tree) {
                 atomicAdd(bad, 1);
                 pred = __builtin_nan("");

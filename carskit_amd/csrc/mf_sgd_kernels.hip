@@ -934,27 +934,26 @@ __global__ __launch_bounds__(256) void delta_apply_f32x4(float4 *__restrict__ st
 
 template <typename T>
 __global__ __launch_bounds__(256) void eval_kernel(EvalArgs<T> a, int64_t n) {
-    __shared__ double s_part[4][5];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t stride = (int64_t)gridDim.x * 4;
-    double s_abs = 0, s_sq = 0, s_rabs = 0, s_rsq = 0, s_cnt = 0;
+    EvalSums sums;
     const int k = a.k;
     const int model = a.model;
     const bool has_bu = model == BIASEDMF || model == CAMF_C || model == CAMF_CI;
     const bool has_bj = model == BIASEDMF || model == CAMF_C || model == CAMF_CU;
     for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < n; t += stride) {
-        const int uu = a.u[t], jj = a.j[t];
+        const int uu = a.io.u[t], jj = a.io.j[t];
         const T *pu = a.P + (size_t)uu * k;
         const T *qj = a.Q + (size_t)jj * k;
         double part = 0.0;
         for (int f = lane; f < k; f += 64) part += (double)pu[f] * (double)qj[f];
         const double dot = wave_sum64(part);
-        double pred = a.gm;
+        double pred = a.io.gm;
         if (has_bu) pred += (double)a.userBias[uu];
         if (has_bj) pred += (double)a.itemBias[jj];
         pred += dot;
         if (model != BIASEDMF && model != PMF) {
-            const int c = a.ctx[t];
+            const int c = a.io.ctx[t];
             for (int q = a.ctx_ptr[c]; q < a.ctx_ptr[c + 1]; ++q) {
                 const int cond = a.ctx_conds[q];
                 if (model == CAMF_C) pred += (double)a.condBias[cond];
@@ -963,36 +962,9 @@ __global__ __launch_bounds__(256) void eval_kernel(EvalArgs<T> a, int64_t n) {
                 else pred += (double)a.icBias[(size_t)jj * a.n_conds + cond] + (double)a.ucBias[(size_t)uu * a.n_conds + cond];
             }
         }
-        if (a.bound) {
-            if (pred > a.hi) pred = a.hi;
-            if (pred < a.lo) pred = a.lo;
-        }
-        if (a.preds && lane == 0) a.preds[t] = pred;
-        if (a.r && !isnan(pred)) {
-            const double rate = a.r[t];
-            const double rpred = floor(pred / a.min_rate + 0.5) * a.min_rate; // Math.round(x)*minRate
-            const double err = fabs(rate - pred), rerr = fabs(rate - rpred);
-            s_abs += err;
-            s_sq += err * err;
-            s_rabs += rerr;
-            s_rsq += rerr * rerr;
-            s_cnt += 1.0;
-        }
+        eval_tuple(a.io, t, lane, pred, sums);
     }
-    if (a.part) {
-        if (lane == 0) {
-            s_part[wave][0] = s_abs;
-            s_part[wave][1] = s_sq;
-            s_part[wave][2] = s_rabs;
-            s_part[wave][3] = s_rsq;
-            s_part[wave][4] = s_cnt;
-        }
-        __syncthreads();
-        if (threadIdx.x < 5) {
-            const int c = threadIdx.x;
-            a.part[(size_t)blockIdx.x * 5 + c] = ((s_part[0][c] + s_part[1][c]) + s_part[2][c]) + s_part[3][c];
-        }
-    }
+    eval_block_store(a.io, wave, lane, sums);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eval_device.hpp"
+
 namespace cmi {
 
 enum Model { BIASEDMF = 0, CAMF_C = 1, CAMF_CI = 2, CAMF_CU = 3, CAMF_CUCI = 4, PMF = 5,
@@ -118,13 +120,9 @@ hipError_t launch_reduce_loss(const double *loss_part, int64_t n_slots, double *
 template <typename T>
 struct EvalArgs {
     const T *P, *Q, *userBias, *itemBias, *condBias, *ucBias, *icBias;
-    const int32_t *u, *j, *ctx;       // n tuples (ctx may be null for BiasedMF)
-    const double *r;                  // may be null (predict only)
     const int32_t *ctx_ptr, *ctx_conds;
-    double *preds;                    // may be null
-    double *part;                     // [blocks x 5] partial sums (abs, sq, rabs, rsq, count); may be null
-    double gm, lo, hi, min_rate;
-    int32_t k, n_conds, bound, model;
+    EvalIO io; // eval_device.hpp
+    int32_t k, n_conds, model;
 };
 int eval_blocks(int64_t n);
 template <typename T>
@@ -161,12 +159,9 @@ hipError_t launch_svdpp_team(const ExtArgs<T> &a, int64_t n, double *loss_out, h
 template <typename T>
 struct ExtEvalArgs {
     const T *P, *Q, *userBias, *itemBias, *Y, *cc, *cf, *cv;
-    const int32_t *u, *j, *ctx;
-    const double *r;
     const int32_t *ctx_ptr, *ctx_conds, *empty_conds, *ui_ptr, *ui_items;
-    double *preds, *part;
-    double gm, lo, hi, min_rate;
-    int32_t k, n_conds, num_f, n_empty, bound, model;
+    EvalIO io; // the ranking operands read io.gm alone
+    int32_t k, n_conds, num_f, n_empty, model;
 };
 template <typename T>
 hipError_t launch_ext_eval(const ExtEvalArgs<T> &a, int64_t n, hipStream_t s);

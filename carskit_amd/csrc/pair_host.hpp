@@ -1,5 +1,5 @@
 // pair_host.hpp -- the host side that the pair-co-occurrence handles share (cmi_knn_*: knn_api.cpp, cmi_slope_*: slopeone_api.cpp): the
-// handle's common state, the ingest of the 2-D train matrix, the dense-matrix reservation, the timed build and the prediction batch.
+// handle's common state, the ingest of the 2-D train matrix, the dense-matrix reservation and the timed build (the prediction batch is abi_predict).
 // Every function that can fail takes the C function's name, `fn`, which opens its messages.  Internal.
 #pragma once
 #include <algorithm>
@@ -145,25 +145,6 @@ int pair_timed_build(PairModelBase *h, Body &&body) {
     CMI_HIP(h, hipStreamSynchronize(h->stream));
     CMI_HIP(h, hipEventElapsedTime(&h->build_ms, h->ev0, h->ev1));
     h->built = true;
-    return CMI_OK;
-}
-
-// predict_batch of n > 0 checked tuples: a and b uploaded, launch(d_a, d_b, d_out) enqueued on h->stream, out copied back.  The stream
-// is drained before anything is freed, whatever failed: the uploads read a and b until then.
-template <typename Launch>
-int pair_predict(PairModelBase *h, const char *fn, int64_t n, const int32_t *a, const int32_t *b, double *out, Launch &&launch) {
-    CMI_HIP(h, hipSetDevice(h->device));
-    int32_t *d_a = nullptr, *d_b = nullptr;
-    double *d_out = nullptr;
-    hipError_t e = abi_upload(&d_a, a, (size_t)n, h->stream);
-    if (e == hipSuccess) e = abi_upload(&d_b, b, (size_t)n, h->stream);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_out, (size_t)n * sizeof(double));
-    if (e == hipSuccess) e = launch(d_a, d_b, d_out);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = es;
-    abi_free(d_a, d_b, d_out);
-    if (e != hipSuccess) CMI_FAIL(h, CMI_E_HIP, "%s: %s", fn, hipGetErrorString(e));
     return CMI_OK;
 }
 

@@ -1,6 +1,5 @@
 // pair_walk.hpp -- the device side that the pair-co-occurrence models share (ItemKNN / UserKNN: knn_kernels.hip, SlopeOne:
-// slopeone_kernels.hip): the CSR they read, the walk over the common entries of an anchor row and its partners, and the bounding of a
-// prediction.
+// slopeone_kernels.hip): the CSR they read and the walk over the common entries of an anchor row and its partners.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -92,15 +91,6 @@ __device__ __forceinline__ void pair_sweep(const PairCsr &R, int a0, int a1, int
         ++gen;
         qa = qb;
     }
-}
-
-// Recommender.predict(u, j, c, true): the prediction bounded to the rating scale
-__device__ __forceinline__ double pair_bound(double pred, int bound, double lo, double hi) {
-    if (bound) {
-        if (pred > hi) pred = hi;
-        if (pred < lo) pred = lo;
-    }
-    return pred;
 }
 
 } // namespace cmi

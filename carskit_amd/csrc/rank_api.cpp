@@ -1066,10 +1066,10 @@ static RankOperands<T> ext_operands(cmi_instance *h, int k_logical) {
     RankOperands<T> ops;
     ops.k_logical = k_logical;
     ops.build_items = [h](T *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
-        return launch_ext_rank_items<T>(cmi_ext_eval_args<T>(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1), dcand, nc, dB, kp, s);
+        return launch_ext_rank_items<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dcand, nc, dB, kp, s);
     };
     ops.build_queries = [h](T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
-        return launch_ext_rank_queries<T>(cmi_ext_eval_args<T>(h, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1), dqu, dqc, n, dA, drc, kp, s);
+        return launch_ext_rank_queries<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dqu, dqc, n, dA, drc, kp, s);
     };
     return ops;
 }

@@ -101,9 +101,10 @@ static int slope_predict_impl(cmi_slope_handle h, int64_t n, const int32_t *u, c
     if (int rc = pair_check_tuples(h, "cmi_slope_predict_batch", n, u, j, out)) return rc;
     if (n == 0) return CMI_OK;
     const int nwaves = (int)std::min<int64_t>(n, 16384); // one wave per tuple in flight
-    return pair_predict(h, "cmi_slope_predict_batch", n, u, j, out, [&](int32_t *d_u, int32_t *d_j, double *d_out) {
-        return slope_launch_predict(PairCsr{h->d_rptr, h->d_ridx, h->d_rval}, h->d_dev, h->d_card, h->n_items, n, d_u, d_j, gm, bound, lo,
-                                    hi, d_out, nwaves, h->stream);
+    return abi_predict(h, "cmi_slope_predict_batch", n, u, j, nullptr, nullptr, 0, out, [&](const AbiTuples &t, double *d_out) {
+        return abi_hip(h->err, "cmi_slope_predict_batch",
+                       slope_launch_predict(PairCsr{h->d_rptr, h->d_ridx, h->d_rval}, h->d_dev, h->d_card, h->n_items, n, t.a, t.b, gm, bound,
+                                            lo, hi, d_out, nwaves, h->stream));
     });
 }
 

@@ -3,6 +3,7 @@
 // prediction's sum in one chain along the ascending item index (no lane-split reductions, no FMA: -ffp-contract=off), and division is
 // the correctly rounded IEEE operation Java uses.
 #include "slopeone_kernels.hpp"
+#include "eval_device.hpp"
 
 namespace cmi {
 
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(64) void slope_predict_kernel(PairCsr R, const doub
             }
         }
         if (lane == 0) {
-            out[t] = pair_bound(cards > 0.0 ? preds / cards : gm, bound, lo, hi);
+            out[t] = bound_to_scale(cards > 0.0 ? preds / cards : gm, bound, lo, hi);
         }
     }
 }
