@@ -177,6 +177,15 @@ SYMBOLS = [
     ("cmi_slope_get_deviation", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("cmi_slope_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _dbl, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_slope_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_nmf_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_nmf_destroy", C.c_int, [_vp]),
+    ("cmi_nmf_last_error", C.c_char_p, [_vp]),
+    ("cmi_nmf_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_nmf_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_nmf_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_nmf_iterate", C.c_int, [_vp, C.POINTER(_dbl)]),
+    ("cmi_nmf_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_nmf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -916,7 +925,7 @@ def knn_measure(name):
 
 
 class _PairModel(_Handle):
-    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*)."""
+    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*, cmi_nmf_*)."""
 
     _prefix = ""
 
@@ -994,3 +1003,52 @@ class SlopeOneInstance(_PairModel):
 
     def predict(self, u, j, global_mean, bound=False, lo=1.0, hi=5.0):
         return self._predict(u, j, global_mean=global_mean, bound=bound, lo=lo, hi=hi)
+
+
+class NMFInstance(_PairModel):
+    """The reference's NMF on one GPU (a `cmi_nmf_handle`): W is (n_users, k), H is (k, n_items), 1 <= k <= 256."""
+
+    _api = ("cmi_nmf_create", "cmi_nmf_destroy", "cmi_nmf_last_error")
+    _prefix = "cmi_nmf"
+
+    def __init__(self, k, n_users, n_items, device=0, flags=0):
+        self.k, self.n_users, self.n_items = k, n_users, n_items
+        super().__init__(k, n_users, n_items, device, flags)
+
+    def _shaped(self, a, shape, name):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.shape != shape:
+            raise CmiError(E_INVALID, "%s has shape %s, not %s" % (name, a.shape, shape))
+        return a
+
+    def set_model(self, W=None, H=None):
+        W = self._shaped(W, (self.n_users, self.k), "W")
+        H = self._shaped(H, (self.k, self.n_items), "H")
+        self._chk(self.L.cmi_nmf_set_model(self.h, None if W is None else _p(W), None if H is None else _p(H)))
+
+    def model(self):
+        """(W, H)"""
+        W, H = np.empty((self.n_users, self.k)), np.empty((self.k, self.n_items))
+        self._chk(self.L.cmi_nmf_get_model(self.h, _p(W), _p(H)))
+        return W, H
+
+    def iterate(self):
+        """one W phase, H phase and loss; returns the loss (a NaN / Inf loss raises E_NUMERIC)"""
+        loss = _dbl()
+        self._chk(self.L.cmi_nmf_iterate(self.h, C.byref(loss)))
+        return loss.value
+
+    def predict(self, u, j, bound=False, lo=1.0, hi=5.0):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_nmf_predict_batch(self.h, len(u), _p(u), _p(j), 1 if bound else 0, float(lo), float(hi), _p(out)))
+        return out
+
+    def last_iter_ms(self):
+        """(W phase, H phase, loss) device milliseconds of the last iterate()"""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.cmi_nmf_last_iter_ms(self.h, ms))
+        return tuple(ms)

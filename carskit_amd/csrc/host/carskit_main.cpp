@@ -105,6 +105,11 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
             throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of SlopeOne is not accelerated yet");
         if (a == "slopeone" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": SlopeOne runs on one GPU");
+        // NMF: the same two refusals
+        if (a == "nmf" && conf.isRankingPred)
+            throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of NMF is not accelerated yet");
+        if (a == "nmf" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": NMF runs on one GPU");
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData

@@ -474,9 +474,11 @@ class IterativeRecommender {
         const float delta_measure = (float)(last_measure - measure);
         if (conf_.verbose && log_) {
             char buf[256];
-            snprintf(buf, sizeof buf, "%s%s iter %d: loss = %g, delta_loss = %g, learn_rate = %g", algoName.c_str(),
-                     fold_ > 0 ? (" fold [" + std::to_string(fold_) + "]").c_str() : "", iter, (double)(float)loss,
-                     (double)delta_loss, (double)(float)lRate);
+            int len = snprintf(buf, sizeof buf, "%s%s iter %d: loss = %g, delta_loss = %g", algoName.c_str(),
+                               fold_ > 0 ? (" fold [" + std::to_string(fold_) + "]").c_str() : "", iter, (double)(float)loss,
+                               (double)delta_loss);
+            if (lRate > 0 && len > 0 && len < (int)sizeof buf) // :169: no learning rate, no ", learn_rate" (NMF sets lRate = -1)
+                snprintf(buf + len, sizeof buf - (size_t)len, ", learn_rate = %g", (double)(float)lRate);
             log_(buf);
         }
         if (std::isnan(loss) || std::isinf(loss))
@@ -644,8 +646,9 @@ class FM : public IterativeRecommender {
     cmi_fm_handle fm_ = nullptr;
 };
 
-// What ItemKNN, UserKNN and SlopeOne share: a model of the 2-D train matrix behind a handle H of the C ABI, rating prediction only,
-// nothing to initialise and nothing to save (the reference's saveModel() of these models is empty); evaluation through the generic
+// What ItemKNN, UserKNN, SlopeOne and NMF share: a model of the 2-D train matrix behind a handle H of the C ABI, rating prediction only,
+// nothing to initialise (NMF draws its own W and H) and nothing to save (the reference's saveModel() of the memory-based models is
+// empty); evaluation through the generic
 // evalRatings recipe on bounded predictions.
 template <typename H, int (*destroy)(H), const char *(*last_error)(H),
           int (*set_ratings)(H, int64_t, const int32_t *, const int32_t *, const double *)>
@@ -733,6 +736,49 @@ class SlopeOne : public PairRecommender<cmi_slope_handle, cmi_slope_destroy, cmi
     }
 };
 
+// src/carskit/alg/baseline/cf/NMF.java: W (numUsers x numFactors) and H (numFactors x numItems) by multiplicative updates over the 2-D
+// train matrix.  Parameters: num.factors, num.max.iter.  lRate = -1 (NMF.java:51): updateLRate returns at once.
+class NMF : public PairRecommender<cmi_nmf_handle, cmi_nmf_destroy, cmi_nmf_last_error, cmi_nmf_set_ratings> {
+  public:
+    NMF(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("NMF", tr, te, fold, c, log) {
+        lRate = -1;
+    }
+    void initModel() override { // NMF.java:56-65
+        JavaRandom rnd(conf_.randSeed);
+        const size_t nu = (size_t)trainMatrix.n_users, ni = (size_t)trainMatrix.n_items, k = (size_t)conf_.numFactors;
+        // super.initModel() (IterativeRecommender.java:235-241): P and Q, gaussian.  NMF never reads them, but they move the stream
+        for (size_t t = 0; t < (nu + ni) * k; ++t) (void)rnd.nextGaussian();
+        W.resize(nu * k);
+        H.resize(k * ni);
+        for (double &x : W) x = rnd.nextDouble() * 0.01; // W.init(0.01): uniform(0, 0.01)
+        for (double &x : H) x = rnd.nextDouble() * 0.01; // H.init(0.01)
+    }
+    void buildModel() override { // NMF.java:67-131
+        check(cmi_nmf_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &h_), "cmi_nmf_create");
+        setRatings("cmi_nmf_set_ratings");
+        check(cmi_nmf_set_model(h_, W.data(), H.data()), "cmi_nmf_set_model");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_nmf_iterate(h_, &loss); // W phase, H phase, loss
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_nmf_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            losses.push_back(loss);
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        check(cmi_nmf_get_model(h_, W.data(), H.data()), "cmi_nmf_get_model");
+    }
+    // the reference's saveModel() writes P and Q (IterativeRecommender.java:249-270), which NMF never trains, and neither W nor H: there
+    // is nothing of the model to save
+    void saveModel() override {}
+    std::vector<double> W, H; // numUsers x numFactors; numFactors x numItems
+
+  private:
+    void predictBounded(double *pred) override {
+        check(cmi_nmf_predict_batch(h_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), 1, trainMatrix.min_rate,
+                                    trainMatrix.max_rate, pred), "cmi_nmf_predict_batch");
+    }
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -751,7 +797,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "itemknn") return std::unique_ptr<IterativeRecommender>(new ItemKNN(tr, te, fold, c, log));
     if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
     if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn, slopeone)");
+    if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -639,6 +639,36 @@ int cmi_slope_predict_batch(cmi_slope_handle h, int64_t n, const int32_t *u, con
                             double lo, double hi, double *out);
 int cmi_slope_last_build_ms(cmi_slope_handle h, float *ms);
 
+/* ---- NMF (src/carskit/alg/baseline/cf/NMF.java; nmf_api.cpp, nmf_kernels.hip) --------------------------------------------------
+ * Lee & Seung's multiplicative updates over the 2-D train matrix V, fp64, bit-exact to the reference: every sum (product(W, u, H, j)
+ * over the factors, DenseVector.inner over a row's or a column's entries in ascending index order) is one left-to-right chain from
+ * 0.0 without FMA.  State: W (n_users x k) and H (k x n_items, kept item-major on the device), 1 <= k <= 256.  A cell whose value is
+ * 0 takes no part (librec's SparseMatrix.row() / column() leave it out).  No CPU fallback: without a device cmi_nmf_create returns
+ * CMI_E_NO_DEVICE. */
+typedef struct cmi_nmf_instance *cmi_nmf_handle;
+/* NMF.java:47-53,58-59 (numFactors, the shapes of W and H) */
+int cmi_nmf_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_nmf_handle *out);
+int cmi_nmf_destroy(cmi_nmf_handle h);
+const char *cmi_nmf_last_error(cmi_nmf_handle h);
+/* NMF.java:64 (V = train): the 2-D train matrix as n cells; a duplicate (u, i) or an id out of range -> CMI_E_INVALID; n >= 2^31 ->
+ * CMI_E_UNSUPPORTED */
+int cmi_nmf_set_ratings(cmi_nmf_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* NMF.java:58-62: W (n_users x k, row-major) and H (k x n_items, row-major, the reference's layout).  Either may be NULL (left as it
+ * is) once both have been set */
+int cmi_nmf_set_model(cmi_nmf_handle h, const double *W, const double *H);
+int cmi_nmf_get_model(cmi_nmf_handle h, double *W, double *H);
+/* NMF.java:71-126, one pass of buildModel's loop: W[u][f] *= real / (estm + 1e-9) for every user with entries, then the same for H's
+ * columns with the new W, then *loss = 0.5 * the sum of (predict(u, j) - r)^2 over the cells with r > 0.  W and H are bit-identical
+ * to the reference's; the loss is summed in a fixed order that depends on the number of cells alone (block partials, then one chain),
+ * not the reference's single chain: the same bits from run to run, and within (cells) * 2^-53, relatively, of the reference's.
+ * NaN/Inf loss -> CMI_E_NUMERIC with *loss set */
+int cmi_nmf_iterate(cmi_nmf_handle h, double *loss);
+/* NMF.java:142-145, predict(u, j) = product(W, u, H, j) of n tuples; bound: clamp to [lo, hi] as Recommender.predict(u, j, c, true) */
+int cmi_nmf_predict_batch(cmi_nmf_handle h, int64_t n, const int32_t *u, const int32_t *j, int bound, double lo, double hi, double *out);
+/* device time of the last cmi_nmf_iterate, by events: ms[0] the W phase (NMF.java:72-89), ms[1] the H phase (:92-110), ms[2] the loss
+ * (:113-126) */
+int cmi_nmf_last_iter_ms(cmi_nmf_handle h, float ms[3]);
+
 #ifdef __cplusplus
 }
 #endif
