@@ -471,7 +471,7 @@ static bool try_chain(cmi_instance *h, int64_t n, const int32_t *u, const int32_
     // Zipf(0.8) items, the chain schedule has 2.5x fewer levels (434 K vs 1.10 M) but a narrow chain level is latency-bound on
     // the HBM round trip of EVERY spoke row of its longest unit (one row in flight per group), 3.77 s per epoch against 2.61 s for
     // the plain narrow-run walk.  Forced (CMI_FLAG_SCHED_CHAIN) it still runs, one launch per level.
-    if (!forced && csch.n_units() < min_width * csch.n_levels()) {
+    if (!forced && csch.greedy_units < min_width * csch.greedy_levels) { // (the greedy walk's counts: see ChainSchedule)
         free_keep(keep);
         return false;
     }

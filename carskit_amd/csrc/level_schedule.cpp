@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include <thread>
 
+#include "chain_refine.hpp"
 #include "host_pool.hpp"
 
 #include <queue>
@@ -152,7 +153,8 @@ void build_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, i
 // (equal spokes would give A == B); for every user and every item the (level, position in unit) order of its tuples is the
 // CRS order.  Hence executing levels in sequence, units of a level in parallel, and a unit's tuples in order applies to
 // every state element the same updates with the same operands as the sequential walk -- the same result as the plain
-// level schedule, bit for bit at equal arithmetic.
+// level schedule, bit for bit at equal arithmetic.  What is fixed is the order of the updates per row; where a hub row's chain is cut into
+// units is not: the greedy cut of the walk below is refined afterwards (chain_refine.hpp, refine_chain_cuts), which keeps every invariant.
 // Inside a level the units are sorted by length, longest first (free: they are independent): the 4 groups of a wave then
 // walk chains of similar length and the longest chains are dispatched first.
 // The recurrence is sequential in t, but what it costs is the cache miss on the rows' level entries (a 10 M-user table is 40 MB): the
@@ -200,6 +202,68 @@ static void chain_pass(int64_t n, const int32_t *hub, const int32_t *spoke, int3
         if (unit_out) (*unit_out)[(size_t)t] = h.unit;
         if (l > n_levels) n_levels = l;
     }
+}
+
+// Up-only refinement of the greedy cut (chain_refine.hpp): the walk's units, re-cut in `passes` synchronous passes, then levels that
+// emptied are dropped and the units numbered again in CRS order of their first tuples -- the walk's own output format.
+static void refine_chain_cuts(int64_t n, const int32_t *hub, const int32_t *spoke, int32_t n_hub, int32_t n_spoke, int max_chain, int passes,
+                              std::vector<int32_t> &unit_of, std::vector<uint8_t> &pos, std::vector<int32_t> &unit_level,
+                              std::vector<uint8_t> &unit_len, int32_t &n_levels, int64_t &n_units) {
+    // the hub rows' chains (stable counting sort by hub row) and every list entry's spoke successor, as a list position
+    std::vector<int32_t> off((size_t)n_hub + 1, 0), lt((size_t)n), inv((size_t)n), succ((size_t)n);
+    for (int64_t t = 0; t < n; ++t) off[(size_t)hub[t] + 1]++;
+    for (int32_t h = 0; h < n_hub; ++h) off[(size_t)h + 1] += off[(size_t)h];
+    {
+        std::vector<int32_t> cur(off.begin(), off.end() - 1);
+        for (int64_t t = 0; t < n; ++t) {
+            const int32_t i = cur[(size_t)hub[t]]++;
+            lt[(size_t)i] = (int32_t)t;
+            inv[(size_t)t] = i;
+        }
+        std::vector<int32_t> last((size_t)n_spoke, -1);
+        for (int64_t t = n - 1; t >= 0; --t) {
+            succ[(size_t)inv[(size_t)t]] = last[(size_t)spoke[t]];
+            last[(size_t)spoke[t]] = inv[(size_t)t];
+        }
+    }
+    std::vector<int32_t> lev((size_t)n), nxt((size_t)n), &ub = inv; // (inv is not needed any more)
+    const int nt = host_threads(n);
+    parallel_ranges(n, nt, [&](int, int64_t b, int64_t e) {
+        for (int64_t i = b; i < e; ++i) lev[(size_t)i] = unit_level[(size_t)unit_of[(size_t)lt[(size_t)i]]];
+    });
+    std::vector<int32_t> first_level((size_t)n, 0); // per tuple: level of the unit it starts (0: none), as the device walk records it
+    std::vector<uint8_t> first_len((size_t)n, 0);
+    for (int p = 0; p < passes; ++p) {
+        const bool last_pass = p + 1 == passes;
+        parallel_ranges(n, nt, [&](int, int64_t b, int64_t e) {
+            for (int64_t i = b; i < e; ++i) ub[(size_t)i] = succ[(size_t)i] >= 0 ? lev[(size_t)succ[(size_t)i]] - 1 : n_levels;
+        });
+        parallel_ranges(n_hub, nt, [&](int, int64_t b, int64_t e) {
+            for (int64_t h = b; h < e; ++h)
+                chain_recut_row(off[(size_t)h], off[(size_t)h + 1], max_chain, lev.data(), ub.data(), nxt.data(), last_pass ? lt.data() : nullptr,
+                                unit_of.data(), pos.data(), first_level.data(), first_len.data());
+        });
+        lev.swap(nxt);
+    }
+    // levels that emptied are dropped; dense unit ids in CRS order of the first tuples
+    std::vector<int32_t> remap((size_t)n_levels + 1, 0);
+    for (int64_t t = 0; t < n; ++t) remap[(size_t)first_level[(size_t)t]] = 1;
+    int32_t kept = 0;
+    for (int32_t l = 1; l <= n_levels; ++l) remap[(size_t)l] = remap[(size_t)l] ? ++kept : 0;
+    unit_level.clear();
+    unit_len.clear();
+    std::vector<int32_t> &dense = nxt;
+    for (int64_t t = 0; t < n; ++t)
+        if (first_level[(size_t)t]) {
+            dense[(size_t)t] = (int32_t)unit_level.size();
+            unit_level.push_back(remap[(size_t)first_level[(size_t)t]]);
+            unit_len.push_back(first_len[(size_t)t]);
+        }
+    parallel_ranges(n, nt, [&](int, int64_t b, int64_t e) {
+        for (int64_t t = b; t < e; ++t) unit_of[(size_t)t] = dense[(size_t)unit_of[(size_t)t]];
+    });
+    n_levels = kept;
+    n_units = (int64_t)unit_level.size();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -372,6 +436,12 @@ bool build_chain_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t
         if (!hub) std::swap(side, other);
     } else run_side(hub ? 1 : 0, side);
     out.hub_is_item = hub ? 1 : 0;
+    out.greedy_units = side.nu; // (what the side was picked on, and what decides whether the schedule is wide enough to be used)
+    out.greedy_levels = side.nl;
+    if (const int passes = max_chain > 1 ? chain_refine_passes() : 0) {
+        if (hub) refine_chain_cuts(n, j, u, n_items, n_users, max_chain, passes, side.unit_of, side.pos, side.unit_level, side.unit_len, side.nl, side.nu);
+        else refine_chain_cuts(n, u, j, n_users, n_items, max_chain, passes, side.unit_of, side.pos, side.unit_level, side.unit_len, side.nl, side.nu);
+    }
     const int32_t nl = side.nl;
     const int64_t nu = side.nu;
     const std::vector<int32_t> &unit_of = side.unit_of, &unit_level = side.unit_level;

@@ -29,6 +29,8 @@ struct ChainSchedule {
     std::vector<int64_t> level_off; // n_levels+1 offsets into unit_off (unit indices)
     int hub_is_item = 1;
     int64_t max_level_units = 0;    // most units in one level
+    int64_t greedy_units = 0;       // units and levels of the greedy walk, before the cut was refined (chain_refine.hpp): the hub side and
+    int64_t greedy_levels = 0;      // the use of the schedule are decided on these, so refining changes no data set's schedule kind
     int64_t n_units() const { return (int64_t)unit_off.size() - 1; }
     int64_t n_levels() const { return (int64_t)level_off.size() - 1; }
 };

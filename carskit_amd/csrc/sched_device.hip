@@ -1,8 +1,9 @@
 // sched_device.hip -- the hub-chain level schedule (level_schedule.cpp build_chain_schedule) and the spoke arena's position lists
 // (cmi_api.cpp arena_positions) built ON THE DEVICE.  Same results, element for element, as the host builders they replace: the
 // schedule is the order-exact restatement of librec's MatrixIterator order (CAMF_CI.java:80 `for (MatrixEntry me :
-// trainMatrix)`), so nothing about it may change -- only where it is computed.  With epochs at milliseconds the host walk (11 ns per
-// tuple, one core: 0.4 s for C3's 50 M tuples, 2 s for north_star's 200 M) was the long step of a run.
+// trainMatrix)`): the order of the updates per row is fixed; where a hub row's chain is cut into units is not (chain_refine.hpp refines
+// the greedy cut, here with the same rule as on the host), and neither is where the schedule is computed.  With epochs at milliseconds the
+// host walk (11 ns per tuple, one core: 0.4 s for C3's 50 M tuples, 2 s for north_star's 200 M) was the long step of a run.
 //
 // The recurrence (chain_pass): tuple t, in CRS order, with hub row h and spoke row s:
 //     A = level of h's previous tuple, B = level of s's previous tuple
@@ -34,6 +35,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "chain_refine.hpp"
 #include "level_schedule.hpp"
 #include "sched_device.hpp"
 
@@ -323,6 +325,36 @@ __global__ void k_fill(int32_t *v, int64_t n, int32_t x) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[i] = x;
 }
 
+// ---- the cut refined within the schedule's slack (chain_refine.hpp): plain data-parallel passes, no lane waits on another ----
+__global__ void k_inv(const int32_t *lt, int64_t n, int32_t *inv) { // inv[t] = list position of tuple t in its hub row's chain
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) inv[lt[i]] = (int32_t)i;
+}
+// the spoke successor of every list entry, as a list position (-1: none), out of the tuples sorted by spoke row (stable: CRS order inside a row)
+__global__ void k_succ(const int32_t *skey, const int32_t *st, const int32_t *inv, int64_t n, int32_t *succ) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x)
+        succ[inv[st[p]]] = p + 1 < n && skey[p + 1] == skey[p] ? inv[st[p + 1]] : -1;
+}
+__global__ void k_list_levels(const int32_t *lt, const int32_t *unit_of, const int32_t *unit_level, int64_t n, int32_t *lev) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) lev[i] = unit_level[unit_of[lt[i]]];
+}
+__global__ void k_upper(const int32_t *succ, const int32_t *lev, int64_t n, int32_t n_levels, int32_t *ub) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        ub[i] = succ[i] >= 0 ? lev[succ[i]] - 1 : n_levels;
+}
+__global__ void k_recut(const int32_t *hub_off, int32_t n_hub, int max_chain, const int32_t *lev_in, const int32_t *ub, int32_t *lev_out, const int32_t *lt,
+                        int32_t *unit_of, uint8_t *pos, int32_t *unit_level, uint8_t *unit_len) {
+    for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < n_hub; h += (int64_t)gridDim.x * blockDim.x)
+        chain_recut_row(hub_off[h], hub_off[h + 1], max_chain, lev_in, ub, lev_out, lt, unit_of, pos, unit_level, unit_len);
+}
+__global__ void k_mark_levels(const int32_t *unit_level, int64_t n, int32_t *used) {
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        if (unit_level[t] != 0) used[unit_level[t]] = 1;
+}
+__global__ void k_renumber_levels(int32_t *unit_level, int64_t n, const int32_t *before) { // before[l] = kept levels below l
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (int64_t)gridDim.x * blockDim.x)
+        if (unit_level[t] != 0) unit_level[t] = before[unit_level[t]] + 1;
+}
+
 inline unsigned grid_for(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 inline unsigned bits_for(int64_t values) { // bits needed for keys in [0, values)
     unsigned b = 1;
@@ -448,6 +480,45 @@ hipError_t walk(DevPool &pool, int device, hipStream_t s, const Sorted &hubs, co
     return hipSuccess; // no convergence (should not happen): ok stays false, the host builder takes it
 }
 
+hipError_t exclusive_scan_i32(DevPool &pool, hipStream_t s, const int32_t *in, int32_t *out, size_t count) {
+    size_t tb = 0;
+    SD(rocprim::exclusive_scan(nullptr, tb, in, out, 0, count, rocprim::plus<int32_t>(), s));
+    void *tmp = pool.get<char>(tb);
+    SD(pool.err);
+    return rocprim::exclusive_scan(tmp, tb, in, out, 0, count, rocprim::plus<int32_t>(), s);
+}
+
+// refine_chain_cuts (level_schedule.cpp) on the device: the walk's per-tuple output re-cut in `passes` synchronous passes, emptied levels dropped
+hipError_t refine(DevPool &pool, hipStream_t s, const Sorted &hubs, const Sorted &spokes, int64_t n, int32_t n_hub, int max_chain, int passes,
+                  const WalkOut &wo, int32_t &n_levels) {
+    int32_t *inv = pool.get<int32_t>((size_t)n), *succ = pool.get<int32_t>((size_t)n), *lev = pool.get<int32_t>((size_t)n);
+    int32_t *nxt = pool.get<int32_t>((size_t)n), *used = pool.get<int32_t>((size_t)n_levels + 2), *before = pool.get<int32_t>((size_t)n_levels + 2);
+    SD(pool.err);
+    int32_t *ub = inv; // (free once the successors are list positions)
+    const dim3 gn(grid_for(n)), b(256);
+    hipLaunchKernelGGL(k_inv, gn, b, 0, s, hubs.st, n, inv);
+    hipLaunchKernelGGL(k_succ, gn, b, 0, s, spokes.skey, spokes.st, inv, n, succ);
+    hipLaunchKernelGGL(k_list_levels, gn, b, 0, s, hubs.st, wo.unit_of, wo.unit_level, n, lev);
+    for (int p = 0; p < passes; ++p) {
+        const bool last_pass = p + 1 == passes;
+        hipLaunchKernelGGL(k_upper, gn, b, 0, s, succ, lev, n, n_levels, ub);
+        if (last_pass) SD(hipMemsetAsync(wo.unit_level, 0, (size_t)n * 4, s));
+        hipLaunchKernelGGL(k_recut, dim3(grid_for(n_hub)), b, 0, s, hubs.off, n_hub, max_chain, lev, ub, nxt, last_pass ? hubs.st : nullptr, wo.unit_of, wo.pos,
+                           wo.unit_level, wo.unit_len);
+        std::swap(lev, nxt);
+    }
+    SD(hipMemsetAsync(used, 0, ((size_t)n_levels + 2) * 4, s));
+    hipLaunchKernelGGL(k_mark_levels, gn, b, 0, s, wo.unit_level, n, used);
+    SD(exclusive_scan_i32(pool, s, used, before, (size_t)n_levels + 2));
+    hipLaunchKernelGGL(k_renumber_levels, gn, b, 0, s, wo.unit_level, n, before);
+    SD(hipGetLastError());
+    int32_t kept = 0;
+    SD(hipMemcpyAsync(&kept, before + n_levels + 1, 4, hipMemcpyDeviceToHost, s)); // levels 1 .. n_levels in use
+    SD(hipStreamSynchronize(s));
+    n_levels = kept;
+    return hipSuccess;
+}
+
 } // namespace
 
 void ChainDeviceKeep::release() {
@@ -552,22 +623,33 @@ bool build_chain_schedule_device(int device, void *stream, int64_t n, const int3
         if (e != hipSuccess || !ok) return fail("walk", e);
     }
     lap("walk");
+    out.greedy_units = nu;
+    out.greedy_levels = nl;
+    const int passes = max_chain > 1 ? chain_refine_passes() : 0;
+    if (passes) {
+        const hipError_t e = hub ? refine(pool, s, by_j, by_u, n, n_items, max_chain, passes, wo, nl) : refine(pool, s, by_u, by_j, n, n_users, max_chain, passes, wo, nl);
+        if (e != hipSuccess) return fail("refinement", e);
+    }
     // dense unit ids (CRS order of the first tuples), the units sorted by (level, length descending), offsets, the permutation
     int32_t *flag = pool.get<int32_t>((size_t)n), *dense = pool.get<int32_t>((size_t)n);
+    if (pool.err != hipSuccess) return fail("allocation", pool.err);
+    hipLaunchKernelGGL(k_flags, dim3(grid_for(n)), dim3(256), 0, s, wo.unit_level, n, flag);
+    if (hipError_t e = exclusive_scan_i32(pool, s, flag, dense, (size_t)n)) return fail("scan", e);
+    if (passes) { // the refined cut's unit count
+        int32_t before_last = 0, last_flag = 0;
+        if (hipMemcpyAsync(&before_last, dense + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess) return fail("copy back", hipGetLastError());
+        if (hipMemcpyAsync(&last_flag, flag + (n - 1), 4, hipMemcpyDeviceToHost, s) != hipSuccess) return fail("copy back", hipGetLastError());
+        if (hipError_t e = hipStreamSynchronize(s)) return fail("synchronize", e);
+        nu = (int64_t)before_last + last_flag;
+        lap("refinement");
+        if (times) fprintf(stderr, "[cmi] device schedule: %d refinement pass(es): %lld -> %lld units, %lld -> %d levels\n", passes, (long long)out.greedy_units, (long long)nu, (long long)out.greedy_levels, nl);
+    }
     uint32_t *key = pool.get<uint32_t>((size_t)nu), *skey = pool.get<uint32_t>((size_t)nu);
     int32_t *uid = pool.get<int32_t>((size_t)nu), *suid = pool.get<int32_t>((size_t)nu), *rank_of = pool.get<int32_t>((size_t)nu);
     int32_t *len_sorted = pool.get<int32_t>((size_t)nu + 1), *unit_off = pool.get<int32_t>((size_t)nu + 1), *perm = pool.get<int32_t>((size_t)n);
     uint8_t *ulen = pool.get<uint8_t>((size_t)nu);
     int64_t *level_off = pool.get<int64_t>((size_t)nl + 1);
     if (pool.err != hipSuccess) return fail("allocation", pool.err);
-    hipLaunchKernelGGL(k_flags, dim3(grid_for(n)), dim3(256), 0, s, wo.unit_level, n, flag);
-    {
-        size_t tb = 0;
-        if (hipError_t e = rocprim::exclusive_scan(nullptr, tb, flag, dense, 0, (size_t)n, rocprim::plus<int32_t>(), s)) return fail("scan", e);
-        void *tmp = pool.get<char>(tb);
-        if (pool.err != hipSuccess) return fail("allocation", pool.err);
-        if (hipError_t e = rocprim::exclusive_scan(tmp, tb, flag, dense, 0, (size_t)n, rocprim::plus<int32_t>(), s)) return fail("scan", e);
-    }
     hipLaunchKernelGGL(k_units, dim3(grid_for(n)), dim3(256), 0, s, wo.unit_level, wo.unit_len, dense, n, max_chain, key, uid, ulen);
     {
         const unsigned bits = bits_for((int64_t)nl * max_chain + 1);
