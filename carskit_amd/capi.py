@@ -186,6 +186,21 @@ SYMBOLS = [
     ("cmi_nmf_iterate", C.c_int, [_vp, C.POINTER(_dbl)]),
     ("cmi_nmf_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_nmf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_slim_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_slim_destroy", C.c_int, [_vp]),
+    ("cmi_slim_last_error", C.c_char_p, [_vp]),
+    ("cmi_slim_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_slim_build_neighbors", C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dbl, _dbl]),
+    ("cmi_slim_cut_neighbors", C.c_int, [C.c_int32, _vp, C.c_int, _vp, C.POINTER(C.c_int32)]),
+    ("cmi_slim_get_neighbors", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_slim_set_weights", C.c_int, [_vp, _vp]),
+    ("cmi_slim_get_weights", C.c_int, [_vp, _vp]),
+    ("cmi_slim_iterate", C.c_int, [_vp, _dbl, _dbl, C.POINTER(_dbl)]),
+    ("cmi_slim_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_slim_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                         C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_slim_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_slim_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -925,7 +940,7 @@ def knn_measure(name):
 
 
 class _PairModel(_Handle):
-    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*, cmi_nmf_*)."""
+    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*, cmi_nmf_*, cmi_slim_*)."""
 
     _prefix = ""
 
@@ -1051,4 +1066,78 @@ class NMFInstance(_PairModel):
         """(W phase, H phase, loss) device milliseconds of the last iterate()"""
         ms = (C.c_float * 3)()
         self._chk(self.L.cmi_nmf_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+
+def slim_cut_neighbors(sims, knn):
+    """Host-only: the neighbour list SLIM.initModel makes of one item's similarity row (NaN unset), in its iteration order
+    (see cmi_slim_cut_neighbors); E_UNSUPPORTED when a hash bin would treeify"""
+    sims = np.ascontiguousarray(sims, dtype=np.float64)
+    out, n = np.empty(max(len(sims), 1), np.int32), C.c_int32()
+    rc = lib().cmi_slim_cut_neighbors(len(sims), _p(sims), int(knn), _p(out), C.byref(n))
+    if rc != OK:
+        raise CmiError(rc, (lib().cmi_last_error(None) or b"cmi_slim_cut_neighbors").decode())
+    return out[:n.value].tolist()
+
+
+class SLIMInstance(_PairModel):
+    """The reference's SLIM on one GPU (a `cmi_slim_handle`): per item a neighbour list in the reference's iteration order and one
+    weight per list entry, W[i][j]."""
+
+    _api = ("cmi_slim_create", "cmi_slim_destroy", "cmi_slim_last_error")
+    _prefix = "cmi_slim"
+
+    def __init__(self, n_users, n_items, device=0, flags=0):
+        self.n_users, self.n_items = n_users, n_items
+        super().__init__(n_users, n_items, device, flags)
+
+    def build_neighbors(self, knn, measure="pcc", shrinkage=-1, min_rate=1.0, max_rate=5.0):
+        m = knn_measure(measure) if isinstance(measure, str) else int(measure)
+        self._chk(self.L.cmi_slim_build_neighbors(self.h, int(knn), m, int(shrinkage), float(min_rate), float(max_rate)))
+
+    def neighbors(self):
+        """(ptr, idx): item j's list is idx[ptr[j]:ptr[j + 1]]"""
+        ptr = np.empty(self.n_items + 1, np.int64)
+        self._chk(self.L.cmi_slim_get_neighbors(self.h, _p(ptr), None))
+        idx = np.empty(int(ptr[-1]), np.int32)
+        self._chk(self.L.cmi_slim_get_neighbors(self.h, _p(ptr), _p(idx)))
+        return ptr, idx
+
+    def set_weights(self, w):
+        """w[p] = W[idx[p]][j], aligned with neighbors()'s idx"""
+        ptr = np.empty(self.n_items + 1, np.int64)
+        self._chk(self.L.cmi_slim_get_neighbors(self.h, _p(ptr), None))
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (int(ptr[-1]),):
+            raise CmiError(E_INVALID, "w has shape %s, not (%d,)" % (w.shape, int(ptr[-1])))
+        self._chk(self.L.cmi_slim_set_weights(self.h, _p(w)))
+
+    def weights(self):
+        ptr = np.empty(self.n_items + 1, np.int64)
+        self._chk(self.L.cmi_slim_get_neighbors(self.h, _p(ptr), None))
+        w = np.empty(int(ptr[-1]))
+        self._chk(self.L.cmi_slim_get_weights(self.h, _p(w)))
+        return w
+
+    def iterate(self, l1, l2):
+        """one pass over every coordinate; l1, l2: the doubles of the reference's floats.  Returns the loss (NaN / Inf raises E_NUMERIC)"""
+        loss = _dbl()
+        self._chk(self.L.cmi_slim_iterate(self.h, float(l1), float(l2), C.byref(loss)))
+        return loss.value
+
+    def predict(self, u, j):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_slim_predict_batch(self.h, len(u), _p(u), _p(j), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_slim_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_iter_ms(self):
+        """(sweep, loss chain) device milliseconds of the last iterate()"""
+        ms = (C.c_float * 2)()
+        self._chk(self.L.cmi_slim_last_iter_ms(self.h, ms))
         return tuple(ms)

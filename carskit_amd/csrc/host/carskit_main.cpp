@@ -110,6 +110,9 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
             throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of NMF is not accelerated yet");
         if (a == "nmf" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": NMF runs on one GPU");
+        // SLIM is a top-N model (item.ranking -diverse is refused with every model, by Conf), on one GPU
+        if (a == "slim" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": SLIM runs on one GPU");
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
@@ -144,7 +147,7 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     const std::string algoName = LineConfiger(cf.getString("recommender")).getMainParam();
     {   // the similarity-based CAMF recommenders are top-N models: their constructors switch the (static) isRankingPred on
         const std::string a = lower(algoName);
-        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs") conf.isRankingPred = true;
+        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim") conf.isRankingPred = true; // SLIM.java:68
     }
     log("With Setup: " + cf.getString("evaluation.setup"));
     std::vector<Measures> all;

@@ -158,6 +158,9 @@ struct Conf {
     int knn = 20, knnShrinkage = 0;
     bool knnShrinkageSet = false, knnShrinkagePresent = false;
     std::string similarity = "PCC", knnShrinkageRaw;
+    // SLIM=-l1 -l2 -k (SLIM.java:71-74): the regularisers are Java floats, held here as the doubles they widen to
+    double slimL1 = 0, slimL2 = 0;
+    int slimKnn = 0;
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
         if (cf.contains("learn.rate")) {
@@ -207,6 +210,12 @@ struct Conf {
             size_t p = (!v.empty() && (v[0] == '-' || v[0] == '+')) ? 1 : 0;
             knnShrinkageSet = p < v.size() && v.find_first_not_of("0123456789", p) == std::string::npos;
             if (knnShrinkageSet) knnShrinkage = (int)std::strtol(v.c_str(), nullptr, 10);
+        }
+        if (cf.contains("SLIM")) { // SLIM.java:71-74: getFloat("-l1"), getFloat("-l2"), getInt("-k")
+            LineConfiger sl = cf.getParamOptions("SLIM");
+            slimL1 = sl.getFloat("-l1", 0);
+            slimL2 = sl.getFloat("-l2", 0);
+            slimKnn = sl.getInt("-k", 0);
         }
         if (cf.contains("FM")) {
             LineConfiger fm = cf.getParamOptions("FM");
@@ -779,6 +788,93 @@ class NMF : public PairRecommender<cmi_nmf_handle, cmi_nmf_destroy, cmi_nmf_last
     }
 };
 
+// src/carskit/alg/baseline/ranking/SLIM.java: the item x item weights W by coordinate descent over each item's neighbour list, for
+// top-N.  Parameters: SLIM=-l1 -l2 -k, similarity, num.shrinkage, num.max.iter.  The constructor sets the static isRankingPred = true
+// (SLIM.java:68), so execute() evaluates with evalRankings() whatever item.ranking says.
+class SLIM : public PairRecommender<cmi_slim_handle, cmi_slim_destroy, cmi_slim_last_error, cmi_slim_set_ratings> {
+  public:
+    SLIM(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("SLIM", tr, te, fold, c, log) {
+        conf_.isRankingPred = true;
+    }
+    // SLIM.java:78-118.  The lists come first here (they do not touch the random stream); then the stream as the reference draws it:
+    // P and Q (IterativeRecommender.java:235-241, gaussian, never read), then W.init(): numItems^2 uniform draws, row by row, of which
+    // the listed cells are kept (no other cell is ever read); the diagonal is 0 (:93, :116).
+    void initModel() override {
+        if (conf_.slimKnn > 0 && !conf_.knnShrinkageSet) // buildCorrs -> correlation(): Integer.parseInt of num.shrinkage, as for the KNN models
+            throw std::runtime_error(!conf_.knnShrinkagePresent ? std::string("null (num.shrinkage is not set)")
+                                                                     : "For input string: \"" + conf_.knnShrinkageRaw + "\" (num.shrinkage)");
+        check(cmi_slim_create(trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &h_), "cmi_slim_create");
+        setRatings("cmi_slim_set_ratings");
+        check(cmi_slim_build_neighbors(h_, conf_.slimKnn, cmi_knn_measure(conf_.similarity.c_str()), conf_.knnShrinkage, trainMatrix.min_rate,
+                                       trainMatrix.max_rate), "cmi_slim_build_neighbors");
+        const size_t nu = (size_t)trainMatrix.n_users, ni = (size_t)trainMatrix.n_items, k = (size_t)conf_.numFactors;
+        ptr.resize(ni + 1);
+        check(cmi_slim_get_neighbors(h_, ptr.data(), nullptr), "cmi_slim_get_neighbors");
+        idx.resize((size_t)ptr[ni]);
+        check(cmi_slim_get_neighbors(h_, ptr.data(), idx.data()), "cmi_slim_get_neighbors");
+        // per column its list positions by ascending neighbour: the walk below meets the cells of a row in column order
+        std::vector<int64_t> byRow(idx.size()), cur(ni);
+        for (size_t j = 0; j < ni; ++j) {
+            std::iota(byRow.begin() + ptr[j], byRow.begin() + ptr[j + 1], ptr[j]);
+            std::sort(byRow.begin() + ptr[j], byRow.begin() + ptr[j + 1], [&](int64_t a, int64_t b) { return idx[(size_t)a] < idx[(size_t)b]; });
+            cur[j] = ptr[j];
+        }
+        JavaRandom rnd(conf_.randSeed);
+        for (size_t t = 0; t < (nu + ni) * k; ++t) (void)rnd.nextGaussian();
+        W.assign(idx.size(), 0.0);
+        for (size_t i = 0; i < ni; ++i)
+            for (size_t j = 0; j < ni; ++j) {
+                const double v = rnd.nextDouble(); // W.init(): uniform(0, 1)
+                if (cur[j] < ptr[j + 1] && (size_t)idx[(size_t)byRow[(size_t)cur[j]]] == i) W[(size_t)byRow[(size_t)cur[j]++]] = i == j ? 0.0 : v;
+            }
+        check(cmi_slim_set_weights(h_, W.data()), "cmi_slim_set_weights");
+    }
+    void buildModel() override { // SLIM.java:121-181, with its own isConverged (:212-220)
+        last_loss = 0;
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_slim_iterate(h_, conf_.slimL1, conf_.slimL2, &loss);
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_slim_iterate"); // the reference goes on with a NaN loss (its isConverged has no check)
+            losses.push_back(loss);
+            itersDone = iter;
+            const double delta_loss = last_loss - loss;
+            last_loss = loss;
+            if (conf_.verbose && log_) {
+                char buf[256];
+                snprintf(buf, sizeof buf, "%s%s iter %d: loss = %.17g, delta_loss = %.17g", algoName.c_str(),
+                         fold_ > 0 ? (" fold [" + std::to_string(fold_) + "]").c_str() : "", iter, loss, delta_loss);
+                log_(buf);
+            }
+            if (iter > 1 && delta_loss < 1e-5) break;
+        }
+        check(cmi_slim_get_weights(h_, W.data()), "cmi_slim_get_weights");
+    }
+    Measures evalRankings() override { // Recommender.java:668-964 with SLIM.predict
+        static const char *names[CMI_RANK_MEASURES] = {"Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN",
+                                                       "MAP5", "MAP10", "MAPN", "NDCG5", "NDCG10", "NDCGN", "MRR5", "MRR10",
+                                                       "MRRN", "D5", "D10", "DN"};
+        double out[CMI_RANK_MEASURES];
+        int64_t nq = 0;
+        check(cmi_slim_eval_rankings(h_, trainMatrix.n(), trainMatrix.u.data(), trainMatrix.j.data(), trainMatrix.ctx.data(),
+                                     trainMatrix.r.data(), testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(),
+                                     testMatrix.r.data(), conf_.binThold, conf_.numRecs, conf_.numIgnore,
+                                     conf_.evalStrategy == "uc" ? CMI_RANK_UC : CMI_RANK_UCU, out, &nq, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr), "cmi_slim_eval_rankings");
+        Measures m;
+        for (int i = 0; i < CMI_RANK_MEASURES; ++i) m[names[i]] = out[i];
+        return m;
+    }
+    // the reference's saveModel() writes P and Q (IterativeRecommender.java:249-270), which SLIM never trains, and not W: there is
+    // nothing of the model to save
+    void saveModel() override {}
+    std::vector<int64_t> ptr; // the lists and their weights, as cmi_slim_get_neighbors / cmi_slim_get_weights give them
+    std::vector<int32_t> idx;
+    std::vector<double> W;
+
+  private:
+    void predictBounded(double *) override { throw std::runtime_error("SLIM is a top-N recommender: it has no rating evaluation"); }
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -794,11 +890,12 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "camf_ics") return std::unique_ptr<IterativeRecommender>(new CAMF_ICS(tr, te, fold, c, log));   // CARSKit.java:708
     if (n == "camf_lcs") return std::unique_ptr<IterativeRecommender>(new CAMF_LCS(tr, te, fold, c, log));   // CARSKit.java:710
     if (n == "camf_mcs") return std::unique_ptr<IterativeRecommender>(new CAMF_MCS(tr, te, fold, c, log));   // CARSKit.java:712
+    if (n == "slim") return std::unique_ptr<IterativeRecommender>(new SLIM(tr, te, fold, c, log));           // CARSKit.java:471-472
     if (n == "itemknn") return std::unique_ptr<IterativeRecommender>(new ItemKNN(tr, te, fold, c, log));
     if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
     if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
     if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, itemknn, userknn, slopeone, nmf)");
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -62,29 +62,8 @@ static int knn_set_ratings_impl(cmi_knn_handle h, int64_t n, const int32_t *u, c
     PairHostCsr by_user, by_item;
     if (int rc = pair_ingest(h, "cmi_knn_set_ratings", n, u, i, r, /*scan_items=*/item, by_user, by_item)) return rc;
     const PairHostCsr &rows = item ? by_item : by_user, &lists = item ? by_user : by_item;
-    const std::vector<int32_t> &rptr = rows.ptr, &ridx = rows.idx, &lptr = lists.ptr;
-    // librec SparseVector.contains: Arrays.binarySearch over the whole index array of a vector built by set() -- capacity the next
-    // power of two >= count, the tail zero.  Per entry of every row: does the row's own contains() find it?
-    std::vector<uint8_t> rok((size_t)n, 0);
-    for (int e = 0; e < h->n_ent; ++e) {
-        const int32_t b0 = rptr[(size_t)e], cnt = rptr[(size_t)e + 1] - b0;
-        int32_t cap = 1;
-        while (cap < cnt) cap <<= 1;
-        for (int32_t k = 0; k < cnt; ++k) {
-            const int32_t key = ridx[(size_t)(b0 + k)];
-            int32_t low = 0, high = cap - 1;
-            while (low <= high) {
-                const int32_t mid = (int32_t)((uint32_t)(low + high) >> 1);
-                const int32_t v = mid < cnt ? ridx[(size_t)(b0 + mid)] : 0;
-                if (v < key) low = mid + 1;
-                else if (v > key) high = mid - 1;
-                else {
-                    rok[(size_t)(b0 + k)] = 1;
-                    break;
-                }
-            }
-        }
-    }
+    const std::vector<int32_t> &lptr = lists.ptr;
+    const std::vector<uint8_t> rok = pair_contains_flags(rows);
     CMI_HIP(h, hipSetDevice(h->device));
     CMI_HIP(h, hipStreamSynchronize(h->stream));
     knn_free_ratings(h);

@@ -66,18 +66,6 @@ extern "C" int cmi_nmf_create(int k, int n_users, int n_items, int device, unsig
     return CMI_OK;
 }
 
-// the CSR without its zero-valued cells
-static PairHostCsr nmf_drop_zeros(const PairHostCsr &m) {
-    PairHostCsr o;
-    o.ptr.assign(m.ptr.size(), 0);
-    for (size_t row = 0; row + 1 < m.ptr.size(); ++row) {
-        for (int32_t q = m.ptr[row]; q < m.ptr[row + 1]; ++q)
-            if (m.val[(size_t)q] != 0.0) o.idx.push_back(m.idx[(size_t)q]), o.val.push_back(m.val[(size_t)q]);
-        o.ptr[row + 1] = (int32_t)o.idx.size();
-    }
-    return o;
-}
-
 // the rows with entries, longest first (equal lengths in index order): the longest chain starts first
 static std::vector<int32_t> nmf_order(const PairHostCsr &m) {
     std::vector<int32_t> ord;
@@ -92,7 +80,7 @@ static std::vector<int32_t> nmf_order(const PairHostCsr &m) {
 static int nmf_set_ratings_impl(cmi_nmf_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r) {
     PairHostCsr rows, cols;
     if (int rc = pair_ingest(h, "cmi_nmf_set_ratings", n, u, i, r, /*scan_items=*/false, rows, cols)) return rc;
-    rows = nmf_drop_zeros(rows), cols = nmf_drop_zeros(cols);
+    rows = pair_drop_zeros(rows), cols = pair_drop_zeros(cols);
     const std::vector<int32_t> uorder = nmf_order(rows), iorder = nmf_order(cols);
     std::vector<int32_t> cu(rows.idx.size());
     for (int a = 0; a < h->n_users; ++a) std::fill(cu.begin() + rows.ptr[(size_t)a], cu.begin() + rows.ptr[(size_t)a + 1], a);

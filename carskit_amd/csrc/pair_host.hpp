@@ -1,5 +1,6 @@
-// pair_host.hpp -- the host side that the pair-co-occurrence handles share (cmi_knn_*: knn_api.cpp, cmi_slope_*: slopeone_api.cpp): the
-// handle's common state, the ingest of the 2-D train matrix, the dense-matrix reservation and the timed build (the prediction batch is abi_predict).
+// pair_host.hpp -- the host side that the pair-co-occurrence handles share (cmi_knn_*: knn_api.cpp, cmi_slope_*: slopeone_api.cpp,
+// cmi_nmf_*: nmf_api.cpp, cmi_slim_*: slim_api.cpp): the handle's common state, the ingest of the 2-D train matrix, librec's contains()
+// flags and its zero-cell filter, the dense-matrix reservation and the timed build (the prediction batch is abi_predict).
 // Every function that can fail takes the C function's name, `fn`, which opens its messages.  Internal.
 #pragma once
 #include <algorithm>
@@ -110,6 +111,44 @@ inline int pair_ingest(PairModelBase *h, const char *fn, int64_t n, const int32_
                 CMI_FAIL(h, CMI_E_INVALID, "%s: duplicate cell (user %d, item %d)", fn, scan_items ? m.idx[(size_t)k] : e,
                          scan_items ? e : m.idx[(size_t)k]);
     return CMI_OK;
+}
+
+// librec SparseVector.contains: Arrays.binarySearch over the whole index array of a vector built by set() -- capacity the next power
+// of two >= count, the tail zero.  Per entry of every row: does the row's own contains() find it?
+inline std::vector<uint8_t> pair_contains_flags(const PairHostCsr &m) {
+    std::vector<uint8_t> ok(m.idx.size(), 0);
+    for (size_t e = 0; e + 1 < m.ptr.size(); ++e) {
+        const int32_t b0 = m.ptr[e], cnt = m.ptr[e + 1] - b0;
+        int32_t cap = 1;
+        while (cap < cnt) cap <<= 1;
+        for (int32_t k = 0; k < cnt; ++k) {
+            const int32_t key = m.idx[(size_t)(b0 + k)];
+            int32_t low = 0, high = cap - 1;
+            while (low <= high) {
+                const int32_t mid = (int32_t)((uint32_t)(low + high) >> 1);
+                const int32_t v = mid < cnt ? m.idx[(size_t)(b0 + mid)] : 0;
+                if (v < key) low = mid + 1;
+                else if (v > key) high = mid - 1;
+                else {
+                    ok[(size_t)(b0 + k)] = 1;
+                    break;
+                }
+            }
+        }
+    }
+    return ok;
+}
+
+// the CSR without its zero-valued cells (librec's SparseMatrix.row() / column() leave them out)
+inline PairHostCsr pair_drop_zeros(const PairHostCsr &m) {
+    PairHostCsr o;
+    o.ptr.assign(m.ptr.size(), 0);
+    for (size_t row = 0; row + 1 < m.ptr.size(); ++row) {
+        for (int32_t q = m.ptr[row]; q < m.ptr[row + 1]; ++q)
+            if (m.val[(size_t)q] != 0.0) o.idx.push_back(m.idx[(size_t)q]), o.val.push_back(m.val[(size_t)q]);
+        o.ptr[row + 1] = (int32_t)o.idx.size();
+    }
+    return o;
 }
 
 inline hipError_t pair_upload(const PairHostCsr &m, int32_t **ptr, int32_t **idx, double **val, hipStream_t s) {

@@ -606,7 +606,7 @@ hipError_t RankWorkspace::need(Buf &b, size_t bytes, bool pinned) {
 }
 
 void RankWorkspace::release() {
-    Buf *dev[] = {&dA, &dB, &dS, &drc, &dcand, &dqu, &dqc, &dexptr, &dexcl, &dtop, &dscore, &dcount, &dB2, &dA2, &dS2, &dqg, &dqd, &dgu, &ddc, &dscr, &dSb, &dAb, &dcolc, &dM1, &dM1b, &dM2};
+    Buf *dev[] = {&dA, &dB, &dS, &drc, &dcand, &dqu, &dqc, &dexptr, &dexcl, &dtop, &dscore, &dcount, &dB2, &dA2, &dS2, &dqg, &dqd, &dgu, &dgq0, &ddc, &dscr, &dSb, &dAb, &dcolc, &dM1, &dM1b, &dM2};
     if (sel_stream) (void)hipStreamDestroy(sel_stream);
     sel_stream = nullptr;
     for (std::vector<hipEvent_t> *v : {&evgemm, &evsel}) {
@@ -1019,6 +1019,73 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     }
     // flops of THIS form: the two contractions it actually runs
     if (flops) *flops = 2.0 * (double)ng * (double)nc * (double)a.kp1 + (s2 ? 2.0 * (double)n_dc * (double)nc * (double)a.kp2 : 0.0);
+    return e;
+}
+
+hipError_t rank_run_device_slab(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankSlabFn &fill, double thold, int topn,
+                                const RankBatchFn &on_batch, float *ms) {
+    const auto t_setup = std::chrono::steady_clock::now();
+    const int nc = (int)plan.cand.size();
+    const int64_t nq = (int64_t)plan.qu.size();
+    const size_t ng = plan.gu.size();
+    int64_t bq = std::max<int64_t>(64, ((int64_t)1 << 30) / ((int64_t)std::max(nc, 1) * (int64_t)sizeof(double))); // the slab around 1 GiB
+    bq = std::min<int64_t>(bq, nq);
+    if (const char *e = getenv("CMI_RANK_BATCH")) bq = std::max<int64_t>(1, std::min<int64_t>(atoll(e), nq)); // tests: batching is invisible
+    hipError_t e = hipSuccess;
+    auto need = [&](RankWorkspace::Buf &b, size_t bytes, bool pinned = false) {
+        if (e == hipSuccess) e = ws.need(b, bytes, pinned);
+    };
+    need(ws.dS, (size_t)bq * (size_t)nc * sizeof(double) + RANK_SLAB_SLACK);
+    need(ws.dcand, (size_t)nc * 4);
+    need(ws.dgu, ng * 4);
+    need(ws.dgq0, (ng + 1) * 4);
+    need(ws.dexptr, (size_t)(nq + 1) * 8);
+    need(ws.dexcl, plan.excl_idx.size() * 4);
+    need(ws.dtop, (size_t)nq * topn * 4);
+    need(ws.dscore, (size_t)nq * topn * 8);
+    need(ws.dcount, (size_t)nq * 4);
+    need(ws.h_top, (size_t)nq * topn * 4, true);
+    need(ws.h_score, (size_t)nq * topn * 8, true);
+    need(ws.h_count, (size_t)nq * 4, true);
+    hipEvent_t *evs[] = {&ws.ev0, &ws.ev1};
+    for (hipEvent_t *ev : evs)
+        if (e == hipSuccess && !*ev) e = hipEventCreate(ev);
+    if (e != hipSuccess) return e;
+    double *dS = (double *)ws.dS.p, *dscore = (double *)ws.dscore.p;
+    int32_t *dcand = (int32_t *)ws.dcand.p, *dgu = (int32_t *)ws.dgu.p, *dgq0 = (int32_t *)ws.dgq0.p, *dexcl = (int32_t *)ws.dexcl.p;
+    int32_t *dtop = (int32_t *)ws.dtop.p, *dcount = (int32_t *)ws.dcount.p;
+    int64_t *dexptr = (int64_t *)ws.dexptr.p;
+    auto up = [&](void *d, const void *s, size_t bytes) {
+        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream);
+    };
+    up(dcand, plan.cand.data(), (size_t)nc * 4);
+    up(dgu, plan.gu.data(), ng * 4);
+    up(dgq0, plan.gq0.data(), plan.gq0.size() * 4);
+    up(dexptr, plan.excl_ptr.data(), (size_t)(nq + 1) * 8);
+    up(dexcl, plan.excl_idx.data(), plan.excl_idx.size() * 4);
+    if (e == hipSuccess) e = hipMemsetAsync(dtop, 0xff, (size_t)nq * topn * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(dscore, 0, (size_t)nq * topn * 8, stream);
+    if (e == hipSuccess) e = hipEventRecord(ws.ev0, stream);
+    ws.host_ms[1] = ms_since(t_setup);
+    const auto t_loop = std::chrono::steady_clock::now();
+    std::vector<std::pair<int64_t, int64_t>> batches; // all enqueued first, consumed behind the device (see rank_run_device)
+    const std::vector<int64_t> cuts = batch_cuts(nq, bq);
+    for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
+        const int64_t q0 = cuts[b];
+        const int n = (int)(cuts[b + 1] - q0);
+        e = fill(dS, dcand, nc, dgu, dgq0, plan.qg[(size_t)q0], plan.qg[(size_t)(q0 + n - 1)] + 1, q0, n, stream);
+        if (e == hipSuccess) e = rank_launch_select<double>(dS, n, nc, dexptr, dexcl, (int)q0, thold, topn, dtop, dscore, dcount, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((int32_t *)ws.h_top.p + (size_t)q0 * topn, dtop + (size_t)q0 * topn, (size_t)n * topn * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync((double *)ws.h_score.p + (size_t)q0 * topn, dscore + (size_t)q0 * topn, (size_t)n * topn * 8, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync((int32_t *)ws.h_count.p + q0, dcount + q0, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess) e = ws.batch_event(batches.size(), stream);
+        batches.emplace_back(q0, q0 + n);
+    }
+    if (e == hipSuccess) e = hipEventRecord(ws.ev1, stream);
+    e = ws.consume_batches(e, batches, on_batch, t_loop);
+    if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, ws.ev0, ws.ev1);
     return e;
 }
 

@@ -52,6 +52,7 @@ struct RankWorkspace {
     Buf dA, dB, dS, drc, dcand, dqu, dqc, dexptr, dexcl, dtop, dscore, dcount; // device
     Buf dB2, dA2, dS2, dqg, dqd, dgu, ddc, dscr;                                // device, split form (rank_run_device_split)
     Buf dcolc;                                                                  // split form: itemBias of the candidates (the S1 contraction adds it at the end)
+    Buf dgq0;                                                                   // slab form (rank_run_device_slab): group -> first query (+ end); it shares dgu with the split form
     Buf dSb, dAb;                                                               // split form: the second slab / operand buffer (batch b + 1 is contracted while batch b is selected)
     Buf dM1, dM1b, dM2;                                                         // split form: per-row maxima of S1 (per slab) / S2 over tiles of 64 candidates (the selection's tile pruning)
     hipStream_t sel_stream = nullptr;                                           // split form: the selection's stream
@@ -151,6 +152,13 @@ using RankBatchFn = std::function<void(int64_t, int64_t)>;
 // the measures and the users' means folded batch by batch behind the device, the averages.  `ready` checks the model's preconditions
 // and makes its device current; `score` runs the device loop over the plan and hands every batch of lists to on_batch.  Messages go
 // to `err`, prefixed "<what>: ".
+// The slab form, for a model whose scores are no contraction (SLIM: slim_kernels.hip): fill(dS, dcand, nc, dgu, dgq0, g0, g1, q0, nq,
+// stream) writes the fp64 scores of the queries [q0, q0 + nq), whose groups are g0 .. g1 (a group at a batch boundary comes in both
+// batches), into dS[(q - q0) * nc + c]; the exclusions are masked and the lists selected as in rank_run_device.
+using RankSlabFn = std::function<hipError_t(double *, const int32_t *, int, const int32_t *, const int32_t *, int, int, int64_t, int64_t, hipStream_t)>;
+hipError_t rank_run_device_slab(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankSlabFn &fill, double thold, int topn,
+                                const RankBatchFn &on_batch, float *ms);
+
 int rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, int n_users, int n_items, int64_t ctx_bound, const RankEvalIO &io,
                   const std::function<int()> &ready, const std::function<hipError_t(const RankPlan &, const RankBatchFn &)> &score);
 

@@ -802,6 +802,21 @@ hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, i
     return hipGetLastError();
 }
 
+template <typename T>
+hipError_t rank_launch_select(T *S, int nq, int nc, const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
+                              int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s) {
+    if (nq <= 0 || nc <= 0) return hipSuccess;
+    hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq);
+    if (topn <= 64)
+        hipLaunchKernelGGL(rank_topn_stream<T>, dim3((nq + 3) / 4), dim3(256), 0, s, (const T *)S, nq, nc, thold, topn, out_idx,
+                           out_score, out_count, q_base);
+    else
+        hipLaunchKernelGGL(rank_topn<T>, dim3((nq + 3) / 4), dim3(256), 0, s, S, nq, nc, thold, topn, out_idx, out_score,
+                           out_count, q_base);
+    return hipGetLastError();
+}
+template hipError_t rank_launch_select<double>(double *, int, int, const int64_t *, const int32_t *, int, double, int, int32_t *, double *, int32_t *,
+                                               hipStream_t);
 
 hipError_t rank_launch_split_operands(const RankSplitArgs &a, hipStream_t s) {
     // B1 = Q[j] for the candidates (k columns, zero-padded to kp1); itemBias[j] goes to colc: the contraction adds it at the end

@@ -50,6 +50,11 @@ hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, i
                              const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
                              int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s);
 
+// the exclusions masked and the top-N selected on a FINISHED slab S[nq][nc] (scores that are no contraction: SLIM): what
+// rank_launch_score does behind its contraction
+template <typename T>
+hipError_t rank_launch_select(T *S, int nq, int nc, const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
+                              int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s);
 
 // the split form of the MF family's scores (rank_kernels.hip, "the split form"): fp32 state
 struct RankSplitArgs {

@@ -669,6 +669,56 @@ int cmi_nmf_predict_batch(cmi_nmf_handle h, int64_t n, const int32_t *u, const i
  * (:113-126) */
 int cmi_nmf_last_iter_ms(cmi_nmf_handle h, float ms[3]);
 
+/* ---- SLIM (src/carskit/alg/baseline/ranking/SLIM.java; slim_api.cpp, slim_kernels.hip) -----------------------------------------
+ * Ning & Karypis' sparse linear method for top-N over the 2-D train matrix, fp64, bit-exact to the reference: coordinate descent over
+ * the listed cells of the item x item matrix W, column by column, every sum one left-to-right chain from 0.0 without FMA, in the
+ * iteration order of the reference's hash collections.  A cell whose value is 0 takes no part.  State: per item j its neighbour list
+ * nns(j), in the order SLIM.java walks it, and one weight per list entry, W[i][j].  The caller draws W.init() (SLIM.java:81-82) and
+ * hands over the listed cells.  No CPU fallback: without a device cmi_slim_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_slim_instance *cmi_slim_handle;
+/* SLIM.java:65-75,81 (W is numItems x numItems) */
+int cmi_slim_create(int n_users, int n_items, int device, unsigned flags, cmi_slim_handle *out);
+int cmi_slim_destroy(cmi_slim_handle h);
+const char *cmi_slim_last_error(cmi_slim_handle h);
+/* Recommender.java:1076-1081 (train) and SLIM.java:84 (userCache): the 2-D train matrix as n cells; a duplicate (u, i) or an id out of
+ * range -> CMI_E_INVALID; n >= 2^31 -> CMI_E_UNSUPPORTED */
+int cmi_slim_set_ratings(cmi_slim_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* SLIM.java:86-117.  knn > 0: buildCorrs(false) on the device (the kernel of cmi_knn_build; measure, shrinkage, min_rate, max_rate as
+ * there), then per item on the host the row's non-zero similarities into a java.util.HashMap in ascending order, the cut to the knn
+ * largest (Lists.sortMap's stable descending sort over the map's order, clear(), re-put) and the HashMultimap's value set (a HashSet of
+ * 4 slots that doubles at load 0.75); the list is that set's iteration order.  knn <= 0: every list is train.columns(), the items with
+ * an entry, ascending, the item itself included.  Device memory is reserved before anything runs: the n x n similarity matrix (knn > 0)
+ * and 20 bytes a list entry; what does not fit -> CMI_E_INVALID with the bytes needed (nothing is built).  A list whose map or set
+ * would treeify a bin -> CMI_E_UNSUPPORTED.  The weights start at 0.0 */
+int cmi_slim_build_neighbors(cmi_slim_handle h, int knn, int measure, int shrinkage, double min_rate, double max_rate);
+/* host-only: SLIM.java:96-109 for ONE item, as cmi_slim_build_neighbors runs it per row of the similarity matrix: sims[n] is the item's
+ * row (NaN: unset; 0.0 is not a neighbour), knn >= 1; out (room for n entries) receives the list in its iteration order, *n_out its
+ * length.  A list whose map or set would treeify a bin -> CMI_E_UNSUPPORTED (cmi_last_error(NULL) has the message) */
+int cmi_slim_cut_neighbors(int32_t n, const double *sims, int knn, int32_t *out, int32_t *n_out);
+/* the lists: ptr[n_items + 1] and idx[ptr[n_items]]; with idx == NULL only ptr is written (call it so first to size idx) */
+int cmi_slim_get_neighbors(cmi_slim_handle h, int64_t *ptr, int32_t *idx);
+/* SLIM.java:81-82,93,116: the weights, aligned with idx: w[p] = W[idx[p]][j] for ptr[j] <= p < ptr[j + 1] */
+int cmi_slim_set_weights(cmi_slim_handle h, const double *w);
+int cmi_slim_get_weights(cmi_slim_handle h, double *w);
+/* SLIM.java:127-176, one pass of buildModel's loop: for j ascending and i in nns(j), the coordinate update of W[i][j] from the means of
+ * r_ui * e_uj, r_ui^2 and e_uj^2 over column i's users, e_uj = r_uj - predict(u, j, true, i).  l1 and l2 are the DOUBLE values of the
+ * reference's float options (-l1 0.1 is (double)0.1f).  *loss is the reference's, bit for bit: one chain over the coordinates.
+ * NaN/Inf loss -> CMI_E_NUMERIC with *loss set */
+int cmi_slim_iterate(cmi_slim_handle h, double l1, double l2, double *loss);
+/* SLIM.java:183-209, predict(u, j) = predict(u, j, true, j) of n tuples: unbounded, context-free */
+int cmi_slim_predict_batch(cmi_slim_handle h, int64_t n, const int32_t *u, const int32_t *j, double *out);
+/* Recommender.evalRankings (Recommender.java:668-964) with SLIM.predict (SLIM.java:206-209) as the scorer: arguments, outputs and
+ * semantics exactly as cmi_eval_rankings above.  The scores of a user are computed once and serve all of the user's contexts */
+int cmi_slim_eval_rankings(cmi_slim_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                           const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
+                           const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy, double out[21],
+                           int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items,
+                           double *top_scores);
+/* device time of the last cmi_slim_build_neighbors' similarity build (SLIM.java:88), by events */
+int cmi_slim_last_build_ms(cmi_slim_handle h, float *ms);
+/* device time of the last cmi_slim_iterate, by events: ms[0] the sweep (SLIM.java:130-176), ms[1] the loss chain (:160) */
+int cmi_slim_last_iter_ms(cmi_slim_handle h, float ms[2]);
+
 #ifdef __cplusplus
 }
 #endif

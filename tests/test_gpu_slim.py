@@ -1,0 +1,438 @@
+"""SLIM on the GPU through the C ABI: neighbour lists entry for entry, W, every loss and every score bit for bit against the run of the
+reference's own source (tests/golden/reference_slim.json.gz) and, on generated matrices that take every path of the kernels, against the
+CPU restatement (tests/slim_ref.py); top-N lists and measures against selections from the restatement's scores; run-to-run
+reproducibility; the refusals; and the driver's ranking measures on DePaul (cv -k 5) against the restatement over the same folds."""
+import functools
+import math
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from carskit_amd import capi, dao
+from oracle import rank_oracle
+from tests import slim_ref as sref
+from tests.hostmirror import splitter
+from tests.hostmirror.javarand import JavaRandom
+from tests.util import same_bits_exact, to2d
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EXE = os.path.join(ROOT, "carskit_amd", "bin", "carskit-mi355x")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+CHUNK = 64    # users of a neighbour column per pass of the sweep kernel, one per lane
+RTILE = 256   # SLIM_RTILE: entries of a user's row the score kernel stages in LDS
+RUNS = sref.golden_runs()
+
+
+def flat(W):
+    return np.concatenate([np.asarray(w, dtype=np.float64) for w in W]) if len(W) else np.zeros(0)
+
+
+def all_tuples(nu, ni):
+    return np.repeat(np.arange(nu, dtype=np.int32), ni), np.tile(np.arange(ni, dtype=np.int32), nu)
+
+
+def instance(nu, ni, cells):
+    h = capi.SLIMInstance(nu, ni)
+    h.set_ratings([c[0] for c in cells], [c[1] for c in cells], [c[2] for c in cells])
+    return h
+
+
+def lists_of(h):
+    ptr, idx = h.neighbors()
+    return [idx[ptr[j]:ptr[j + 1]].tolist() for j in range(h.n_items)]
+
+
+@pytest.mark.parametrize("run", RUNS, ids=[r["name"] for r in RUNS])
+def test_golden_runs_match_the_reference_run(run):
+    nu, ni = run["n_users"], run["n_items"]
+    h = instance(nu, ni, run["cells"])
+    h.build_neighbors(run["knn"], run["measure"], run["shrinkage"])
+    assert lists_of(h) == run["neighbors"]
+    assert same_bits_exact(h.weights(), np.zeros(sum(len(x) for x in run["neighbors"])))
+    h.set_weights(flat(run["W0"]))
+    for it, want in enumerate(run["loss"], 1):
+        loss = h.iterate(run["l1"], run["l2"])
+        assert same_bits_exact([loss], [want]), (it, loss, want)
+        if it in run["W"]:
+            assert same_bits_exact(h.weights(), flat(run["W"][it])), (it, np.argwhere(h.weights() != flat(run["W"][it]))[:5])
+    tu, tj = all_tuples(nu, ni)
+    assert same_bits_exact(h.predict(tu, tj).reshape(nu, ni), run["predict"])
+    assert all(ms >= 0.0 for ms in h.last_iter_ms()) and sum(h.last_iter_ms()) > 0.0 and h.last_build_ms() >= 0.0
+    h.close()
+
+
+# ---- top-N ---------------------------------------------------------------------------------------------------------------------
+def select(cand, queries, scores, thold, num_recs):
+    """the lists cmi_slim_eval_rankings must return, from a score matrix: per query the candidates not excluded whose score is above the
+    threshold, by descending score, ties in candidate order, the first num_recs"""
+    out = {}
+    for u, c, correct, excl in queries:
+        ex = set(excl)
+        sc = [(j, float(scores[u, j])) for p, j in enumerate(cand) if p not in ex and scores[u, j] > thold]
+        sc.sort(key=lambda kv: -kv[1])
+        if correct and sc:
+            out[(u, c)] = sc[:num_recs]
+    return out
+
+
+def check_rankings(h, scores, train, test, tol=1e-12, **kw):
+    """lists (items and scores) exactly those selected from `scores`; the 21 measures within the tolerance tests/test_gpu_ranking.py
+    uses for fp64 state"""
+    res, lists = h.eval_rankings(train, test, with_lists=True, **kw)
+    thold, num_recs = kw.get("bin_thold", -1.0), kw.get("num_recs", 10)
+    cand, queries = capi.rank_plan(h.n_users, h.n_items, train, test, thold, kw.get("num_ignore", 0))
+    want = select(cand, queries, scores, thold, num_recs)
+    assert set(lists) == set(want) and len(want) > 0
+    for key in want:
+        assert [i for i, _ in lists[key]] == [i for i, _ in want[key]], key
+        assert same_bits_exact([s for _, s in lists[key]], [s for _, s in want[key]]), key
+    tup = lambda d: list(zip(*[np.asarray(a).tolist() for a in d]))  # noqa: E731
+    ref, ref_lists = rank_oracle.eval_rankings(lambda u, j, c: float(scores[u, j]), tup(train), tup(test), **kw)
+    assert ref_lists == want
+    for m in rank_oracle.MEASURES:
+        a, b = res[m], ref[m]
+        print("%s gpu %r ref %r" % (m, a, b))
+        assert (math.isnan(a) and math.isnan(b)) or abs(a - b) <= tol, (m, a, b)
+    assert res["D5"] == res["D10"] == res["DN"] == 0.0
+    return lists
+
+
+def contextual_split(cells, n_ctx, seed, test_share=0.25):
+    """(u, j, ctx, r) train and test tuples over the cells of a 2-D matrix: a cell appears in one to three contexts"""
+    rng = np.random.default_rng(seed)
+    tr, te = [], []
+    for u, j, v in cells:
+        for c in rng.choice(n_ctx, int(rng.integers(1, 4)), replace=False).tolist():
+            (te if rng.random() < test_share else tr).append((u, j, c, v if v != 0.0 else 1.0))
+    arr = lambda ts: (np.array([t[0] for t in ts], np.int32), np.array([t[1] for t in ts], np.int32),  # noqa: E731
+                      np.array([t[2] for t in ts], np.int32), np.array([t[3] for t in ts]))
+    return arr(sorted(tr)), arr(sorted(te))
+
+
+@pytest.mark.parametrize("name", ["knn_matrix knn=5 l1=0.1 l2=0.5", "knn_matrix knn=0 l1=1 l2=1", "edge_matrix knn=13 l1=0.1 l2=0.5"])
+def test_eval_rankings_on_golden_models(name):
+    run = next(r for r in RUNS if r["name"] == name)
+    h = instance(run["n_users"], run["n_items"], run["cells"])
+    h.build_neighbors(run["knn"], run["measure"], run["shrinkage"])
+    last = max(run["W"])
+    h.set_weights(flat(run["W"][last]))
+    if last == len(run["loss"]):   # the golden scores belong to the last recorded weights
+        scores = run["predict"]
+    else:
+        s = sref.Slim(run["n_users"], run["n_items"], run["cells"])
+        scores = s.scores(run["neighbors"], run["W"][last])
+    train, test = contextual_split(run["cells"], 4, 11)
+    for kw in (dict(bin_thold=-1.0, num_recs=10), dict(bin_thold=-1.0, num_recs=5, strategy="uc"), dict(bin_thold=0.05, num_recs=10, num_ignore=3)):
+        check_rankings(h, scores, train, test, **kw)
+    h.close()
+
+
+# ---- kernel edges: the sweep -----------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def sweep_matrix():
+    """200 users x 72 items.  Users 0..39 rate items 0..65 with probability 0.35, so every pair of those items has common users; item 66
+    has 1 user, 67 has CHUNK - 1, 68 CHUNK, 69 CHUNK + 1, 70 has 2 * CHUNK + 1 (users 40..195 fill them and rate two base items each);
+    user 196 has 1 item, user 197 has 64, user 198 has 65; item 71 is empty and so is user 199."""
+    rng = np.random.default_rng(20261102)
+    nu, ni = 200, 72
+    val = lambda: float(rng.integers(2, 11)) / 2.0  # noqa: E731
+    cells = {}
+    for u in range(40):
+        for j in range(66):
+            if rng.random() < 0.35:
+                cells[(u, j)] = val()
+    cells[(0, 66)] = val()
+    for j, cnt in ((67, CHUNK - 1), (68, CHUNK), (69, CHUNK + 1), (70, 2 * CHUNK + 1)):
+        for u in rng.choice(np.arange(1, 196), cnt, replace=False).tolist():
+            cells[(u, j)] = val()
+    for u in range(40, 196):
+        for j in rng.choice(66, 2, replace=False).tolist():
+            cells[(u, j)] = val()
+    for u, cnt in ((196, 1), (197, 64), (198, 65)):
+        for j in range(cnt):
+            cells[(u, j)] = val()
+    cl = sorted((u, j, v) for (u, j), v in cells.items())
+    return nu, ni, cl, sref.Slim(nu, ni, cl)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_lists(knn):
+    nu, ni, cells, s = sweep_matrix()
+    nbr = s.neighbors(knn, "cos", -1)
+    assert s.treeified == 0
+    return nbr
+
+
+def test_sweep_matrix_has_the_edges():
+    nu, ni, cells, s = sweep_matrix()
+    assert [len(s.cols[j]) for j in range(66, 72)] == [1, CHUNK - 1, CHUNK, CHUNK + 1, 2 * CHUNK + 1, 0] and not s.rows[199]
+    assert [len(s.rows[u]) for u in (196, 197, 198)] == [1, 64, 65]
+    nbr = sweep_lists(65)
+    assert max(len(x) for x in nbr) == 65 and all(any(j in lst for lst in nbr) for j in range(66, 71))  # every special column is walked
+    assert max(len(x) for x in sweep_lists(64)) == 64 and {len(x) for x in sweep_lists(1)} == {0, 1}
+    assert len(cells) < 2500
+
+
+@pytest.mark.parametrize("knn,l1,l2", [(1, 0.1, 0.5), (64, 0.1, 0.5), (65, 1.0, 1.0), (0, 0.0, 0.0)])
+def test_sweep_kernel_edges(knn, l1, l2):
+    """lists of 1, 64 and 65 neighbours and all items (knn = 0, with its i == j coordinate, l1 = l2 = 0); neighbour columns of 1, 63, 64, 65
+    and 129 users; weights drawn in (0, 1), far above the solution, so the first pass takes the negative branch"""
+    nu, ni, cells, s = sweep_matrix()
+    nbr = sweep_lists(knn)
+    l1, l2 = sref.f32(l1), sref.f32(l2)
+    rng = np.random.default_rng(knn)
+    W = [rng.random(len(lst)) for lst in nbr]
+    h = instance(nu, ni, cells)
+    h.build_neighbors(knn, "cos", -1)
+    assert lists_of(h) == nbr
+    h.set_weights(flat(W))
+    for it in range(2):
+        want = s.iterate(nbr, W, l1, l2)
+        loss = h.iterate(l1, l2)
+        assert same_bits_exact([loss], [want]), (it, loss, want)
+        assert same_bits_exact(h.weights(), flat(W)), (it, np.argwhere(h.weights() != flat(W))[:5])
+        if it == 0 and knn != 1:   # (a list of one neighbour predicts 0.0: its gradient cannot be negative)
+            assert (flat(W) < 0).any()
+    if knn == 0:
+        j = nbr[0][0]
+        assert j in nbr[j] and W[j][nbr[j].index(j)] != 0.0          # W[j][j] is updated, and never scored
+    tu, tj = all_tuples(nu, ni)
+    assert same_bits_exact(h.predict(tu, tj).reshape(nu, ni), s.scores(nbr, W))
+    h.close()
+
+
+@functools.lru_cache(maxsize=None)
+def long_list_matrix():
+    """520 users x 1032 items, 1030 of them with an entry: at knn = 0 every list has 1030 neighbours, more than the WTILE = 1024 weights
+    the sweep keeps in LDS, so every column takes the kernel instance whose weights stay in global memory.  User u < 515 rates items 2u
+    and 2u + 1: coordinate 2u + 1 reads, for that user, the weight coordinate 2u has just written.  Users 515..518 rate 40 items each."""
+    rng = np.random.default_rng(20261104)
+    nu, ni, live = 520, 1032, 1030
+    cells = {}
+    for u in range(515):
+        cells[(u, 2 * u)], cells[(u, 2 * u + 1)] = float(rng.integers(1, 6)), float(rng.integers(1, 6))
+    for u in range(515, 519):
+        for j in rng.choice(live, 40, replace=False).tolist():
+            cells[(u, j)] = float(rng.integers(2, 11)) / 2.0
+    cl = sorted((u, j, v) for (u, j), v in cells.items())
+    return nu, ni, cl, sref.Slim(nu, ni, cl)
+
+
+def test_lists_longer_than_the_lds_tile():
+    """1030 neighbours a column: the sweep with the weights in global memory, two iterations, bit for bit, the i == j coordinate
+    included.  (1030^2 coordinates is the smallest case that takes this path; the restatement needs about 4 s an iteration.)"""
+    nu, ni, cells, s = long_list_matrix()
+    nbr = s.neighbors(0)
+    assert len(nbr[0]) == 1030 > 1024 and len(cells) < 1300
+    l1, l2 = sref.f32(0.1), sref.f32(0.5)
+    rng = np.random.default_rng(4)
+    W = [0.05 * rng.random(len(lst)) for lst in nbr]
+    h = instance(nu, ni, cells)
+    h.build_neighbors(0)
+    assert lists_of(h) == nbr
+    h.set_weights(flat(W))
+    for it in range(2):
+        want = s.iterate(nbr, W, l1, l2)
+        loss = h.iterate(l1, l2)
+        assert same_bits_exact([loss], [want]), (it, loss, want)
+        assert same_bits_exact(h.weights(), flat(W)), (it, np.argwhere(h.weights() != flat(W))[:5])
+    assert all(W[j][nbr[j].index(j)] != 0.0 for j in (0, 1, 1029)) and (flat(W) < 0).any() and (flat(W) > 0).any()
+    tu = np.repeat(np.arange(510, 520, dtype=np.int32), len(range(0, ni, 7)))
+    tj = np.tile(np.arange(0, ni, 7, dtype=np.int32), 10)
+    assert same_bits_exact(h.predict(tu, tj), [s.predict(nbr, W, int(a), int(b)) for a, b in zip(tu, tj)])
+    h.close()
+
+
+def test_gradient_at_the_threshold_zeroes_the_weight():
+    """one user, two items of rating 1, no weights yet: every coordinate's gradient is exactly 1.0.  l1 = 1.0 is not below it: the weight
+    becomes 0.0; the next float below 1.0 is: the weight moves"""
+    cells = [(0, 0, 1.0), (0, 1, 1.0)]
+    s = sref.Slim(1, 2, cells)
+    for l1, moves in ((1.0, False), (sref.f32(np.nextafter(np.float32(1.0), np.float32(0.0))), True)):
+        h = instance(1, 2, cells)
+        h.build_neighbors(0)
+        nbr = lists_of(h)
+        assert nbr == [[0, 1], [0, 1]]
+        h.set_weights(np.zeros(4))
+        W = [np.zeros(2), np.zeros(2)]
+        want = s.iterate(nbr, W, l1, 0.0)
+        assert same_bits_exact([h.iterate(l1, 0.0)], [want]) and same_bits_exact(h.weights(), flat(W))
+        assert bool(h.weights().any()) == moves
+        h.close()
+
+
+def test_same_model_same_bits():
+    nu, ni, cells, s = sweep_matrix()
+    nbr = sweep_lists(65)
+    W0 = np.random.default_rng(9).random(sum(len(x) for x in nbr))
+    h = instance(nu, ni, cells)
+    out = []
+    for _ in range(2):
+        h.build_neighbors(65, "cos", -1)
+        h.set_weights(W0)
+        losses = [h.iterate(0.5, 0.25), h.iterate(0.5, 0.25)]
+        out.append((losses, lists_of(h), h.weights()))
+    assert same_bits_exact(out[0][0], out[1][0]) and out[0][1] == out[1][1] and same_bits_exact(out[0][2], out[1][2])
+    h.close()
+
+
+# ---- kernel edges: the scores and the selection -----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def score_matrix():
+    """8 users x 520 items, knn = 0 (every list is the 330 items with an entry), weights drawn: user 0 has 1 item, user 1 has 64, user 2
+    has 65, user 3 has RTILE, user 4 has RTILE + 44 (read from global memory), users 5 and 6 share the rest, user 7 none"""
+    rng = np.random.default_rng(20261103)
+    nu, ni, live = 8, 520, 330
+    cells = {}
+    for u, cnt in ((0, 1), (1, 64), (2, 65), (3, RTILE), (4, RTILE + 44), (5, 30), (6, 31)):
+        for j in rng.choice(live, cnt, replace=False).tolist():
+            cells[(u, j)] = float(rng.integers(1, 6))
+    for j in range(live):
+        cells.setdefault((int(rng.integers(5, 7)), j), 3.0)       # every one of the 330 items has an entry
+    cl = sorted((u, j, v) for (u, j), v in cells.items())
+    s = sref.Slim(nu, ni, cl)
+    nbr = s.neighbors(0)
+    W = [rng.random(len(lst)) - 0.3 for lst in nbr]
+    return nu, ni, cl, s, nbr, W, s.scores(nbr, W)
+
+
+@pytest.mark.parametrize("n_cand,num_recs", [(63, 10), (64, 70), (65, 10), (513, 70), (513, 10)])
+def test_score_kernel_and_selection_edges(n_cand, num_recs):
+    """user rows of 1, 64, 65, RTILE and more than RTILE entries; 63, 64, 65 and 513 candidates (513: three blocks of the score kernel);
+    lists of 10 (the streaming selection) and 70 (one pass per rank); a user with four contexts whose exclusions differ"""
+    nu, ni, cells, s, nbr, W, scores = score_matrix()
+    assert [len(s.rows[u]) for u in range(5)] == [1, 64, 65, RTILE, RTILE + 44] and not s.rows[7]
+    rng = np.random.default_rng(n_cand)
+    cand = sorted(rng.choice(ni, n_cand, replace=False).tolist())
+    tr, te = [], []
+    for p, j in enumerate(cand):                                   # the candidates are the items of the training tuples
+        tr.append((int(rng.integers(0, nu)), j, int(rng.integers(0, 4)), 4.0))
+    for c in range(4):                                             # user 4: four contexts, a different exclusion set in each
+        for j in cand[c::7]:
+            tr.append((4, j, c, 2.0))
+    tr = sorted(set((u, j, c) for u, j, c, _ in tr))
+    seen = set(tr)
+    for u in range(nu):
+        for c in range(4):
+            for j in rng.choice(cand, 3, replace=False).tolist():
+                if (u, j, c) not in seen:
+                    te.append((u, j, c, 5.0))
+    train = tuple(np.array(x, dt) for x, dt in zip(zip(*[(u, j, c, 3.0) for u, j, c in tr]), (np.int32, np.int32, np.int32, np.float64)))
+    test = tuple(np.array(x, dt) for x, dt in zip(zip(*sorted(set(te))), (np.int32, np.int32, np.int32, np.float64)))
+    h = instance(nu, ni, cells)
+    h.build_neighbors(0)
+    assert lists_of(h) == nbr
+    h.set_weights(flat(W))
+    tu, tj = all_tuples(nu, ni)
+    assert same_bits_exact(h.predict(tu, tj).reshape(nu, ni), scores)
+    lists = check_rankings(h, scores, train, test, bin_thold=-1e9, num_recs=num_recs)
+    plan_cand, queries = capi.rank_plan(nu, ni, train, test, -1e9, 0)
+    assert len(plan_cand) == n_cand
+    ex4 = {c: tuple(e) for u, c, _, e in queries if u == 4}
+    assert len(ex4) == 4 and len(set(ex4.values())) == 4           # one group of four queries, four exclusion lists
+    assert max(len(v) for v in lists.values()) == min(num_recs, max(n_cand - len(e) for _, _, _, e in queries))
+    assert (scores[7] == 0.0).all() and any(k[0] == 7 for k in lists)  # the user without a row: every score 0.0, ties in candidate order
+    os.environ["CMI_RANK_BATCH"] = "3"                             # batches that cut user 4's group: the same lists
+    try:
+        assert h.eval_rankings(train, test, bin_thold=-1e9, num_recs=num_recs, with_lists=True)[1] == lists
+    finally:
+        del os.environ["CMI_RANK_BATCH"]
+    h.close()
+
+
+# ---- refusals ----------------------------------------------------------------------------------------------------------------------
+def test_refusals():
+    h = capi.SLIMInstance(3, 3)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0, 0], [1, 1], [1.0, 2.0])
+    assert e.value.code == capi.E_INVALID and "duplicate" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0, 3], [0, 1], [1.0, 2.0])
+    assert e.value.code == capi.E_INVALID and "out of range" in str(e.value)
+    for call in (lambda: h.build_neighbors(2), h.neighbors, h.weights, lambda: h.iterate(0.1, 0.1), lambda: h.predict([0], [1]),
+                 h.last_iter_ms, h.last_build_ms):
+        with pytest.raises(capi.CmiError) as e:
+            call()
+        assert e.value.code == capi.E_INVALID
+    h.set_ratings([0, 1, 2, 0], [1, 1, 0, 0], [1.0, 2.0, 3.0, 2.0])
+    with pytest.raises(capi.CmiError) as e:
+        h.build_neighbors(2, measure=17)
+    assert e.value.code == capi.E_INVALID and "measure" in str(e.value)
+    h.build_neighbors(2, "cos", -1)
+    with pytest.raises(capi.CmiError) as e:
+        h.iterate(0.1, 0.1)                                          # lists, but no weights
+    assert e.value.code == capi.E_INVALID and "cmi_slim_set_weights first" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_weights(np.zeros(len(h.neighbors()[1]) + 1))
+    assert e.value.code == capi.E_INVALID and "shape" in str(e.value)
+    w = np.ones(len(h.neighbors()[1]))
+    w[0] = np.nan
+    h.set_weights(w)
+    with pytest.raises(capi.CmiError) as e:
+        h.iterate(0.1, 0.1)
+    assert e.value.code == capi.E_NUMERIC and "NaN" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.predict([0], [3])
+    assert e.value.code == capi.E_INVALID
+    h.close()
+    with pytest.raises(capi.CmiError) as e:
+        capi.SLIMInstance(2, 0)
+    assert e.value.code == capi.E_INVALID
+
+
+def test_all_items_lists_that_do_not_fit_are_refused_with_the_bytes():
+    n = 150_000                                                      # knn <= 0: n lists of n entries, 20 bytes each: 450 GB
+    h = capi.SLIMInstance(1, n)
+    h.set_ratings(np.zeros(n, np.int32), np.arange(n, dtype=np.int32), np.ones(n))
+    with pytest.raises(capi.CmiError) as e:
+        h.build_neighbors(0)
+    assert e.value.code == capi.E_INVALID and "bytes of device memory" in str(e.value) and str(n * n * 20)[:4] in str(e.value)
+    with pytest.raises(capi.CmiError):
+        h.neighbors()                                                # nothing was built
+    h.close()
+
+
+# ---- the driver ------------------------------------------------------------------------------------------------------------------
+def test_driver_parity_depaul(tmp_path):
+    iters, knn, l1, l2, k = 3, 5, 0.1, 0.5, 10
+    shutil.copyfile(os.path.join(GOLDEN, "depaul_ratings_compact.csv"), tmp_path / "ratings.txt")
+    dao.transform(str(tmp_path / "ratings.txt"), str(tmp_path / "train.csv"))
+    d = dao.DataDAO(str(tmp_path / "train.csv")).rating_data()
+    labels, nf = splitter.split_folds(d.n, 5, 1)
+    conf = open(os.path.join(GOLDEN, "depaul_setting.conf")).read().replace("PLACEHOLDER_SET_BY_TEST", str(tmp_path / "ratings.txt"))
+    assert "num.max.iter=100" in conf and "num.factors=%d" % k in conf and "--rand-seed 1" in conf and "item.ranking=off" in conf
+    conf = conf.replace("recommender=biasedmf", "recommender=slim").replace("num.max.iter=100", "num.max.iter=%d" % iters)
+    (tmp_path / "slim.conf").write_text(conf + "SLIM=-l1 %g -l2 %g -k %d\nsimilarity=cos\nnum.shrinkage=30\n" % (l1, l2, knn))
+    p = subprocess.run([EXE, "-c", str(tmp_path / "slim.conf"), "--precise"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    m = re.search(r"PRECISE SLIM folds=5 Pre10=(\S+) Rec10=(\S+) AUC10=(\S+) MAP10=(\S+) NDCG10=(\S+) MRR10=(\S+)", p.stdout)
+    assert m and "Final Results by SLIM, Pre5: " in p.stdout, p.stdout[-500:]   # a top-N run although item.ranking is off
+    want = {}
+    for f in range(1, nf + 1):
+        tr, te = splitter.kth_fold(d, labels, f)
+        u, i, r = to2d(tr.u, tr.j, tr.r)
+        s = sref.Slim(d.n_users, d.n_items, list(zip(u.tolist(), i.tolist(), r.tolist())))
+        nbr = s.neighbors(knn, "cos", 30, d.min_rate, d.max_rate)
+        assert s.treeified == 0
+        W = sref.init_weights(JavaRandom(1), d.n_users, d.n_items, k, nbr)      # P and Q drawn (and dropped) first
+        last = 0.0
+        for it in range(1, iters + 1):
+            loss = s.iterate(nbr, W, sref.f32(l1), sref.f32(l2))
+            delta, last = last - loss, loss
+            if it > 1 and delta < 1e-5:
+                break
+        scores = s.scores(nbr, W)
+        tup = lambda x: list(zip(x.u.tolist(), x.j.tolist(), x.ctx.tolist(), x.r.tolist()))  # noqa: E731
+        res, _ = rank_oracle.eval_rankings(lambda a, b, c: float(scores[a, b]), tup(tr), tup(te), bin_thold=-1.0, num_recs=10)
+        for name in ("Pre10", "Rec10", "AUC10", "MAP10", "NDCG10", "MRR10"):
+            want[name] = want.get(name, 0.0) + res[name] / nf
+    for g, name in zip(m.groups(), ("Pre10", "Rec10", "AUC10", "MAP10", "NDCG10", "MRR10")):
+        print(name, g, want[name])
+        assert abs(float(g) - want[name]) <= 1e-12, (name, g, want[name])
