@@ -6,8 +6,7 @@
 //   * cmi_transform_compact_to_binary: DataTransformer.TransformationFromCompactToBinary
 //     (src/carskit/data/processor/DataTransformer.java:231-259, 266-329) including the row order of the
 //     rewritten train.csv, which is the iteration order of a java.util.HashMap<String,...> keyed by the
-//     input line (String.hashCode, hash spreading h ^ (h>>>16), power-of-two table grown at load 0.75,
-//     buckets in index order, insertion order inside a bucket).
+//     input line (String.hashCode; the table's rule is in java_hash.hpp).
 // Plain C++ (no GPU involved); exported through the same C ABI so the Java/ctypes hosts and the tests share it.
 #include "../../include/carskit_mi355x.h"
 #include "abi.hpp"
@@ -32,8 +31,10 @@
 #include <unistd.h>
 
 #include "host_pool.hpp"
+#include "java_hash.hpp"
 
 using cmi::host_threads;
+using cmi::JavaHashTable;
 using cmi::parallel_ranges;
 
 namespace {
@@ -1048,31 +1049,17 @@ int32_t jstring_hash(const std::string &s) { // String.hashCode over UTF-16 code
     return (int32_t)h;
 }
 
-// Keys in the order `for (K k : map.keySet())` visits them after inserting `keys` (first insertion of each
-// distinct key) into a default-constructed HashMap: table 16, doubled whenever ++size > 0.75*capacity; bucket
-// index (h ^ (h >>> 16)) & (cap-1); a resize splits every bin preserving relative order, so the final order is
-// bucket index ascending, then insertion order.  (Bins that reach 8 entries while the table has >= 64 buckets
-// are treeified and their root moves to the front; that needs >= 8 keys in one of >= 64 buckets and is not
-// modelled -- the function reports whether any bin reached that size.)
+// Positions of the keys in the order `for (K k : map.keySet())` visits them after inserting `distinct_keys` in order into a
+// default-constructed HashMap (java_hash.hpp).  *treeified: a put made a bin of 9 nodes in a table of 64 slots or more at the time of
+// the put; that bin becomes a tree, whose order is not modelled, so the order returned is then not guaranteed.
 std::vector<size_t> java_hashmap_order(const std::vector<std::string> &distinct_keys, bool *treeified) {
-    size_t cap = 16;
-    while ((double)distinct_keys.size() > 0.75 * (double)cap) cap <<= 1;
-    std::vector<std::pair<uint32_t, size_t>> order;
-    order.reserve(distinct_keys.size());
-    std::vector<uint32_t> load(cap, 0);
-    bool tree = false;
-    for (size_t i = 0; i < distinct_keys.size(); ++i) {
-        const uint32_t h = (uint32_t)jstring_hash(distinct_keys[i]);
-        const uint32_t b = (h ^ (h >> 16)) & (uint32_t)(cap - 1);
-        order.emplace_back(b, i);
-        if (++load[b] >= 8 && cap >= 64) tree = true;
-    }
-    std::stable_sort(order.begin(), order.end(), [](const std::pair<uint32_t, size_t> &a, const std::pair<uint32_t, size_t> &b) { return a.first < b.first; });
-    std::vector<size_t> out;
-    out.reserve(order.size());
-    for (auto &p : order) out.push_back(p.second);
-    if (treeified) *treeified = tree;
-    return out;
+    std::vector<uint32_t> hash(distinct_keys.size());
+    for (size_t i = 0; i < hash.size(); ++i) hash[i] = (uint32_t)jstring_hash(distinct_keys[i]);
+    const auto hash_at = [&](size_t i) { return hash[i]; };
+    JavaHashTable map(16);
+    map.fill(hash_at, hash.size());
+    if (treeified) *treeified = map.tree;
+    return map.order(hash_at, hash.size());
 }
 
 } // namespace

@@ -4,6 +4,7 @@
 // -ffp-contract=off), and division / sqrt are the correctly rounded IEEE operations Java uses.
 #include "knn_kernels.hpp"
 #include "eval_device.hpp"
+#include "java_hash.hpp"
 #include "../../include/carskit_mi355x.h"
 
 namespace cmi {
@@ -120,48 +121,30 @@ hipError_t knn_launch_row_stats(PairCsr rows, int n, double *mean, double *norm2
 }
 
 // ---- prediction --------------------------------------------------------------------------------------------------------------
-// java.util.HashMap<Integer, Double> (JDK 8): bucket = (h ^ h >>> 16) & (cap - 1); a bin is a list in insertion order; a put that makes
-// a list of 9 nodes calls treeifyBin, which doubles a table of fewer than 64 slots and treeifies the bin otherwise; ++size > threshold
-// doubles the table.  Resizing keeps the relative order inside a bin, so as long as no bin is treeified the iteration order is
-// (bucket at the final capacity, insertion order).
-__device__ __forceinline__ uint32_t jhash(int32_t k) { return (uint32_t)k ^ ((uint32_t)k >> 16); }
-
-// the table's growth while keys kat(0..n-1) are put in that order; cap == 0: a new map (16 slots at the first put).  *tree: a bin
+// ItemKNN / UserKNN.predict iterate a java.util.HashMap<Integer, Double>: java_hash.hpp has its rule (Integer.hashCode() is the value).
+// The table's growth while keys kat(0..n-1) are put in that order; cap == 0: a new map (16 slots at the first put).  *tree: a bin
 // would be treeified (its order is not modelled).  Called by the whole wave; cnt: 64 ints of LDS.
 template <class K>
 __device__ void hm_grow(K kat, int n, int &cap, int &thr, int &tree, int32_t *cnt) {
     const int lane = threadIdx.x;
     __shared__ int32_t sh[3];
     if (cap == 0) cap = 16, thr = 12;
-    if (lane == 0) { // tables below 64 slots: a serial walk with the bin counts (at most 48 puts)
-        int t = 0;
-        auto recount = [&](int upto) {
-            for (int b = 0; b < 64; ++b) cnt[b] = 0;
-            for (int s = 0; s < upto; ++s) ++cnt[jhash(kat(s)) & (cap - 1)];
-        };
-        if (cap < 64) recount(0);
-        while (t < n && cap < 64) {
-            const int b = jhash(kat(t)) & (cap - 1);
-            const bool grow = ++cnt[b] >= 9; // treeifyBin on a small table: resize()
-            ++t;
-            const int before = cap;
-            if (grow) cap <<= 1, thr <<= 1;
-            if (t > thr) cap <<= 1, thr <<= 1; // ++size > threshold
-            if (cap != before && cap < 64) recount(t);
-        }
-        sh[0] = t, sh[1] = cap, sh[2] = thr;
+    if (lane == 0) { // tables below 64 slots: the serial walk (at most 48 puts)
+        sh[0] = java_walk_below_64(kat, n, cap, thr, cnt);
+        sh[1] = cap, sh[2] = thr;
     }
     __syncthreads();
     const int t0 = sh[0];
     cap = sh[1], thr = sh[2];
     __syncthreads();
-    // 64 slots and more: the capacity follows the size alone; a bin reaching 9 nodes is treeified.  Nine keys in one bucket of such a
-    // table share their low 6 hash bits, so a histogram mod 64 rules most maps out before the exact check.
+    // 64 slots and more, the parallel form of JavaHashTable::fill's rule: the capacity follows the size alone, and a put that finds 8
+    // nodes in its bin at the capacity in force for that put is refused.  Nine keys in one bucket of such a table share their low 6
+    // hash bits, so a histogram mod 64 rules most maps out before the exact count.
     int flag = 0;
     if (t0 < n) {
         if (lane < 64) cnt[lane] = 0;
         __syncthreads();
-        for (int i = lane; i < n; i += 64) atomicAdd(&cnt[jhash(kat(i)) & 63], 1);
+        for (int i = lane; i < n; i += 64) atomicAdd(&cnt[java_spread(kat(i)) & 63], 1);
         __syncthreads();
         bool maybe = false;
         for (int b = 0; b < 64; ++b) maybe |= cnt[b] >= 9;
@@ -170,9 +153,9 @@ __device__ void hm_grow(K kat, int n, int &cap, int &thr, int &tree, int32_t *cn
             for (int i = t0 + lane; i < n; i += 64) {
                 int ci = cap, ti = thr;
                 while (i > ti) ci <<= 1, ti <<= 1; // the table when key i is put (size i)
-                const uint32_t hi = jhash(kat(i));
+                const uint32_t hi = java_spread(kat(i));
                 int same = 0;
-                for (int s = 0; s < i; ++s) same += ((jhash(kat(s)) ^ hi) & (uint32_t)(ci - 1)) == 0;
+                for (int s = 0; s < i; ++s) same += ((java_spread(kat(s)) ^ hi) & (uint32_t)(ci - 1)) == 0;
                 flag |= same >= 8;
             }
         }
@@ -219,10 +202,10 @@ __global__ __launch_bounds__(64) void knn_predict_kernel(PairCsr L, const double
             hm_grow([&](int i) { return key[i]; }, m, cap, thr, tree, cnt);
             const uint32_t mask1 = (uint32_t)(cap - 1);
             for (int i = lane; i < m; i += 64) { // HashMap position: (bucket, insertion)
-                const uint32_t bi = jhash(key[i]) & mask1;
+                const uint32_t bi = java_spread(key[i]) & mask1;
                 int p = 0;
                 for (int s = 0; s < m; ++s) {
-                    const uint32_t bs = jhash(key[s]) & mask1;
+                    const uint32_t bs = java_spread(key[s]) & mask1;
                     p += bs < bi || (bs == bi && s < i);
                 }
                 pos[i] = p;
@@ -242,10 +225,10 @@ __global__ __launch_bounds__(64) void knn_predict_kernel(PairCsr L, const double
                 hm_grow([&](int r) { return key[sel[r]]; }, knn, cap, thr, tree, cnt);
                 const uint32_t mask2 = (uint32_t)(cap - 1);
                 for (int r = lane; r < knn; r += 64) {
-                    const uint32_t br = jhash(key[sel[r]]) & mask2;
+                    const uint32_t br = java_spread(key[sel[r]]) & mask2;
                     int p = 0;
                     for (int s = 0; s < knn; ++s) {
-                        const uint32_t bs = jhash(key[sel[s]]) & mask2;
+                        const uint32_t bs = java_spread(key[sel[s]]) & mask2;
                         p += bs < br || (bs == br && s < r);
                     }
                     pos[p] = sel[r];

@@ -18,6 +18,7 @@
 #include "abi.hpp"
 #include "cmi_instance.hpp"
 #include "host_pool.hpp"
+#include "java_hash.hpp"
 #include "rank_host.hpp"
 #include "rank_kernels.hpp"
 
@@ -25,20 +26,15 @@ using namespace cmi;
 
 namespace {
 
-// ---- java.util.HashSet<Integer> iteration order -----------------------------------------------------------------
-// Integer.hashCode() is the value; HashMap spreads h ^ (h >>> 16), indexes with (cap-1), doubles the table when
-// size > 0.75*cap, and on a split keeps relative order inside a bucket, so iteration = (bucket, insertion order).
+// ---- java.util.HashSet<Integer> iteration order (java_hash.hpp; Integer.hashCode() is the value) ---------------------------------
+// The set's tree flag is not acted on: ranking neither refuses nor reorders a set with a tree bin (a known limit).
 std::vector<int32_t> java_int_hashset_order(const std::vector<int32_t> &first_seen) {
-    size_t cap = 16;
-    while ((double)first_seen.size() > 0.75 * (double)cap) cap <<= 1;
-    std::vector<std::pair<uint32_t, int32_t>> keyed(first_seen.size());
-    for (size_t i = 0; i < first_seen.size(); ++i) {
-        const uint32_t h = (uint32_t)first_seen[i];
-        keyed[i] = {(uint32_t)((h ^ (h >> 16)) & (cap - 1)), (int32_t)i};
-    }
-    std::stable_sort(keyed.begin(), keyed.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
-    std::vector<int32_t> out(first_seen.size());
-    for (size_t i = 0; i < keyed.size(); ++i) out[i] = first_seen[keyed[i].second];
+    const auto hash_at = [&](size_t i) { return (uint32_t)first_seen[i]; };
+    JavaHashTable set(16);
+    set.fill(hash_at, first_seen.size());
+    std::vector<int32_t> out;
+    out.reserve(first_seen.size());
+    for (size_t p : set.order(hash_at, first_seen.size())) out.push_back(first_seen[p]);
     return out;
 }
 

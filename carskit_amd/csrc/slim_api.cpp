@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "host_pool.hpp"
+#include "java_hash.hpp"
 #include "knn_kernels.hpp"
 #include "pair_host.hpp"
 #include "rank_host.hpp"
@@ -110,77 +111,35 @@ extern "C" int cmi_slim_set_ratings(cmi_slim_handle h, int64_t n, const int32_t 
 }
 
 namespace {
-// The iteration order of a java.util.HashMap<Integer, Double> / HashSet<Integer> of JDK 8: a bin holds its keys in insertion order and
-// a resize keeps the order inside a bin, so the order is (bin at the final capacity, insertion).  The table doubles when the size
-// passes 0.75 x capacity, and when a put makes a bin of 9 nodes in a table below 64 slots (treeifyBin); in a table of 64 slots or more
-// that put builds a tree bin, whose order is not modelled: put() returns false.
-struct JavaIntTable {
-    int cap = 0, thr = 0;
-    std::vector<int32_t> keys, cnt;
-    std::vector<double> vals;
-    static uint32_t hash(int32_t k) {
-        const uint32_t x = (uint32_t)k;
-        return x ^ (x >> 16);
-    }
-    void init(int slots) { // slots 16: new HashMap(); 4: new HashSet(3) behind HashMultimap.create()
-        cap = slots, thr = slots * 3 / 4;
-        keys.clear(), vals.clear();
-        cnt.assign((size_t)cap, 0);
-    }
-    void grow() {
-        cap *= 2, thr *= 2;
-        cnt.assign((size_t)cap, 0);
-        for (int32_t k : keys) ++cnt[hash(k) & (uint32_t)(cap - 1)];
-    }
-    bool put(int32_t k, double v) { // a key the table does not hold
-        const uint32_t b = hash(k) & (uint32_t)(cap - 1);
-        const int nodes = cnt[b]++;
-        keys.push_back(k), vals.push_back(v);
-        if (nodes >= 8) {
-            if (cap >= 64) return false;
-            grow();
-        }
-        if ((int)keys.size() > thr) grow();
-        return true;
-    }
-    void clear() { // keeps the table
-        keys.clear(), vals.clear();
-        std::fill(cnt.begin(), cnt.end(), 0);
-    }
-    void order(std::vector<int32_t> &pos) const {
-        pos.resize(keys.size());
-        std::iota(pos.begin(), pos.end(), 0);
-        std::stable_sort(pos.begin(), pos.end(), [&](int32_t a, int32_t b) {
-            return (hash(keys[(size_t)a]) & (uint32_t)(cap - 1)) < (hash(keys[(size_t)b]) & (uint32_t)(cap - 1));
-        });
-    }
-};
-
-// SLIM.java:96-109 for one item: `sims` is the item's row of the similarity matrix (NaN unset).  false: a bin would treeify.
+// SLIM.java:96-109 for one item: `sims` is the item's row of the similarity matrix (NaN unset).  Three tables of java_hash.hpp: the
+// map nns, the same map kept by clear() and refilled with the survivors of the cut, and the set guava keeps per key.  false: a bin
+// would treeify.
 bool slim_cut(const double *sims, int n, int knn, std::vector<int32_t> &out) {
-    JavaIntTable nns, set;
-    std::vector<int32_t> pos;
-    nns.init(16);
+    std::vector<int32_t> key; // the keys of the table being filled, in put order
+    const auto hash_at = [&](size_t t) { return (uint32_t)key[t]; };
     for (int i = 0; i < n; ++i)
-        if (sims[i] == sims[i] && sims[i] != 0.0)
-            if (!nns.put(i, sims[i])) return false;
-    nns.order(pos);
-    if (knn < (int)nns.keys.size()) {
-        std::stable_sort(pos.begin(), pos.end(), [&](int32_t a, int32_t b) { return nns.vals[(size_t)a] > nns.vals[(size_t)b]; });
-        std::vector<int32_t> k((size_t)knn);
-        std::vector<double> v((size_t)knn);
-        for (int t = 0; t < knn; ++t) k[(size_t)t] = nns.keys[(size_t)pos[(size_t)t]], v[(size_t)t] = nns.vals[(size_t)pos[(size_t)t]];
-        nns.clear();
-        for (int t = 0; t < knn; ++t)
-            if (!nns.put(k[(size_t)t], v[(size_t)t])) return false;
-        nns.order(pos);
+        if (sims[i] == sims[i] && sims[i] != 0.0) key.push_back(i);
+    JavaHashTable nns(16);
+    nns.fill(hash_at, key.size());
+    if (nns.tree) return false;
+    std::vector<size_t> pos = nns.order(hash_at, key.size());
+    if (knn < (int)key.size()) { // Lists.sortMap(nns, true): stable, descending by value; nns.clear(); the first knn are put back
+        std::stable_sort(pos.begin(), pos.end(), [&](size_t a, size_t b) { return sims[key[a]] > sims[key[b]]; });
+        std::vector<int32_t> kept((size_t)knn);
+        for (size_t t = 0; t < kept.size(); ++t) kept[t] = key[pos[t]];
+        key.swap(kept);
+        nns.fill(hash_at, key.size());
+        if (nns.tree) return false;
+        pos = nns.order(hash_at, key.size());
     }
-    set.init(4);
-    for (int32_t p : pos)
-        if (!set.put(nns.keys[(size_t)p], 0.0)) return false;
-    set.order(pos);
-    out.resize(pos.size());
-    for (size_t t = 0; t < pos.size(); ++t) out[t] = set.keys[(size_t)pos[t]];
+    std::vector<int32_t> in_map(key.size()); // the set receives the keys in the map's order
+    for (size_t t = 0; t < in_map.size(); ++t) in_map[t] = key[pos[t]];
+    key.swap(in_map);
+    JavaHashTable set(4);
+    set.fill(hash_at, key.size());
+    if (set.tree) return false;
+    out.clear();
+    for (size_t p : set.order(hash_at, key.size())) out.push_back(key[p]);
     return true;
 }
 } // namespace

@@ -515,8 +515,8 @@ int cmi_dao_rating_scale(cmi_dao_handle h, double *out, int32_t cap, int32_t *n)
 const char *cmi_dao_raw_id(cmi_dao_handle h, int kind, int32_t idx);
 
 /* Iteration order of a default java.util.HashMap<String,?> (JDK 8+) after inserting n DISTINCT keys in the given
- * order: positions[i] = index of the i-th key `for (k : map.keySet())` visits.  *treeified = 1 if a bin reached
- * the treeify threshold (order then not guaranteed).  Used by the transformer below. */
+ * order: positions[i] = index of the i-th key `for (k : map.keySet())` visits.  *treeified = 1 if a put made a bin of
+ * 9 nodes in a table of 64 slots or more at the time of the put (order then not guaranteed).  Used by the transformer below. */
 int cmi_java_hashmap_order(int64_t n, const char *const *keys, int64_t *positions, int *treeified);
 /* DataTransformer.TransformationFromCompactToBinary + PublishNewRatingFiles + getHeader
  * (src/carskit/data/processor/DataTransformer.java:231-259,266-329,155-163): rewrites a compact-format file

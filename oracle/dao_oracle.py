@@ -117,8 +117,9 @@ def jstring_hash(s):
 class JavaHashMap:
     """java.util.HashMap<String, V> insertion + iteration, as an explicit table of bins (lists).  put() appends to
     the bin (tail insertion), resize doubles the table and splits every bin into lo/hi preserving order; iteration
-    walks the table in index order.  Treeification (bins of >= 8 entries) is not simulated; `max_bin` records the
-    largest bin ever seen so a caller can tell whether it could have happened."""
+    walks the table in index order.  A put that makes a bin of 9 entries in a table below 64 slots resizes it (treeifyBin).
+    Tree bins (9 entries in a table of 64 slots or more) are not simulated; `max_bin` records the largest bin ever seen so a
+    caller can tell whether one could have happened."""
 
     def __init__(self):
         self.table = None
@@ -156,6 +157,8 @@ class JavaHashMap:
                 return
         b.append((key, value, h))
         self.max_bin = max(self.max_bin, len(b))
+        if len(b) >= 9 and len(self.table) < 64:        # treeifyBin, before the size test as in putVal
+            self._resize()
         self.size += 1
         if self.size > self.threshold:
             self._resize()

@@ -104,19 +104,25 @@ def mean(xs):
 
 
 def java_int_hashset_order(values):
-    """Iteration order of a java.util.HashSet<Integer> after add()ing `values` in order (duplicates ignored)."""
-    seen, keys = set(), []
-    for v in values:
-        if v not in seen:
-            seen.add(v)
-            keys.append(v)
-    cap = 16
-    while len(keys) > 0.75 * cap:
-        cap <<= 1
-    def bucket(v):
+    """Iteration order of a java.util.HashSet<Integer> after add()ing `values` in order (duplicates ignored), put by put: the table
+    starts at 16 slots, doubles when a put makes a bin of 9 nodes while it has fewer than 64 slots (treeifyBin resizes such a table),
+    then doubles when the size passes 0.75 x slots.  Bins keep insertion order, so iteration is by (bucket, insertion).  Tree bins
+    (9 nodes in a table of 64 slots or more) are not modelled."""
+    def bucket(v, cap):
         h = v & 0xFFFFFFFF
         return (h ^ (h >> 16)) & (cap - 1)
-    return [k for _, _, k in sorted((bucket(k), i, k) for i, k in enumerate(keys))]
+    cap, thr, seen, keys = 16, 12, set(), []
+    for v in values:
+        if v in seen:
+            continue
+        seen.add(v)
+        nodes = sum(bucket(k, cap) == bucket(v, cap) for k in keys) if cap < 64 else 0    # at most 48 keys while that small
+        keys.append(v)
+        if nodes >= 8:
+            cap, thr = cap * 2, thr * 2
+        if len(keys) > thr:
+            cap, thr = cap * 2, thr * 2
+    return [k for _, _, k in sorted((bucket(k, cap), i, k) for i, k in enumerate(keys))]
 
 
 MEASURES = ("Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN", "MAP5", "MAP10", "MAPN",

@@ -148,6 +148,64 @@ def test_java_hashmap_order_closed_form_equals_simulation():
         assert tree == (m.max_bin >= 8 and n > 48) or not tree
 
 
+def test_java_hashmap_order_ninth_node_of_a_small_bin_doubles_the_table():
+    # String.hashCode of the nine first keys = 0 (mod 64): the ninth doubles the 16-slot table although 11 <= 12, so "aq" (3120) goes
+    # to bucket 16 of 32 and "ab" (3105) to bucket 1
+    keys = ["bb", "dd", "ff", "hh", "jj", "ll", "nn", "pp", "rr", "aq", "ab"]
+    assert all(dao_oracle.jstring_hash(k) % 64 == 0 for k in keys[:9])
+    want = keys[:9] + ["ab", "aq"]
+    m = dao_oracle.JavaHashMap()
+    for k in keys:
+        m.put(k, 1)
+    assert m.keys() == want and len(m.table) == 32
+    pos, tree = dao.java_hashmap_order(keys)
+    assert [keys[i] for i in pos] == want and not tree
+
+
+def _short_keys(want, count, skip=0):
+    """the short lower-case strings, shortest first, whose spread hash satisfies want(): `count` of them after the first `skip`"""
+    import itertools
+    import string
+    out = []
+    for n in (1, 2, 3):
+        for t in itertools.product(string.ascii_lowercase, repeat=n):
+            k = "".join(t)
+            if want(dao_oracle.JavaHashMap._spread(k)):
+                out.append(k)
+                if len(out) == skip + count:
+                    return out[skip:]
+    raise AssertionError("not enough short keys")
+
+
+def _simulated(keys):
+    """the oracle's key order, and whether some put made a bin of 9 in a table of 64 slots or more at the time of that put"""
+    m, tree = dao_oracle.JavaHashMap(), False
+    for k in keys:
+        slots = len(m.table) if m.table else 16
+        m.put(k, 1)
+        b = m._spread(k) & (slots - 1)
+        tree |= slots >= 64 and sum((m._spread(q) & (slots - 1)) == b for q in m.keys()) >= 9
+    return m.keys(), len(m.table), tree
+
+
+def test_java_hashmap_tree_flag_is_decided_at_the_capacity_of_the_put():
+    """30 keys bring the table to 64 slots; then nine keys share bin 5 of 64 (five in bin 5 of 128, four in bin 69), so the ninth
+    makes a tree bin; 12 more keys double the table to 128 slots, where no bin holds more than five of them.  The flag must be set
+    all the same.  Eight keys in bin 5 of 128 make no tree bin at either capacity: the flag must be clear."""
+    head = _short_keys(lambda h: h % 64 != 5, 30)
+    tail = _short_keys(lambda h: h % 64 != 5, 12, skip=30)
+    nine = _short_keys(lambda h: h % 128 == 5, 5) + _short_keys(lambda h: h % 128 == 69, 4)
+    eight = _short_keys(lambda h: h % 128 == 5, 8)
+    for mid, want_tree in ((nine, True), (eight, False)):
+        keys = head + mid + tail
+        assert len(set(keys)) == len(keys)
+        order, slots, sim_tree = _simulated(keys)
+        assert slots == 128 and sim_tree == want_tree                 # the case is what it says
+        pos, tree = dao.java_hashmap_order(keys)
+        assert tree == want_tree
+        assert [keys[i] for i in pos] == order
+
+
 def test_java_string_hash_known_answers():
     # published String.hashCode values
     assert dao_oracle.jstring_hash("") == 0

@@ -58,11 +58,54 @@ def test_hashset_order_small_tables():
     assert ro.java_int_hashset_order([65536, 0, 1]) == [0, 65536, 1]
 
 
+# the ninth key of bin 0 doubles the 16-slot table although 11 <= 12 (treeifyBin resizes a table below 64 slots): 16 moves to bucket 16
+NINE_IN_A_BIN = [0, 64, 128, 192, 256, 320, 384, 448, 512, 16, 1]
+NINE_IN_A_BIN_ORDER = [0, 64, 128, 192, 256, 320, 384, 448, 512, 1, 16]
+
+
+def test_hashset_order_ninth_node_of_a_small_bin_doubles_the_table():
+    assert ro.java_int_hashset_order(NINE_IN_A_BIN) == NINE_IN_A_BIN_ORDER
+    assert capi.java_int_hashset_order(NINE_IN_A_BIN).tolist() == NINE_IN_A_BIN_ORDER
+
+
+def test_rank_plan_candidates_when_a_small_bin_doubles_the_table():
+    j = np.array(NINE_IN_A_BIN + [64, 1], dtype=np.int32)        # first-seen order is the set's put order
+    u = np.arange(len(j), dtype=np.int32) % 3
+    c = np.arange(len(j), dtype=np.int32) % 2
+    r = np.full(len(j), 4.0)
+    test = (np.array([0], np.int32), np.array([16], np.int32), np.array([0], np.int32), np.array([5.0]))
+    cand, _ = capi.rank_plan(3, 513, (u, j, c, r), test)
+    assert cand == NINE_IN_A_BIN_ORDER
+
+
+def test_hashset_order_thirteen_keys_two_resizes():
+    """13 keys, nine of them = 0 (mod 16) and put first.  They are multiples of 64, so the 9th put doubles the table to 32 slots
+    (threshold 24) and leaves all nine in bin 0; the 10th key, 32, is a 10th node there and doubles it to 64 slots (threshold 48).
+    Size 13 > 12 then adds nothing: both thresholds were doubled with the tables.  Sized by 13 > 12 alone the table would have 32
+    slots, where 32 sits in bin 0 and 33 in bin 1; a table doubled without its threshold would reach 128 slots, where 64 leaves
+    bin 0."""
+    keys = [0, 64, 128, 192, 256, 320, 384, 448, 512, 32, 33, 1, 48]
+    want = [0, 64, 128, 192, 256, 320, 384, 448, 512, 1, 32, 33, 48]
+    assert ro.java_int_hashset_order(keys) == want
+    assert capi.java_int_hashset_order(keys).tolist() == want
+    # nine multiples of 16 that part at 32 slots: one resize, by the 9th node; 13 <= 24 adds none
+    keys = [0, 16, 32, 48, 64, 80, 96, 112, 128, 1, 2, 17, 33]
+    want = [0, 32, 64, 96, 128, 1, 33, 2, 16, 48, 80, 112, 17]
+    assert ro.java_int_hashset_order(keys) == want
+    assert capi.java_int_hashset_order(keys).tolist() == want
+
+
 def test_hashset_order_library_matches_oracle():
     rng = np.random.default_rng(5)
     for n, hi in ((0, 10), (1, 10), (12, 100), (13, 100), (200, 1000), (5000, 200000)):
         v = rng.integers(0, hi, size=n)
         assert capi.java_int_hashset_order(v).tolist() == ro.java_int_hashset_order(v.tolist())
+    # strided ids fill one bin of a small table: the 9-node resize, in put order and shuffled
+    for stride in (16, 64, 128):
+        for n in range(9, 50):
+            v = np.arange(n) * stride
+            for w in (v, rng.permutation(v), np.concatenate([rng.permutation(v[:n // 2]), rng.integers(0, 1000, 20)])):
+                assert capi.java_int_hashset_order(w).tolist() == ro.java_int_hashset_order(w.tolist()), (stride, n)
 
 
 def _tiny():
