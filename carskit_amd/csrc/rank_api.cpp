@@ -589,91 +589,88 @@ void rank_average(const RankPlan &plan, int strategy, const int32_t *top_count, 
     total.mean(out);
 }
 
-hipError_t RankWorkspace::need(Buf &b, size_t bytes, bool pinned) {
+static double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+hipError_t RankEvents::grow(size_t n) {
+    while (v.size() < n) {
+        hipEvent_t ev = nullptr;
+        if (hipError_t e = hipEventCreateWithFlags(&ev, flags)) return e;
+        v.push_back(ev);
+    }
+    return hipSuccess;
+}
+
+hipError_t RankEvents::record(size_t i, hipStream_t stream) {
+    if (hipError_t e = grow(i + 1)) return e;
+    return hipEventRecord(v[i], stream);
+}
+
+void RankEvents::destroy() {
+    for (hipEvent_t ev : v) (void)hipEventDestroy(ev);
+    v.clear();
+}
+
+static hipError_t grow_buf(RankWorkspace::Buf &b, size_t bytes, bool pinned) {
     bytes = std::max<size_t>(bytes, 8);
     if (b.cap >= bytes) return hipSuccess;
     if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
+    b = RankWorkspace::Buf();
     const size_t want = bytes + bytes / 8; // a little head room: the next fold's test set is rarely the same size
     hipError_t e = pinned ? hipHostMalloc(&b.p, want, hipHostMallocDefault) : hipMalloc(&b.p, want);
     if (e == hipSuccess) b.cap = want;
     return e;
 }
+hipError_t RankWorkspace::need(Dev b, size_t bytes) { return grow_buf(dev[b], bytes, false); }
+hipError_t RankWorkspace::need(Pin b, size_t bytes) { return grow_buf(pin[b], bytes, true); }
 
 void RankWorkspace::release() {
-    Buf *dev[] = {&dA, &dB, &dS, &drc, &dcand, &dqu, &dqc, &dexptr, &dexcl, &dtop, &dscore, &dcount, &dB2, &dA2, &dS2, &dqg, &dqd, &dgu, &dgq0, &ddc, &dscr, &dSb, &dAb, &dcolc, &dM1, &dM1b, &dM2};
     if (sel_stream) (void)hipStreamDestroy(sel_stream);
     sel_stream = nullptr;
-    for (std::vector<hipEvent_t> *v : {&evgemm, &evsel}) {
-        for (hipEvent_t ev : *v) (void)hipEventDestroy(ev);
-        v->clear();
-    }
+    for (RankEvents *ev : {&ev01, &evb, &evgemm, &evsel, &evk}) ev->destroy();
     plan_valid = false;
-    for (const void *&r : resident) r = nullptr;
-    for (Buf *b : dev) {
-        if (b->p) (void)hipFree(b->p);
-        *b = Buf();
+    for (Buf &b : dev) {
+        if (b.p) (void)hipFree(b.p);
+        b = Buf();
     }
-    Buf *host[] = {&h_top, &h_score, &h_count};
-    for (Buf *b : host) {
-        if (b->p) (void)hipHostFree(b->p);
-        *b = Buf();
+    for (Buf &b : pin) {
+        if (b.p) (void)hipHostFree(b.p);
+        b = Buf();
     }
-    hipEvent_t *evs[] = {&ev0, &ev1};
-    for (hipEvent_t *e : evs) {
-        if (*e) (void)hipEventDestroy(*e);
-        *e = nullptr;
-    }
-    for (hipEvent_t e : evb)
-        if (e) (void)hipEventDestroy(e);
-    evb.clear();
-    for (hipEvent_t e : evk)
-        if (e) (void)hipEventDestroy(e);
-    evk.clear();
 }
 
-hipError_t RankWorkspace::kernel_event(size_t i, hipStream_t stream) {
-    while (evk.size() <= i) {
-        hipEvent_t ev = nullptr;
-        if (hipError_t e = hipEventCreate(&ev)) return e;
-        evk.push_back(ev);
-    }
-    return hipEventRecord(evk[i], stream);
+// The copy is tagged only once it is enqueued: a failed upload is repeated by the next evaluation.
+hipError_t RankWorkspace::upload_plan(Dev b, const void *host, size_t bytes, hipStream_t stream, bool always) {
+    if (dev[b].plan_gen == plan_gen && !always) return hipSuccess;
+    if (bytes)
+        if (hipError_t e = hipMemcpyAsync(dev[b].p, host, bytes, hipMemcpyHostToDevice, stream)) return e;
+    dev[b].plan_gen = plan_gen;
+    return hipSuccess;
 }
 
-hipError_t RankWorkspace::batch_event(size_t b, hipStream_t stream) {
-    while (evb.size() <= b) {
-        hipEvent_t ev = nullptr;
-        if (hipError_t e = hipEventCreateWithFlags(&ev, hipEventDisableTiming)) return e;
-        evb.push_back(ev);
-    }
-    return hipEventRecord(evb[b], stream);
+void RankWorkspace::forget_uploads() {
+    for (Buf &b : dev) b.plan_gen = 0;
 }
 
 hipError_t RankWorkspace::consume_batches(hipError_t e, const std::vector<std::pair<int64_t, int64_t>> &batches,
                                           const std::function<void(int64_t, int64_t)> &on_batch,
                                           std::chrono::steady_clock::time_point t_loop) {
     const bool times = getenv("CMI_PLAN_TIMES") != nullptr;
-    auto at = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count(); };
-    if (times) fprintf(stderr, "rank loop: all batches enqueued at %.3f ms\n", at());
+    if (times) fprintf(stderr, "rank loop: all batches enqueued at %.3f ms\n", ms_since(t_loop));
     for (size_t b = 0; b + 1 < batches.size() && e == hipSuccess; ++b) {
-        e = hipEventSynchronize(evb[b]);
-        if (times) fprintf(stderr, "rank loop: batch %zu's lists on the host at %.3f ms\n", b, at());
+        e = hipEventSynchronize(evb.at(b));
+        if (times) fprintf(stderr, "rank loop: batch %zu's lists on the host at %.3f ms\n", b, ms_since(t_loop));
         if (e == hipSuccess && on_batch) on_batch(batches[b].first, batches[b].second);
     }
-    if (times) fprintf(stderr, "rank loop: host done with all but the last batch at %.3f ms\n", at());
-    if (e == hipSuccess) e = hipEventSynchronize(ev1); // recorded behind the last batch's copies
-    if (times) fprintf(stderr, "rank loop: last batch's lists on the host at %.3f ms\n", at());
-    host_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count();
+    if (times) fprintf(stderr, "rank loop: host done with all but the last batch at %.3f ms\n", ms_since(t_loop));
+    if (e == hipSuccess) e = hipEventSynchronize(ev01.at(1)); // recorded behind the last batch's copies
+    if (times) fprintf(stderr, "rank loop: last batch's lists on the host at %.3f ms\n", ms_since(t_loop));
+    host_ms[2] = ms_since(t_loop);
     const auto t_tail = std::chrono::steady_clock::now();
     if (e == hipSuccess && !batches.empty() && on_batch) on_batch(batches.back().first, batches.back().second);
-    host_ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_tail).count();
+    host_ms[3] = ms_since(t_tail);
     return e;
-}
-
-static double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
 // Batch boundaries over n units of at most b.  The host turns a batch's lists into measures while the device works on the batches
@@ -702,88 +699,141 @@ static std::vector<int64_t> batch_cuts(int64_t n, int64_t b) {
     return cuts;
 }
 
+// ---- the device loop: one skeleton (rank_run_batches), three forms that plug their scoring into it ----------------------------------------
+namespace {
+using W = RankWorkspace;
+
+// Units per batch: a score slab (nc elements of `elem` bytes per unit) of about 1 GiB, at least 64 units, at most all of them.  A unit
+// is what the form cuts into batches: a query, or a user group in the split form.
+int64_t rank_batch_size(int64_t units, int nc, size_t elem) {
+    int64_t b = std::max<int64_t>(64, ((int64_t)1 << 30) / ((int64_t)std::max(nc, 1) * (int64_t)elem));
+    b = std::min<int64_t>(b, units);
+    if (const char *e = getenv("CMI_RANK_BATCH")) b = std::max<int64_t>(1, std::min<int64_t>(atoll(e), units)); // tests: batching is invisible
+    return b;
+}
+
+struct RankBatch {
+    int64_t q0, q1;   // the batch's queries
+    hipStream_t done; // the stream on which their lists are complete
+};
+
+// What a form supplies.  Its steps read the workspace's pointers when they run: the skeleton has allocated everything by then.
+struct RankForm {
+    std::chrono::steady_clock::time_point t_setup; // when the form's set-up began (host_ms[1] counts from here)
+    int64_t units = 0, batch = 0; // units to cut (batch_cuts) and rank_batch_size of them
+    struct Sized {
+        W::Dev buf;
+        size_t bytes;
+        const void *host;
+    };
+    std::vector<Sized> buffers;     // its own device buffers (per-evaluation data: never resident)
+    std::vector<Sized> plan_arrays; // the arrays of the plan it reads on the device (RankWorkspace::upload_plan)
+    bool upload_always = false;     // copy them on every evaluation, resident or not (see rank_run_device)
+    std::function<void(const char *)> lap;                                         // optional: told the set-up's phases as they end (CMI_PLAN_TIMES)
+    std::function<hipError_t()> prepare;                                           // optional: operands built once, in front of the timed span
+    std::function<hipError_t()> start;                                             // optional: work done once inside the timed span
+    std::function<hipError_t(size_t b, int64_t u0, int64_t u1, RankBatch &)> enqueue; // scores and selects the units [u0, u1) of batch b
+    std::function<hipError_t(size_t n_batches)> finish;                            // optional: after the lists are on the host
+};
+template <typename V>
+RankForm::Sized plan_array(W::Dev buf, const std::vector<V> &v) {
+    return {buf, v.size() * sizeof(V), v.data()};
+}
+
+hipError_t rank_run_batches(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, int topn, const RankForm &f, const RankBatchFn &on_batch,
+                            float *ms) {
+    auto lap = [&](const char *w) {
+        if (f.lap) f.lap(w);
+    };
+    const size_t nq = plan.qu.size();
+    const struct {
+        W::Dev d;
+        W::Pin h;
+        size_t per_query;
+    } lists[3] = {{W::DTOP, W::H_TOP, (size_t)topn * 4}, {W::DSCORE, W::H_SCORE, (size_t)topn * 8}, {W::DCOUNT, W::H_COUNT, 4}};
+    hipError_t e = hipSuccess;
+    for (const RankForm::Sized &b : f.buffers)
+        if (e == hipSuccess) e = ws.need(b.buf, b.bytes);
+    for (const RankForm::Sized &a : f.plan_arrays)
+        if (e == hipSuccess) e = ws.need(a.buf, a.bytes);
+    for (const auto &l : lists) {
+        if (e == hipSuccess) e = ws.need(l.d, nq * l.per_query);
+        if (e == hipSuccess) e = ws.need(l.h, nq * l.per_query);
+    }
+    if (e == hipSuccess) e = ws.ev01.grow(2);
+    if (e != hipSuccess) return e;
+    lap("buffers");
+    for (const RankForm::Sized &a : f.plan_arrays)
+        if (e == hipSuccess) e = ws.upload_plan(a.buf, a.host, a.bytes, stream, f.upload_always);
+    lap("uploads");
+    if (e == hipSuccess) e = hipMemsetAsync(ws.d<void>(W::DTOP), 0xff, nq * topn * 4, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(ws.d<void>(W::DSCORE), 0, nq * topn * 8, stream);
+    if (e == hipSuccess && f.prepare) e = f.prepare();
+    if (e == hipSuccess) e = ws.ev01.record(0, stream);
+    if (e == hipSuccess && f.start) e = f.start();
+    lap("memsets + operand launches");
+    ws.host_ms[1] = ms_since(f.t_setup);
+    const auto t_loop = std::chrono::steady_clock::now();
+    // Every batch is enqueued before the host waits for anything (a stream orders a batch's scoring behind the selection that last read
+    // the same slab); the host then turns the lists into measures batch by batch as their copies land, behind the device, and can
+    // never hold the device up.
+    std::vector<std::pair<int64_t, int64_t>> batches;
+    const std::vector<int64_t> cuts = batch_cuts(f.units, f.batch);
+    hipStream_t done = stream;
+    for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
+        RankBatch r{0, 0, stream};
+        e = f.enqueue(b, cuts[b], cuts[b + 1], r);
+        done = r.done;
+        for (const auto &l : lists)
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(ws.h<char>(l.h) + (size_t)r.q0 * l.per_query, ws.d<char>(l.d) + (size_t)r.q0 * l.per_query,
+                                   (size_t)(r.q1 - r.q0) * l.per_query, hipMemcpyDeviceToHost, done);
+        if (e == hipSuccess) e = ws.evb.record(b, done);
+        batches.emplace_back(r.q0, r.q1);
+    }
+    // the loop ends when the last batch's lists are on the host: ev1 on the main stream, behind the other stream's last batch event
+    if (done != stream && e == hipSuccess && !batches.empty()) e = hipStreamWaitEvent(stream, ws.evb.at(batches.size() - 1), 0);
+    if (e == hipSuccess) e = ws.ev01.record(1, stream);
+    e = ws.consume_batches(e, batches, on_batch, t_loop);
+    if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, ws.ev01.at(0), ws.ev01.at(1));
+    if (e == hipSuccess && f.finish) e = f.finish(batches.size());
+    return e;
+}
+} // namespace
+
 template <typename T>
 hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankOperands<T> &ops, double thold, int topn,
-                           const std::function<void(int64_t, int64_t)> &on_batch, float *ms, double *flops) {
-    const auto t_setup = std::chrono::steady_clock::now();
-    const std::vector<int32_t> &cand = plan.cand, &qu = plan.qu, &qc = plan.qc, &excl_idx = plan.excl_idx;
-    const std::vector<int64_t> &excl_ptr = plan.excl_ptr;
-    const int nc = (int)cand.size();
-    const int64_t nq = (int64_t)qu.size();
+                           const RankBatchFn &on_batch, float *ms, double *flops) {
+    RankForm f;
+    f.t_setup = std::chrono::steady_clock::now();
+    const int nc = (int)plan.cand.size();
+    const int64_t nq = (int64_t)plan.qu.size();
     // operand rows are zero-padded to the GEMM's k step; row counts rounded up to the 128-row block tile (pad rows are
     // never written back)
     const int kp = (ops.k_logical + 15) / 16 * 16; // multiple of both kernels' k step
     auto up128 = [](int64_t v) { return (size_t)((v + 127) / 128 * 128); };
-    // query batch: keep the score slab around 1 GiB
-    int64_t bq = std::max<int64_t>(64, ((int64_t)1 << 30) / ((int64_t)nc * (int64_t)sizeof(T)));
-    bq = std::min<int64_t>(bq, nq);
-    if (const char *e = getenv("CMI_RANK_BATCH")) bq = std::max<int64_t>(1, std::min<int64_t>(atoll(e), nq)); // tests: batching is invisible
-
-    hipError_t e = hipSuccess;
-    auto need = [&](RankWorkspace::Buf &b, size_t bytes, bool pinned = false) {
-        if (e == hipSuccess) e = ws.need(b, bytes, pinned);
-    };
-    need(ws.dB, up128(nc) * kp * sizeof(T));
-    need(ws.dA, up128(bq) * kp * sizeof(T));
-    need(ws.dS, (size_t)bq * (size_t)nc * sizeof(T));
-    need(ws.drc, (size_t)bq * sizeof(T));
-    need(ws.dcand, (size_t)nc * 4);
-    need(ws.dqu, (size_t)nq * 4);
-    need(ws.dqc, (size_t)nq * 4);
-    need(ws.dexptr, (size_t)(nq + 1) * 8);
-    need(ws.dexcl, excl_idx.size() * 4);
-    need(ws.dtop, (size_t)nq * topn * 4);
-    need(ws.dscore, (size_t)nq * topn * 8);
-    need(ws.dcount, (size_t)nq * 4);
-    need(ws.h_top, (size_t)nq * topn * 4, true);
-    need(ws.h_score, (size_t)nq * topn * 8, true);
-    need(ws.h_count, (size_t)nq * 4, true);
-    hipEvent_t *evs[] = {&ws.ev0, &ws.ev1};
-    for (hipEvent_t *ev : evs)
-        if (e == hipSuccess && !*ev) e = hipEventCreate(ev);
-    if (e != hipSuccess) return e;
-    T *dA = (T *)ws.dA.p, *dB = (T *)ws.dB.p, *dS = (T *)ws.dS.p, *drc = (T *)ws.drc.p;
-    int32_t *dcand = (int32_t *)ws.dcand.p, *dqu = (int32_t *)ws.dqu.p, *dqc = (int32_t *)ws.dqc.p, *dexcl = (int32_t *)ws.dexcl.p;
-    int32_t *dtop = (int32_t *)ws.dtop.p, *dcount = (int32_t *)ws.dcount.p;
-    int64_t *dexptr = (int64_t *)ws.dexptr.p;
-    double *dscore = (double *)ws.dscore.p;
-    auto up = [&](void *d, const void *s, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream);
-    };
-    up(dcand, cand.data(), (size_t)nc * 4);
-    up(dqu, qu.data(), (size_t)nq * 4);
-    up(dqc, qc.data(), (size_t)nq * 4);
-    up(dexptr, excl_ptr.data(), (size_t)(nq + 1) * 8);
-    up(dexcl, excl_idx.data(), excl_idx.size() * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(dtop, 0xff, (size_t)nq * topn * 4, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dscore, 0, (size_t)nq * topn * 8, stream);
-    if (e == hipSuccess) e = ops.build_items(dB, dcand, nc, kp, stream);
-    if (e == hipSuccess) e = hipEventRecord(ws.ev0, stream);
-    ws.host_ms[1] = ms_since(t_setup);
-    const auto t_loop = std::chrono::steady_clock::now();
-    // Every batch is enqueued before the host waits for anything (the stream orders a batch's contraction behind the previous
-    // batch's selection, which reads the same slab); the host then turns the lists into measures batch by batch as their copies land,
-    // behind the device, and can never hold the device up.
-    std::vector<std::pair<int64_t, int64_t>> batches;
-    const std::vector<int64_t> cuts = batch_cuts(nq, bq);
-    for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
-        const int64_t q0 = cuts[b];
-        const int n = (int)(cuts[b + 1] - q0);
-        e = ops.build_queries(dA, drc, dqu + q0, dqc + q0, n, kp, stream);
-        if (e == hipSuccess) e = rank_launch_score<T>(dA, dB, drc, dS, n, nc, kp, dexptr, dexcl, (int)q0, thold, topn, dtop, dscore, dcount, stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((int32_t *)ws.h_top.p + (size_t)q0 * topn, dtop + (size_t)q0 * topn, (size_t)n * topn * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((double *)ws.h_score.p + (size_t)q0 * topn, dscore + (size_t)q0 * topn, (size_t)n * topn * 8, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((int32_t *)ws.h_count.p + q0, dcount + q0, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = ws.batch_event(batches.size(), stream);
-        batches.emplace_back(q0, q0 + n);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ws.ev1, stream);
-    e = ws.consume_batches(e, batches, on_batch, t_loop);
-    if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, ws.ev0, ws.ev1);
+    const int64_t bq = rank_batch_size(nq, nc, sizeof(T));
     if (flops) *flops = 2.0 * (double)nq * (double)nc * (double)kp;
-    return e;
+    f.units = nq, f.batch = bq;
+    f.buffers = {{W::DB, up128(nc) * kp * sizeof(T)}, {W::DA, up128(bq) * kp * sizeof(T)}, {W::DS, (size_t)bq * (size_t)nc * sizeof(T)}, {W::DRC, (size_t)bq * sizeof(T)}};
+    f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DQU, plan.qu), plan_array(W::DQC, plan.qc), plan_array(W::DEXPTR, plan.excl_ptr),
+                     plan_array(W::DEXCL, plan.excl_idx)};
+    // This form uploads the plan's arrays on every evaluation, as it always did.  With the uploads skipped, one evaluation of every process
+    // (the 7th of the rank benchmark's sequence) lost 6-9 ms to a host stall in the first copy of lists back to the host, on this one
+    // stream with no host-to-device copy in front of it; the split form, whose lists come back on its selection stream, has never shown
+    // it (profiles/rank_driver_refactor_speed.json).  The tags are still set, so the split form finds resident what this form uploaded.
+    f.upload_always = true;
+    f.prepare = [&] { return ops.build_items(ws.d<T>(W::DB), ws.d<int32_t>(W::DCAND), nc, kp, stream); };
+    f.enqueue = [&](size_t, int64_t q0, int64_t q1, RankBatch &r) {
+        const int n = (int)(q1 - q0);
+        r.q0 = q0, r.q1 = q1;
+        hipError_t e = ops.build_queries(ws.d<T>(W::DA), ws.d<T>(W::DRC), ws.d<int32_t>(W::DQU) + q0, ws.d<int32_t>(W::DQC) + q0, n, kp, stream);
+        if (e == hipSuccess)
+            e = rank_launch_score<T>(ws.d<T>(W::DA), ws.d<T>(W::DB), ws.d<T>(W::DRC), ws.d<T>(W::DS), n, nc, kp, ws.d<int64_t>(W::DEXPTR), ws.d<int32_t>(W::DEXCL),
+                                     (int)q0, thold, topn, ws.d<int32_t>(W::DTOP), ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), stream);
+        return e;
+    };
+    return rank_run_batches(stream, ws, plan, topn, f, on_batch, ms);
 }
 
 // ---- the split form (MF family, fp32 state): see rank_kernels.hip "the split form" ---------------------------------------------------------
@@ -816,11 +866,12 @@ bool rank_split_usable(const RankPlan &plan, int topn, RankWorkspace &ws) {
 }
 
 hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, RankSplitArgs a, double thold, int topn,
-                                 const std::function<void(int64_t, int64_t)> &on_batch, float *ms, double *flops) {
-    const auto t_setup = std::chrono::steady_clock::now();
+                                 const RankBatchFn &on_batch, float *ms, double *flops) {
+    RankForm f;
+    f.t_setup = std::chrono::steady_clock::now();
     const bool times = getenv("CMI_PLAN_TIMES") != nullptr;
-    auto tl = t_setup;
-    auto lap = [&](const char *w) {
+    auto tl = f.t_setup;
+    f.lap = [&](const char *w) {
         if (!times) return;
         const auto n = std::chrono::steady_clock::now();
         fprintf(stderr, "rank setup %s %.3f ms\n", w, std::chrono::duration<double, std::milli>(n - tl).count());
@@ -828,11 +879,9 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     };
     const int nc = (int)plan.cand.size();
     const int64_t nq = (int64_t)plan.qu.size();
-    // query groups = runs of one user (the plan orders the queries by user, then context)
-    // (built by the plan's last phase, in ranges)
-    const std::vector<int32_t> &gu = plan.gu, &qg = plan.qg, &gq0 = plan.gq0; // group -> user; query -> group; group -> first query
-    const int64_t ng = (int64_t)gu.size();
-    lap("groups");
+    // query groups = runs of one user (the plan orders the queries by user, then context): gu, qg, gq0 of the plan
+    const int64_t ng = (int64_t)plan.gu.size();
+    f.lap("groups");
     std::vector<int32_t> &dctx = ws.v_dctx, &qd = ws.v_qd;
     const bool ic = a.icBias != nullptr;
     const bool s2 = ic; // the context part as a slab of its own (distinct contexts x candidates)
@@ -843,7 +892,7 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     }
     ws.ctx_ready = false;
     const int n_dc = (int)dctx.size();
-    lap("contexts");
+    f.lap("contexts");
     a.kp1 = (a.k + 15) / 16 * 16; // (the item bias is not a column: the contraction's epilogue adds it -- k = 128 costs 8 steps of 16, not 9)
     a.kp2 = ic ? (a.n_conds + 15) / 16 * 16 : 16;
     a.nc = nc;
@@ -851,16 +900,9 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     a.n_dctx = n_dc;
     auto up128 = [](int64_t v) { return (size_t)((v + 127) / 128 * 128); };
     // user groups per batch: an S1 slab of about 1 GiB (256-MiB batches were measured slower: 15.3 against 10.7 ms for the loop)
-    int64_t bg = std::max<int64_t>(64, ((int64_t)1 << 30) / ((int64_t)nc * 4));
-    bg = std::min<int64_t>(bg, ng);
-    if (const char *e = getenv("CMI_RANK_BATCH")) bg = std::max<int64_t>(1, std::min<int64_t>(atoll(e), ng)); // tests: batching is invisible
-
-    hipError_t e = hipSuccess;
-    auto need = [&](RankWorkspace::Buf &b, size_t bytes, bool pinned = false) {
-        if (e == hipSuccess) e = ws.need(b, bytes, pinned);
-    };
-    need(ws.dB, up128(nc) * a.kp1 * 4);
-    need(ws.dcolc, up128(nc) * 4);
+    const int64_t bg = rank_batch_size(ng, nc, 4);
+    // flops of THIS form: the two contractions it actually runs
+    if (flops) *flops = 2.0 * (double)ng * (double)nc * (double)a.kp1 + (s2 ? 2.0 * (double)n_dc * (double)nc * (double)a.kp2 : 0.0);
     // two streams: the selection of batch b runs beside the contraction of batch b + 1 (matrix pipe beside the L2 / memory pipes), each
     // batch on the slab / operand buffer of its parity.  CMI_RANK_ONE_STREAM=1: the round-4 form, one stream, one slab (A/B)
     const bool one_stream = getenv("CMI_RANK_ONE_STREAM") != nullptr; // (read per call: bench.py times the two kernels on their own with it)
@@ -869,220 +911,104 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     // CMI_RANK_NO_PRUNE=1: the plain selection (tests compare the two forms entry for entry)
     const bool prune = getenv("CMI_RANK_NO_PRUNE") == nullptr;
     const size_t nt64 = (size_t)(nc + 63) / 64;
-    need(ws.dA, up128(bg) * a.kp1 * 4);
-    need(ws.dS, (size_t)bg * (size_t)nc * 4 + RANK_SLAB_SLACK);
-    if (prune) need(ws.dM1, (size_t)bg * nt64 * 4);
-    if (two) {
-        need(ws.dAb, up128(bg) * a.kp1 * 4);
-        need(ws.dSb, (size_t)bg * (size_t)nc * 4 + RANK_SLAB_SLACK);
-        if (prune) need(ws.dM1b, (size_t)bg * nt64 * 4);
-        if (e == hipSuccess && !ws.sel_stream) e = hipStreamCreateWithFlags(&ws.sel_stream, hipStreamNonBlocking);
-    }
-    need(ws.dscr, std::max<size_t>(up128(bg), up128(n_dc)) * 4);
-    need(ws.drc, (size_t)nq * 4);
-    if (s2) {
-        need(ws.dB2, up128(nc) * a.kp2 * 4);
-        need(ws.dA2, up128(n_dc) * a.kp2 * 4);
-        need(ws.dS2, (size_t)n_dc * (size_t)nc * 4 + RANK_SLAB_SLACK);
-        if (prune) need(ws.dM2, (size_t)n_dc * nt64 * 4);
-        need(ws.ddc, (size_t)n_dc * 4);
-        need(ws.dqd, (size_t)nq * 4);
-    }
-    need(ws.dcand, (size_t)nc * 4);
-    need(ws.dqu, (size_t)nq * 4);
-    need(ws.dqc, (size_t)nq * 4);
-    need(ws.dqg, (size_t)nq * 4);
-    need(ws.dgu, (size_t)ng * 4);
-    need(ws.dexptr, (size_t)(nq + 1) * 8);
-    need(ws.dexcl, plan.excl_idx.size() * 4);
-    need(ws.dtop, (size_t)nq * topn * 4);
-    need(ws.dscore, (size_t)nq * topn * 8);
-    need(ws.dcount, (size_t)nq * 4);
-    need(ws.h_top, (size_t)nq * topn * 4, true);
-    need(ws.h_score, (size_t)nq * topn * 8, true);
-    need(ws.h_count, (size_t)nq * 4, true);
-    hipEvent_t *evs[] = {&ws.ev0, &ws.ev1};
-    for (hipEvent_t *ev : evs)
-        if (e == hipSuccess && !*ev) e = hipEventCreate(ev);
-    if (e != hipSuccess) return e;
-    lap("buffers");
-    auto up = [&](void *d, const void *s, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream);
+    const size_t scr_bytes = std::max<size_t>(up128(bg), up128(n_dc)) * 4, a_bytes = up128(bg) * a.kp1 * 4;
+    const size_t s_bytes = (size_t)bg * (size_t)nc * 4 + RANK_SLAB_SLACK, m_bytes = (size_t)bg * nt64 * 4;
+    f.units = ng, f.batch = bg;
+    f.buffers.reserve(16);
+    f.buffers = {{W::DB, up128(nc) * a.kp1 * 4}, {W::DCOLC, up128(nc) * 4}, {W::DA, a_bytes}, {W::DS, s_bytes}, {W::DSCR, scr_bytes}, {W::DRC, (size_t)nq * 4}};
+    if (prune) f.buffers.push_back({W::DM1, m_bytes});
+    if (two) f.buffers.insert(f.buffers.end(), {{W::DAB, a_bytes}, {W::DSB, s_bytes}});
+    if (two && prune) f.buffers.push_back({W::DM1B, m_bytes});
+    if (s2) f.buffers.insert(f.buffers.end(), {{W::DB2, up128(nc) * a.kp2 * 4}, {W::DA2, up128(n_dc) * a.kp2 * 4}, {W::DS2, (size_t)n_dc * (size_t)nc * 4 + RANK_SLAB_SLACK}});
+    if (s2 && prune) f.buffers.push_back({W::DM2, (size_t)n_dc * nt64 * 4});
+    f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DQU, plan.qu), plan_array(W::DQC, plan.qc), plan_array(W::DQG, plan.qg),
+                     plan_array(W::DGU, plan.gu), plan_array(W::DEXPTR, plan.excl_ptr), plan_array(W::DEXCL, plan.excl_idx)};
+    if (s2) f.plan_arrays.insert(f.plan_arrays.end(), {plan_array(W::DDC, dctx), plan_array(W::DQD, qd)}); // (derived from the plan's qc)
+    f.prepare = [&] {
+        hipError_t e = two && !ws.sel_stream ? hipStreamCreateWithFlags(&ws.sel_stream, hipStreamNonBlocking) : hipSuccess;
+        if (e == hipSuccess) e = hipMemsetAsync(ws.d<void>(W::DSCR), 0, scr_bytes, stream);
+        a.cand = ws.d<int32_t>(W::DCAND);
+        a.qu = ws.d<int32_t>(W::DQU);
+        a.qc = ws.d<int32_t>(W::DQC);
+        a.dctx = ws.d<int32_t>(W::DDC);
+        a.B1 = ws.d<float>(W::DB);
+        a.colc = ws.d<float>(W::DCOLC);
+        a.B2 = ws.d<float>(W::DB2);
+        a.A2 = ws.d<float>(W::DA2);
+        a.rc = ws.d<float>(W::DRC);
+        if (e == hipSuccess) e = rank_launch_split_operands(a, stream);
+        return e;
     };
-    // the plan's index arrays: already on the device when this is the plan of the previous evaluation (ws.plan_valid: same tuples, by
-    // content hash) and none of their buffers was re-allocated since
-    const void *now[9] = {ws.dcand.p, ws.dqu.p, ws.dqc.p, ws.dqg.p, ws.dgu.p, ws.dexptr.p, ws.dexcl.p, s2 ? ws.ddc.p : nullptr, s2 ? ws.dqd.p : nullptr};
-    bool resident = ws.plan_valid && ws.resident[0] != nullptr;
-    for (int i = 0; i < 9 && resident; ++i) resident = ws.resident[i] == now[i];
-    if (!resident) {
-        up(ws.dcand.p, plan.cand.data(), (size_t)nc * 4);
-        up(ws.dqu.p, plan.qu.data(), (size_t)nq * 4);
-        up(ws.dqc.p, plan.qc.data(), (size_t)nq * 4);
-        up(ws.dqg.p, qg.data(), (size_t)nq * 4);
-        up(ws.dgu.p, gu.data(), (size_t)ng * 4);
-        up(ws.dexptr.p, plan.excl_ptr.data(), (size_t)(nq + 1) * 8);
-        up(ws.dexcl.p, plan.excl_idx.data(), plan.excl_idx.size() * 4);
-        if (s2) {
-            up(ws.ddc.p, dctx.data(), (size_t)n_dc * 4);
-            up(ws.dqd.p, qd.data(), (size_t)nq * 4);
-        }
-        for (int i = 0; i < 9; ++i) ws.resident[i] = now[i];
-    }
-    lap("uploads");
-    int32_t *dtop = (int32_t *)ws.dtop.p, *dcount = (int32_t *)ws.dcount.p;
-    double *dscore = (double *)ws.dscore.p;
-    if (e == hipSuccess) e = hipMemsetAsync(dtop, 0xff, (size_t)nq * topn * 4, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dscore, 0, (size_t)nq * topn * 8, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(ws.dscr.p, 0, std::max<size_t>(up128(bg), up128(n_dc)) * 4, stream);
-    a.cand = (const int32_t *)ws.dcand.p;
-    a.qu = (const int32_t *)ws.dqu.p;
-    a.qc = (const int32_t *)ws.dqc.p;
-    a.dctx = (const int32_t *)ws.ddc.p;
-    a.B1 = (float *)ws.dB.p;
-    a.colc = (float *)ws.dcolc.p;
-    a.B2 = (float *)ws.dB2.p;
-    a.A2 = (float *)ws.dA2.p;
-    a.rc = (float *)ws.drc.p;
-    if (e == hipSuccess) e = rank_launch_split_operands(a, stream);
-    if (e == hipSuccess) e = hipEventRecord(ws.ev0, stream);
     // S2: once per evaluation (row constant = the zeroed scratch)
-    if (e == hipSuccess && s2)
-        e = rank_launch_gemm<float>(a.A2, a.B2, (const float *)ws.dscr.p, (float *)ws.dS2.p, n_dc, nc, a.kp2, stream, nullptr, prune ? (float *)ws.dM2.p : nullptr);
-    lap("memsets + operand launches");
-    ws.host_ms[1] = ms_since(t_setup);
-    const auto t_loop = std::chrono::steady_clock::now();
-    std::vector<std::pair<int64_t, int64_t>> batches; // all enqueued first, consumed behind the device (see rank_run_device)
-    const std::vector<int64_t> cuts = batch_cuts(ng, bg);
-    auto ev_at = [&](std::vector<hipEvent_t> &v, size_t i) -> hipEvent_t {
-        while (v.size() <= i && e == hipSuccess) {
-            hipEvent_t ev = nullptr;
-            e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e == hipSuccess) v.push_back(ev);
-        }
-        return i < v.size() ? v[i] : nullptr;
-    };
-    hipStream_t sel = two ? ws.sel_stream : stream;
+    if (s2)
+        f.start = [&] {
+            return rank_launch_gemm<float>(a.A2, a.B2, ws.d<float>(W::DSCR), ws.d<float>(W::DS2), n_dc, nc, a.kp2, stream, nullptr, prune ? ws.d<float>(W::DM2) : nullptr);
+        };
     // (the contraction of batch b + 1 made to wait for the selection of batch b -- the kernels never side by side, only the lists' copies
     // overlapped -- measured the same 6.3 ms as the overlapped form: docs/history/r06.md 3)
-    for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
-        const int64_t g0 = cuts[b];
-        const int n = (int)(cuts[b + 1] - g0);
-        const int64_t q0 = gq0[(size_t)g0], q1 = gq0[(size_t)(g0 + n)];
-        float *dAx = (float *)((two && (b & 1)) ? ws.dAb.p : ws.dA.p), *dSx = (float *)((two && (b & 1)) ? ws.dSb.p : ws.dS.p);
-        float *dMx = prune ? (float *)((two && (b & 1)) ? ws.dM1b.p : ws.dM1.p) : nullptr;
+    f.enqueue = [&](size_t b, int64_t g0, int64_t g1, RankBatch &r) {
+        const int n = (int)(g1 - g0);
+        const int64_t q0 = plan.gq0[(size_t)g0], q1 = plan.gq0[(size_t)g1];
+        const bool odd = two && (b & 1);
+        const hipStream_t sel = two ? ws.sel_stream : stream;
+        float *dAx = ws.d<float>(odd ? W::DAB : W::DA), *dSx = ws.d<float>(odd ? W::DSB : W::DS), *dscr = ws.d<float>(W::DSCR);
+        float *dMx = prune ? ws.d<float>(odd ? W::DM1B : W::DM1) : nullptr;
+        r = RankBatch{q0, q1, sel};
+        hipError_t e = hipSuccess;
         // the slab of this parity is free once the selection of batch b - 2 has read it
-        if (two && b >= 2 && e == hipSuccess) e = hipStreamWaitEvent(stream, ev_at(ws.evsel, b - 2), 0);
+        if (two && b >= 2) e = hipStreamWaitEvent(stream, ws.evsel.at(b - 2), 0);
         // (the builder leaves its per-row constant -- zero here -- in the scratch the contraction then reads as its row constant)
-        if (e == hipSuccess) e = rank_launch_split_users(a, (const int32_t *)ws.dgu.p + g0, n, dAx, (float *)ws.dscr.p, stream);
-        if (e == hipSuccess) e = ws.kernel_event(4 * b, stream);
-        if (e == hipSuccess) e = rank_launch_gemm<float>(dAx, a.B1, (const float *)ws.dscr.p, dSx, n, nc, a.kp1, stream, a.colc, dMx);
-        if (e == hipSuccess) e = ws.kernel_event(4 * b + 1, stream);
-        if (two && e == hipSuccess) {
-            hipEvent_t g = ev_at(ws.evgemm, b);
-            if (e == hipSuccess) e = hipEventRecord(g, stream);
-            if (e == hipSuccess) e = hipStreamWaitEvent(sel, g, 0);
+        if (e == hipSuccess) e = rank_launch_split_users(a, ws.d<int32_t>(W::DGU) + g0, n, dAx, dscr, stream);
+        if (e == hipSuccess) e = ws.evk.record(4 * b, stream);
+        if (e == hipSuccess) e = rank_launch_gemm<float>(dAx, a.B1, dscr, dSx, n, nc, a.kp1, stream, a.colc, dMx);
+        if (e == hipSuccess) e = ws.evk.record(4 * b + 1, stream);
+        if (two && e == hipSuccess) e = ws.evgemm.record(b, stream);
+        if (two && e == hipSuccess) e = hipStreamWaitEvent(sel, ws.evgemm.at(b), 0);
+        if (e == hipSuccess) e = ws.evk.record(4 * b + 2, sel);
+        if (e == hipSuccess)
+            e = rank_launch_split_select(dSx, s2 ? ws.d<float>(W::DS2) : nullptr, a, ws.d<int32_t>(W::DQG), ws.d<int32_t>(W::DQD), (int)g0, (int)q0,
+                                         (int)(q1 - q0), ws.d<int64_t>(W::DEXPTR), ws.d<int32_t>(W::DEXCL), thold, topn, ws.d<int32_t>(W::DTOP),
+                                         ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), sel, dMx, prune && s2 ? ws.d<float>(W::DM2) : nullptr);
+        if (e == hipSuccess) e = ws.evk.record(4 * b + 3, sel);
+        if (two && e == hipSuccess) e = ws.evsel.record(b, sel);
+        return e;
+    };
+    f.finish = [&](size_t n_batches) { // (with two streams the two kernels' times overlap: their sum exceeds the loop)
+        hipError_t e = hipSuccess;
+        for (size_t b = 0; b < n_batches && e == hipSuccess; ++b) {
+            float g = 0.f, t = 0.f;
+            e = hipEventElapsedTime(&g, ws.evk.at(4 * b), ws.evk.at(4 * b + 1));
+            if (e == hipSuccess) e = hipEventElapsedTime(&t, ws.evk.at(4 * b + 2), ws.evk.at(4 * b + 3));
+            ws.kernel_ms[0] += g;
+            ws.kernel_ms[1] += t;
         }
-        if (e == hipSuccess) e = ws.kernel_event(4 * b + 2, sel);
-        if (e == hipSuccess)
-            e = rank_launch_split_select(dSx, s2 ? (const float *)ws.dS2.p : nullptr, a, (const int32_t *)ws.dqg.p,
-                                         (const int32_t *)ws.dqd.p, (int)g0, (int)q0, (int)(q1 - q0), (const int64_t *)ws.dexptr.p,
-                                         (const int32_t *)ws.dexcl.p, thold, topn, dtop, dscore, dcount, sel, dMx, prune && s2 ? (const float *)ws.dM2.p : nullptr);
-        if (e == hipSuccess) e = ws.kernel_event(4 * b + 3, sel);
-        if (two && e == hipSuccess) {
-            hipEvent_t sd = ev_at(ws.evsel, b);
-            if (e == hipSuccess) e = hipEventRecord(sd, sel);
-        }
-        const size_t nqb = (size_t)(q1 - q0);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((int32_t *)ws.h_top.p + (size_t)q0 * topn, dtop + (size_t)q0 * topn, nqb * topn * 4, hipMemcpyDeviceToHost, sel);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((double *)ws.h_score.p + (size_t)q0 * topn, dscore + (size_t)q0 * topn, nqb * topn * 8, hipMemcpyDeviceToHost, sel);
-        if (e == hipSuccess) e = hipMemcpyAsync((int32_t *)ws.h_count.p + q0, dcount + q0, nqb * 4, hipMemcpyDeviceToHost, sel);
-        if (e == hipSuccess) e = ws.batch_event(batches.size(), sel);
-        batches.emplace_back(q0, q1);
-    }
-    // the loop ends when the last batch's lists are on the host: ev1 on the main stream, behind the selection stream's last event
-    if (two && e == hipSuccess && !batches.empty()) e = hipStreamWaitEvent(stream, ws.evb[batches.size() - 1], 0);
-    if (e == hipSuccess) e = hipEventRecord(ws.ev1, stream);
-    e = ws.consume_batches(e, batches, on_batch, t_loop);
-    if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, ws.ev0, ws.ev1);
-    for (size_t b = 0; b < batches.size() && e == hipSuccess; ++b) { // (with two streams the two kernels' times overlap: their sum exceeds the loop)
-        float g = 0.f, t = 0.f;
-        e = hipEventElapsedTime(&g, ws.evk[4 * b], ws.evk[4 * b + 1]);
-        if (e == hipSuccess) e = hipEventElapsedTime(&t, ws.evk[4 * b + 2], ws.evk[4 * b + 3]);
-        ws.kernel_ms[0] += g;
-        ws.kernel_ms[1] += t;
-    }
-    // flops of THIS form: the two contractions it actually runs
-    if (flops) *flops = 2.0 * (double)ng * (double)nc * (double)a.kp1 + (s2 ? 2.0 * (double)n_dc * (double)nc * (double)a.kp2 : 0.0);
-    return e;
+        return e;
+    };
+    return rank_run_batches(stream, ws, plan, topn, f, on_batch, ms);
 }
 
 hipError_t rank_run_device_slab(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankSlabFn &fill, double thold, int topn,
                                 const RankBatchFn &on_batch, float *ms) {
-    const auto t_setup = std::chrono::steady_clock::now();
+    RankForm f;
+    f.t_setup = std::chrono::steady_clock::now();
     const int nc = (int)plan.cand.size();
     const int64_t nq = (int64_t)plan.qu.size();
-    const size_t ng = plan.gu.size();
-    int64_t bq = std::max<int64_t>(64, ((int64_t)1 << 30) / ((int64_t)std::max(nc, 1) * (int64_t)sizeof(double))); // the slab around 1 GiB
-    bq = std::min<int64_t>(bq, nq);
-    if (const char *e = getenv("CMI_RANK_BATCH")) bq = std::max<int64_t>(1, std::min<int64_t>(atoll(e), nq)); // tests: batching is invisible
-    hipError_t e = hipSuccess;
-    auto need = [&](RankWorkspace::Buf &b, size_t bytes, bool pinned = false) {
-        if (e == hipSuccess) e = ws.need(b, bytes, pinned);
-    };
-    need(ws.dS, (size_t)bq * (size_t)nc * sizeof(double) + RANK_SLAB_SLACK);
-    need(ws.dcand, (size_t)nc * 4);
-    need(ws.dgu, ng * 4);
-    need(ws.dgq0, (ng + 1) * 4);
-    need(ws.dexptr, (size_t)(nq + 1) * 8);
-    need(ws.dexcl, plan.excl_idx.size() * 4);
-    need(ws.dtop, (size_t)nq * topn * 4);
-    need(ws.dscore, (size_t)nq * topn * 8);
-    need(ws.dcount, (size_t)nq * 4);
-    need(ws.h_top, (size_t)nq * topn * 4, true);
-    need(ws.h_score, (size_t)nq * topn * 8, true);
-    need(ws.h_count, (size_t)nq * 4, true);
-    hipEvent_t *evs[] = {&ws.ev0, &ws.ev1};
-    for (hipEvent_t *ev : evs)
-        if (e == hipSuccess && !*ev) e = hipEventCreate(ev);
-    if (e != hipSuccess) return e;
-    double *dS = (double *)ws.dS.p, *dscore = (double *)ws.dscore.p;
-    int32_t *dcand = (int32_t *)ws.dcand.p, *dgu = (int32_t *)ws.dgu.p, *dgq0 = (int32_t *)ws.dgq0.p, *dexcl = (int32_t *)ws.dexcl.p;
-    int32_t *dtop = (int32_t *)ws.dtop.p, *dcount = (int32_t *)ws.dcount.p;
-    int64_t *dexptr = (int64_t *)ws.dexptr.p;
-    auto up = [&](void *d, const void *s, size_t bytes) {
-        if (e == hipSuccess && bytes) e = hipMemcpyAsync(d, s, bytes, hipMemcpyHostToDevice, stream);
-    };
-    up(dcand, plan.cand.data(), (size_t)nc * 4);
-    up(dgu, plan.gu.data(), ng * 4);
-    up(dgq0, plan.gq0.data(), plan.gq0.size() * 4);
-    up(dexptr, plan.excl_ptr.data(), (size_t)(nq + 1) * 8);
-    up(dexcl, plan.excl_idx.data(), plan.excl_idx.size() * 4);
-    if (e == hipSuccess) e = hipMemsetAsync(dtop, 0xff, (size_t)nq * topn * 4, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(dscore, 0, (size_t)nq * topn * 8, stream);
-    if (e == hipSuccess) e = hipEventRecord(ws.ev0, stream);
-    ws.host_ms[1] = ms_since(t_setup);
-    const auto t_loop = std::chrono::steady_clock::now();
-    std::vector<std::pair<int64_t, int64_t>> batches; // all enqueued first, consumed behind the device (see rank_run_device)
-    const std::vector<int64_t> cuts = batch_cuts(nq, bq);
-    for (size_t b = 0; b + 1 < cuts.size() && e == hipSuccess; ++b) {
-        const int64_t q0 = cuts[b];
-        const int n = (int)(cuts[b + 1] - q0);
-        e = fill(dS, dcand, nc, dgu, dgq0, plan.qg[(size_t)q0], plan.qg[(size_t)(q0 + n - 1)] + 1, q0, n, stream);
-        if (e == hipSuccess) e = rank_launch_select<double>(dS, n, nc, dexptr, dexcl, (int)q0, thold, topn, dtop, dscore, dcount, stream);
+    f.units = nq, f.batch = rank_batch_size(nq, nc, sizeof(double));
+    f.buffers = {{W::DS, (size_t)f.batch * (size_t)nc * sizeof(double) + RANK_SLAB_SLACK}};
+    f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DGU, plan.gu), plan_array(W::DGQ0, plan.gq0), plan_array(W::DEXPTR, plan.excl_ptr),
+                     plan_array(W::DEXCL, plan.excl_idx)};
+    f.enqueue = [&](size_t, int64_t q0, int64_t q1, RankBatch &r) {
+        const int n = (int)(q1 - q0);
+        r.q0 = q0, r.q1 = q1;
+        // the batch's groups: those of its first and of its last query
+        hipError_t e = fill(ws.d<double>(W::DS), ws.d<int32_t>(W::DCAND), nc, ws.d<int32_t>(W::DGU), ws.d<int32_t>(W::DGQ0), plan.qg[(size_t)q0],
+                            plan.qg[(size_t)(q1 - 1)] + 1, q0, n, stream);
         if (e == hipSuccess)
-            e = hipMemcpyAsync((int32_t *)ws.h_top.p + (size_t)q0 * topn, dtop + (size_t)q0 * topn, (size_t)n * topn * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync((double *)ws.h_score.p + (size_t)q0 * topn, dscore + (size_t)q0 * topn, (size_t)n * topn * 8, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync((int32_t *)ws.h_count.p + q0, dcount + q0, (size_t)n * 4, hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = ws.batch_event(batches.size(), stream);
-        batches.emplace_back(q0, q0 + n);
-    }
-    if (e == hipSuccess) e = hipEventRecord(ws.ev1, stream);
-    e = ws.consume_batches(e, batches, on_batch, t_loop);
-    if (e == hipSuccess && ms) e = hipEventElapsedTime(ms, ws.ev0, ws.ev1);
-    return e;
+            e = rank_launch_select<double>(ws.d<double>(W::DS), n, nc, ws.d<int64_t>(W::DEXPTR), ws.d<int32_t>(W::DEXCL), (int)q0, thold, topn,
+                                           ws.d<int32_t>(W::DTOP), ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), stream);
+        return e;
+    };
+    return rank_run_batches(stream, ws, plan, topn, f, on_batch, ms);
 }
 
 template hipError_t rank_run_device<float>(hipStream_t, RankWorkspace &, const RankPlan &, const RankOperands<float> &, double, int,
@@ -1314,9 +1240,9 @@ int cmi::rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, in
     }
     if (!(ws.plan_valid && ws.plan_key == key)) {
         ws.plan_valid = false;
+        ++ws.plan_gen; // (no buffer holds an array of the new plan)
         rank_build_plan(n_users, n_items, train, test, io.bin_thold, io.num_ignore, plan);
         ws.plan_key = key;
-        for (const void *&r : ws.resident) r = nullptr;
         ws.plan_valid = true;
     }
     ws.host_ms[0] = ms_since(t_all);
@@ -1340,15 +1266,19 @@ int cmi::rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, in
                     if (on) fprintf(stderr, "rank batch of %lld queries: measures + user means %.3f ms on the host\n", (long long)n, ms_since(t0));
                 }
             } lap{times, tb, q1 - q0};
-            rank_measures_range(plan, io.num_recs, (const int32_t *)ws.h_top.p, (const double *)ws.h_score.p, (const int32_t *)ws.h_count.p, q0,
-                                q1, vals, io.q_user, io.q_ctx, io.q_count, io.top_items, io.top_scores);
+            const int32_t *h_count = ws.h<int32_t>(RankWorkspace::H_COUNT);
+            rank_measures_range(plan, io.num_recs, ws.h<int32_t>(RankWorkspace::H_TOP), ws.h<double>(RankWorkspace::H_SCORE), h_count, q0, q1, vals,
+                                io.q_user, io.q_ctx, io.q_count, io.top_items, io.top_scores);
             // the batches arrive in query order: the users they complete are averaged here, behind the device
-            if (io.strategy == CMI_RANK_UCU) rank_fold_users(plan, (const int32_t *)ws.h_count.p, vals, umeans, folded, q1, q1 >= nq);
-            else rank_sum_queries((const int32_t *)ws.h_count.p, vals, folded, q1); // uc: the serial sum over the queries, behind the device
+            if (io.strategy == CMI_RANK_UCU) rank_fold_users(plan, h_count, vals, umeans, folded, q1, q1 >= nq);
+            else rank_sum_queries(h_count, vals, folded, q1); // uc: the serial sum over the queries, behind the device
         };
         const hipError_t e = score(plan, on_batch);
-        if (e != hipSuccess) return abi_fail(err, CMI_E_HIP, "e failed: %s", hipGetErrorString(e));
-        top_count = (const int32_t *)ws.h_count.p;
+        if (e != hipSuccess) {
+            ws.forget_uploads();
+            return abi_fail(err, CMI_E_HIP, "%s: device scoring failed: %s", what, hipGetErrorString(e));
+        }
+        top_count = ws.h<int32_t>(RankWorkspace::H_COUNT);
     } else {
         no_lists.assign((size_t)nq, 0);
         top_count = no_lists.data();

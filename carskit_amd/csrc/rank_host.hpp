@@ -1,6 +1,9 @@
 // rank_host.hpp -- model-agnostic core of the ranking evaluation (Recommender.evalRankings,
-// src/carskit/generic/Recommender.java:668-964), shared by cmi_eval_rankings (MF family) and cmi_fm_eval_rankings (FM):
-// host bookkeeping (candidates, queries, exclusions), the device scoring driver, the metric formulas.  Internal.
+// src/carskit/generic/Recommender.java:668-964): host bookkeeping (candidates, queries, exclusions), the device scoring driver, the
+// metric formulas.  Shared by cmi_eval_rankings (the MF family: BiasedMF, PMF, CAMF_*, SVD++, CAMF_ICS / LCS / MCS),
+// cmi_fm_eval_rankings (FM) and cmi_slim_eval_rankings (SLIM).  A new model calls rank_evaluate with a `score` that runs one of the
+// three forms of the device loop: rank_run_device with its operand builders when its score is a contraction, rank_run_device_slab
+// with a fill when it is not.  Internal.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,25 +45,59 @@ struct RankOperands {
     std::function<hipError_t(T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t)> build_queries;
 };
 
+// A growable store of HIP events, made on first use and kept for the next evaluation.
+struct RankEvents {
+    explicit RankEvents(bool timing) : flags(timing ? hipEventDefault : hipEventDisableTiming) {}
+    hipError_t grow(size_t n);                          // events 0 .. n - 1 exist
+    hipEvent_t at(size_t i) const { return v[i]; }      // an event that grow / record has made
+    hipError_t record(size_t i, hipStream_t stream);    // (grows to i + 1)
+    void destroy();
+
+  private:
+    unsigned flags;
+    std::vector<hipEvent_t> v;
+};
+
 // Device and pinned-host buffers of an evaluation, owned by the handle and reused (grow-only) by the next one: allocating and
 // freeing ~1 GiB per call costs milliseconds and a device synchronisation each.
 struct RankWorkspace {
     struct Buf {
         void *p = nullptr;
         size_t cap = 0;
+        uint64_t plan_gen = 0; // the plan (RankWorkspace::plan_gen) whose array this buffer holds; 0: none
     };
-    Buf dA, dB, dS, drc, dcand, dqu, dqc, dexptr, dexcl, dtop, dscore, dcount; // device
-    Buf dB2, dA2, dS2, dqg, dqd, dgu, ddc, dscr;                                // device, split form (rank_run_device_split)
-    Buf dcolc;                                                                  // split form: itemBias of the candidates (the S1 contraction adds it at the end)
-    Buf dgq0;                                                                   // slab form (rank_run_device_slab): group -> first query (+ end); it shares dgu with the split form
-    Buf dSb, dAb;                                                               // split form: the second slab / operand buffer (batch b + 1 is contracted while batch b is selected)
-    Buf dM1, dM1b, dM2;                                                         // split form: per-row maxima of S1 (per slab) / S2 over tiles of 64 candidates (the selection's tile pruning)
-    hipStream_t sel_stream = nullptr;                                           // split form: the selection's stream
-    std::vector<hipEvent_t> evgemm, evsel;                                           // per batch: contraction done (main stream), selection done (selection stream)
-    Buf h_top, h_score, h_count;                                                // pinned host: the lists as they come back
-    RankPlan plan;                                                              // the last evaluation's plan (capacity is reused)
-    std::vector<int32_t> v_dctx, v_qd;                                          // split form: context index arrays (capacity is reused)
-    bool ctx_ready = false;                                                     // v_dctx / v_qd hold this evaluation's contexts (rank_split_usable)
+    // Every buffer is an entry of `dev` / `pin`: release() frees the arrays, so a buffer declared here cannot leak.
+    enum Dev {
+        DA, DB, DS, DRC,                       // operand rows of a batch of queries / of the candidates, the score slab, the per-row constants
+        DCAND, DQU, DQC, DEXPTR, DEXCL,        // the plan's cand, qu, qc, excl_ptr, excl_idx
+        DTOP, DSCORE, DCOUNT,                  // the lists
+        DQG, DGU,                              // the plan's qg, gu (split form; the slab form shares DGU)
+        DGQ0,                                  // the plan's gq0 (slab form)
+        DDC, DQD,                              // split form: the distinct contexts and every query's index into them (v_dctx, v_qd)
+        DB2, DA2, DS2, DSCR,                   // split form: the S2 contraction's operands and slab; a zeroed per-row constant
+        DCOLC,                                 // split form: itemBias of the candidates (the S1 contraction adds it at the end)
+        DSB, DAB,                              // split form: the second slab / operand buffer (batch b + 1 is contracted while batch b is selected)
+        DM1, DM1B, DM2,                        // split form: per-row maxima of S1 (per slab) / S2 over tiles of 64 candidates (the selection's tile pruning)
+        N_DEV
+    };
+    enum Pin { H_TOP, H_SCORE, H_COUNT, N_PIN }; // pinned host: the lists as they come back
+    Buf dev[N_DEV], pin[N_PIN];
+    template <typename T>
+    T *d(Dev b) const { return (T *)dev[b].p; }
+    template <typename T>
+    T *h(Pin b) const { return (T *)pin[b].p; }
+    hipError_t need(Dev b, size_t bytes); // (a re-allocation forgets the plan array the buffer held)
+    hipError_t need(Pin b, size_t bytes);
+    void release(); // the caller has made the owning device current
+
+    hipStream_t sel_stream = nullptr;                   // split form: the selection's stream
+    RankEvents ev01{true};                              // [0], [1]: around the device loop (timing)
+    RankEvents evb{false};                              // one per batch: its lists have arrived on the host
+    RankEvents evgemm{false}, evsel{false};             // split form, per batch: contraction done (main stream), selection done (selection stream)
+    RankEvents evk{true};                               // split form, four per batch: around the contraction, around the selection
+    RankPlan plan;                                      // the last evaluation's plan (capacity is reused)
+    std::vector<int32_t> v_dctx, v_qd;                  // split form: context index arrays (capacity is reused)
+    bool ctx_ready = false;                             // v_dctx / v_qd hold this evaluation's contexts (rank_split_usable)
     // Repeated evaluations of the same (train, test) tuples (`--early-stop` on a ranking measure evaluates after every epoch,
     // IterativeRecommender.java:149-161): the plan depends on the tuples alone, so it is kept, keyed by their sizes and a 64-bit
     // content hash, and so are the index arrays it put on the device.
@@ -74,8 +111,15 @@ struct RankWorkspace {
                    num_ignore == o.num_ignore && hash == o.hash;
         }
     } plan_key;
-    bool plan_valid = false;      // `plan` belongs to plan_key
-    const void *resident[9] = {}; // split form: the device buffers that hold plan_key's index arrays (null: not uploaded)
+    bool plan_valid = false; // `plan` belongs to plan_key
+    // Residency is kept per buffer: rank_evaluate counts the plans it builds (plan_gen), a buffer remembers the plan whose array was
+    // copied into it (Buf::plan_gen), and upload_plan copies only when the two differ.  A buffer holds one array of the plan whichever
+    // form fills it, so one handle may alternate forms on the same plan (a topN above 64, or CMI_RANK_NO_SPLIT, takes the per-query
+    // form): each form finds resident exactly the arrays that some earlier evaluation of this plan uploaded and uploads the rest.
+    // `always`: copy, then tag, whatever the tag says (the per-query form: see rank_run_device).
+    uint64_t plan_gen = 0;
+    hipError_t upload_plan(Dev b, const void *host, size_t bytes, hipStream_t stream, bool always = false);
+    void forget_uploads(); // after a HIP error: nothing is taken to be on the device
     struct HostVals { // per-query measures, uninitialised and grow-only (38 MB for 270 K queries: not re-faulted per call)
         std::unique_ptr<double[]> p;
         size_t cap = 0;
@@ -87,34 +131,39 @@ struct RankWorkspace {
             return p.get();
         }
     } vals, umeans; // umeans: per-user means of the ucu strategy (rank_fold_users)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr; // around the device loop (timing)
-    std::vector<hipEvent_t> evb;              // one per batch: its lists have arrived on the host
-    std::vector<hipEvent_t> evk;              // three per batch of the split form: before / after the contraction, after the selection
-    double kernel_ms[2] = {0, 0};             // last evaluation: contraction, selection (summed over the batches)
-    hipError_t kernel_event(size_t i, hipStream_t stream);
+    double kernel_ms[2] = {0, 0}; // last evaluation: contraction, selection (summed over the batches)
     // host wall clock of the last evaluation, ms: [0] plan, [1] setup (buffers, uploads, item operands), [2] scoring loop incl. the
     // overlapped per-batch measures, [3] tail (last batch's measures + the averages), [4] total
     double host_ms[5] = {0, 0, 0, 0, 0};
-    hipError_t need(Buf &b, size_t bytes, bool pinned = false);
-    void release(); // the caller has made the owning device current
-    hipError_t batch_event(size_t b, hipStream_t stream);
     // waits for the batches in order and hands each to on_batch while the device works on the later ones; fills host_ms[2], [3]
     hipError_t consume_batches(hipError_t e, const std::vector<std::pair<int64_t, int64_t>> &batches,
                                const std::function<void(int64_t, int64_t)> &on_batch, std::chrono::steady_clock::time_point t_loop);
 };
 
-// on_batch(q0, q1): the lists of queries [q0, q1) have arrived in ws.h_top / h_score / h_count (absolute query indexing); called on
-// the host while the device scores the next batch
+// The three forms of the device loop.  All run on one skeleton (rank_run_batches in rank_api.cpp: batch size, list buffers, uploads of
+// the plan's arrays, the lists' way back, timing) and supply only their scoring.
+// on_batch(q0, q1): the lists of queries [q0, q1) have arrived in the pinned H_TOP / H_SCORE / H_COUNT (absolute query indexing);
+// called on the host while the device scores the next batch
+using RankBatchFn = std::function<void(int64_t, int64_t)>;
+
+// The per-query form: one contraction row per query, from the model's operand builders.
 template <typename T>
 hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankOperands<T> &ops, double thold, int topn,
-                           const std::function<void(int64_t, int64_t)> &on_batch, float *ms, double *flops);
+                           const RankBatchFn &on_batch, float *ms, double *flops);
 
 // The split form for the MF family in fp32 (rank_kernels.hip): S1 per distinct query user, S2 per distinct context, added by the selection.
 struct RankSplitArgs;
 hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, RankSplitArgs base, double thold, int topn,
-                                 const std::function<void(int64_t, int64_t)> &on_batch, float *ms, double *flops);
+                                 const RankBatchFn &on_batch, float *ms, double *flops);
 // whether the split form applies: S2 must stay small (distinct contexts x candidates) and the lists must fit the register selection
 bool rank_split_usable(const RankPlan &plan, int topn, RankWorkspace &ws);
+
+// The slab form, for a model whose scores are no contraction (SLIM: slim_kernels.hip): fill(dS, dcand, nc, dgu, dgq0, g0, g1, q0, nq,
+// stream) writes the fp64 scores of the queries [q0, q0 + nq), whose groups are g0 .. g1 (a group at a batch boundary comes in both
+// batches), into dS[(q - q0) * nc + c]; the exclusions are masked and the lists selected as in rank_run_device.
+using RankSlabFn = std::function<hipError_t(double *, const int32_t *, int, const int32_t *, const int32_t *, int, int, int64_t, int64_t, hipStream_t)>;
+hipError_t rank_run_device_slab(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankSlabFn &fill, double thold, int topn,
+                                const RankBatchFn &on_batch, float *ms);
 
 // the 18 measures of the lists of queries [q0, q1) -> vals[q * 18 + m] (threads over ranges of queries); optional per-query outputs
 void rank_measures_range(const RankPlan &plan, int num_recs, const int32_t *top_idx, const double *top_score, const int32_t *top_count,
@@ -146,19 +195,11 @@ struct RankEvalIO {
     int32_t *q_user, *q_ctx, *q_count, *top_items;
     double *top_scores;
 };
-using RankBatchFn = std::function<void(int64_t, int64_t)>;
-// Recommender.evalRankings around a model's scorer, shared by cmi_eval_rankings and cmi_fm_eval_rankings: the argument checks, the id
+// Recommender.evalRankings around a model's scorer, shared by every model's eval_rankings entry point: the argument checks, the id
 // checks (context ids below ctx_bound; INT64_MAX: any non-negative id), the plan (kept while the tuples are the same, by content hash),
 // the measures and the users' means folded batch by batch behind the device, the averages.  `ready` checks the model's preconditions
 // and makes its device current; `score` runs the device loop over the plan and hands every batch of lists to on_batch.  Messages go
 // to `err`, prefixed "<what>: ".
-// The slab form, for a model whose scores are no contraction (SLIM: slim_kernels.hip): fill(dS, dcand, nc, dgu, dgq0, g0, g1, q0, nq,
-// stream) writes the fp64 scores of the queries [q0, q0 + nq), whose groups are g0 .. g1 (a group at a batch boundary comes in both
-// batches), into dS[(q - q0) * nc + c]; the exclusions are masked and the lists selected as in rank_run_device.
-using RankSlabFn = std::function<hipError_t(double *, const int32_t *, int, const int32_t *, const int32_t *, int, int, int64_t, int64_t, hipStream_t)>;
-hipError_t rank_run_device_slab(hipStream_t stream, RankWorkspace &ws, const RankPlan &plan, const RankSlabFn &fill, double thold, int topn,
-                                const RankBatchFn &on_batch, float *ms);
-
 int rank_evaluate(std::string &err, const char *what, RankWorkspace &ws, int n_users, int n_items, int64_t ctx_bound, const RankEvalIO &io,
                   const std::function<int()> &ready, const std::function<hipError_t(const RankPlan &, const RankBatchFn &)> &score);
 

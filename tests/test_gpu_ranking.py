@@ -403,3 +403,43 @@ def test_two_instances_evaluate_rankings_at_the_same_time():
         os.environ.pop("CMI_RANK_BATCH", None)
     assert not errors, errors
     assert len(done) == 2
+
+
+def test_a_reused_handle_answers_like_a_fresh_one_across_forms_models_and_splits():
+    """The index arrays of a plan stay on the device while the tuples stay the same (an early-stop loop evaluates after every epoch),
+    one tag per buffer.  One handle evaluates: split A in the split form, A again (every array resident), A with lists of 70 (the
+    per-query form on the same plan: it uploads its arrays again and leaves them tagged), A in batches of 7 groups, A after another model
+    was set, another split B of the same data (a new plan: nothing is resident), A again.  Every result equals, entry for entry, the
+    result of the same call on a handle that has evaluated nothing before: a stale or a missing upload of any index array moves lists."""
+    data = synth.generate(60, 90, 3, 3, 2500, seed=3)
+    A, B = synth.split(data, 0.25), synth.split(data, 0.25, seed=77)
+    gm = oracle_c.global_mean(A[0].r)
+    states = [synth.init_state("CAMF_CI", data, 10, seed=s) for s in (9, 10)]
+
+    def handle(state):
+        inst = capi.Instance("CAMF_CI", 10, data.n_users, data.n_items, data.n_conds)
+        inst.set_hparams(util.REG, util.REG, util.REG, util.REGC, gm)
+        inst.set_ratings(A[0].u, A[0].j, A[0].ctx, A[0].r, A[0].ctx_ptr, A[0].ctx_conds)
+        inst.set_states(state)
+        return inst
+
+    def evaluate(inst, split, num_recs, batch):
+        return _with_env({"CMI_RANK_BATCH": batch, "CMI_RANK_NO_SPLIT": None},
+                         lambda: inst.eval_rankings(_arrays(split[0]), _arrays(split[1]), bin_thold=2.5, num_recs=num_recs, with_lists=True))
+
+    steps = [(A, 10, None, 0), (A, 10, None, 0), (A, 70, None, 0), (A, 10, "7", 0), (A, 10, None, 1), (B, 10, None, 1), (A, 10, None, 1)]
+    one, model, fresh = handle(states[0]), 0, []
+    for n, (split, num_recs, batch, m) in enumerate(steps, 1):
+        if m != model:
+            one.set_states(states[m])
+            model = m
+        got = evaluate(one, split, num_recs, batch)
+        # the form the step is meant to take: only the split form times its two kernels
+        assert (one.last_rank_kernel_ms()["contraction"] > 0.0) == (num_recs <= 64), n
+        new = handle(states[m])
+        fresh.append(evaluate(new, split, num_recs, batch))
+        new.close()
+        util.assert_same_rankings(got, fresh[-1], "step %d" % n)
+    # the steps differ where they should: a stale model or a stale plan would not have passed unseen
+    assert len(fresh[0][1]) > 20 and fresh[3][1] != fresh[4][1] and fresh[4][1].keys() != fresh[5][1].keys()
+    one.close()

@@ -17,7 +17,7 @@ from oracle import rank_oracle
 from tests import slim_ref as sref
 from tests.hostmirror import splitter
 from tests.hostmirror.javarand import JavaRandom
-from tests.util import same_bits_exact, to2d
+from tests.util import assert_same_rankings, same_bits_exact, to2d, with_env
 
 pytestmark = pytest.mark.gpu
 
@@ -436,3 +436,29 @@ def test_driver_parity_depaul(tmp_path):
     for g, name in zip(m.groups(), ("Pre10", "Rec10", "AUC10", "MAP10", "NDCG10", "MRR10")):
         print(name, g, want[name])
         assert abs(float(g) - want[name]) <= 1e-12, (name, g, want[name])
+
+
+def test_a_reused_handle_answers_like_a_fresh_one():
+    """The slab form keeps the plan's index arrays on the device while the tuples stay the same.  One handle evaluates split A, A again
+    (every array resident), A in batches of 7 queries, another split B (a new plan), A again; every result equals, entry for entry, the
+    result of the same call on a handle that has evaluated nothing before."""
+    run = next(r for r in RUNS if r["name"] == "knn_matrix knn=5 l1=0.1 l2=0.5")
+
+    def handle():
+        h = instance(run["n_users"], run["n_items"], run["cells"])
+        h.build_neighbors(run["knn"], run["measure"], run["shrinkage"])
+        h.set_weights(flat(run["W"][max(run["W"])]))
+        return h
+
+    def evaluate(h, split, batch):
+        return with_env(lambda: h.eval_rankings(split[0], split[1], bin_thold=-1.0, num_recs=10, with_lists=True), CMI_RANK_BATCH=batch)
+
+    A, B = contextual_split(run["cells"], 4, 11), contextual_split(run["cells"], 4, 12)
+    one, fresh = handle(), []
+    for n, (split, batch) in enumerate([(A, None), (A, None), (A, 7), (B, None), (A, None)], 1):
+        new = handle()
+        fresh.append(evaluate(new, split, batch))
+        new.close()
+        assert_same_rankings(evaluate(one, split, batch), fresh[-1], "step %d" % n)
+    assert len(fresh[0][1]) > 0 and fresh[0][1].keys() != fresh[3][1].keys()
+    one.close()

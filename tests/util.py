@@ -210,6 +210,17 @@ def same_bits_exact(a, b):
     return same_bits(a, b, nan_equal=False)
 
 
+def assert_same_rankings(got, want, label):
+    """two results of eval_rankings(with_lists=True): every measure bit for bit (NaN = NaN), every list entry for entry"""
+    (res, lists), (ref, ref_lists) = got, want
+    assert res.keys() == ref.keys(), label
+    for m in ref:
+        assert same_bits([res[m]], [ref[m]]), (label, m, res[m], ref[m])
+    assert lists.keys() == ref_lists.keys(), label
+    for key, ref_l in ref_lists.items():
+        assert lists[key] == ref_l, (label, key, lists[key], ref_l)
+
+
 def to2d(u, j, r):
     """DataDAO.toTraditionalSparseMatrix: each (user, item) cell's mean over its tuples, summed in tuple order"""
     order = np.lexsort((np.arange(len(r)), j, u))
