@@ -201,6 +201,18 @@ SYMBOLS = [
                                          C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
     ("cmi_slim_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_slim_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_rankals_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_rankals_destroy", C.c_int, [_vp]),
+    ("cmi_rankals_last_error", C.c_char_p, [_vp]),
+    ("cmi_rankals_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_rankals_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_rankals_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_rankals_iterate", C.c_int, [_vp, C.c_int]),
+    ("cmi_rankals_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_rankals_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                            C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_rankals_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_rankals_invert", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -940,7 +952,8 @@ def knn_measure(name):
 
 
 class _PairModel(_Handle):
-    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*, cmi_nmf_*, cmi_slim_*)."""
+    """What the pair-co-occurrence handles share: `_prefix` names their C functions (cmi_knn_*, cmi_slope_*, cmi_nmf_*, cmi_slim_*,
+    cmi_rankals_*)."""
 
     _prefix = ""
 
@@ -1020,11 +1033,9 @@ class SlopeOneInstance(_PairModel):
         return self._predict(u, j, global_mean=global_mean, bound=bound, lo=lo, hi=hi)
 
 
-class NMFInstance(_PairModel):
-    """The reference's NMF on one GPU (a `cmi_nmf_handle`): W is (n_users, k), H is (k, n_items), 1 <= k <= 256."""
-
-    _api = ("cmi_nmf_create", "cmi_nmf_destroy", "cmi_nmf_last_error")
-    _prefix = "cmi_nmf"
+class _FactorModel(_PairModel):
+    """What the handles of a k-factor model of the 2-D train matrix share (cmi_nmf_*, cmi_rankals_*): create(k, n_users, n_items, ...)
+    and the shape check of an injected factor matrix."""
 
     def __init__(self, k, n_users, n_items, device=0, flags=0):
         self.k, self.n_users, self.n_items = k, n_users, n_items
@@ -1037,6 +1048,13 @@ class NMFInstance(_PairModel):
         if a.shape != shape:
             raise CmiError(E_INVALID, "%s has shape %s, not %s" % (name, a.shape, shape))
         return a
+
+
+class NMFInstance(_FactorModel):
+    """The reference's NMF on one GPU (a `cmi_nmf_handle`): W is (n_users, k), H is (k, n_items), 1 <= k <= 256."""
+
+    _api = ("cmi_nmf_create", "cmi_nmf_destroy", "cmi_nmf_last_error")
+    _prefix = "cmi_nmf"
 
     def set_model(self, W=None, H=None):
         W = self._shaped(W, (self.n_users, self.k), "W")
@@ -1141,3 +1159,52 @@ class SLIMInstance(_PairModel):
         ms = (C.c_float * 2)()
         self._chk(self.L.cmi_slim_last_iter_ms(self.h, ms))
         return tuple(ms)
+
+
+class RankALSInstance(_FactorModel):
+    """The reference's RankALS on one GPU (a `cmi_rankals_handle`): P is (n_users, k), Q is (n_items, k), 1 <= k <= 64."""
+
+    _api = ("cmi_rankals_create", "cmi_rankals_destroy", "cmi_rankals_last_error")
+    _prefix = "cmi_rankals"
+
+    def set_model(self, P=None, Q=None):
+        P = self._shaped(P, (self.n_users, self.k), "P")
+        Q = self._shaped(Q, (self.n_items, self.k), "Q")
+        self._chk(self.L.cmi_rankals_set_model(self.h, None if P is None else _p(P), None if Q is None else _p(Q)))
+
+    def model(self):
+        """(P, Q)"""
+        P, Q = np.empty((self.n_users, self.k)), np.empty((self.n_items, self.k))
+        self._chk(self.L.cmi_rankals_get_model(self.h, _p(P), _p(Q)))
+        return P, Q
+
+    def iterate(self, support_weight):
+        """one pass of buildModel's loop: the P step over the users of rows(), the Q step over every item"""
+        self._chk(self.L.cmi_rankals_iterate(self.h, 1 if support_weight else 0))
+
+    def predict(self, u, j):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_rankals_predict_batch(self.h, len(u), _p(u), _p(j), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_rankals_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_iter_ms(self):
+        """(item moments, user solves, user moments, item solves) device milliseconds of the last iterate() and the scoring loop of the
+        last eval_rankings(); 0.0 for whichever of the two has not run yet"""
+        ms = (C.c_float * 5)()
+        self._chk(self.L.cmi_rankals_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+    def invert(self, A):
+        """librec's DenseMatrix.inv() of a batch of square matrices, shape (n_mats, n, n), by the device routine the solves use"""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 3 or A.shape[1] != A.shape[2]:
+            raise CmiError(E_INVALID, "A has shape %s, not (n_mats, n, n)" % (A.shape,))
+        out = np.empty_like(A)
+        self._chk(self.L.cmi_rankals_invert(self.h, A.shape[0], A.shape[1], _p(A), _p(out)))
+        return out

@@ -1,7 +1,9 @@
 // carskit_main.cpp -- `carskit-mi355x -c setting.conf`: the reference driver's flow (src/carskit/main/CARSKit.java:
 // execute :109, preset :140, readData :220, runAlgorithm :310, runCrossValidation :388, printEvalInfo :362) for the
 // recommenders libcarskit_mi355x accelerates (rating prediction, or top-N evaluation with item.ranking=on).  Links nothing but the C ABI.
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <mutex>
@@ -64,6 +66,39 @@ struct Dao {
     }
 };
 
+// java.lang.Float.toString of a finite value: the fewest decimal digits that read back as the same float, at least one after the point;
+// plain notation for 1e-3 <= |x| < 1e7, else d.dddE[-]x
+static std::string java_float_string(float x) {
+    if (x == 0.0f) return std::signbit(x) ? "-0.0" : "0.0";
+    char e[32];
+    int prec = 0;
+    for (; prec < 9; ++prec) {
+        snprintf(e, sizeof e, "%.*e", prec, (double)x);
+        if (std::strtof(e, nullptr) == x) break;
+    }
+    std::string digits; // the significant digits and the decimal exponent of d.ddd e x
+    const char *p = e;
+    const bool neg = *p == '-';
+    if (neg) ++p;
+    for (; *p && *p != 'e'; ++p)
+        if (*p != '.') digits += *p;
+    const int ex = (int)std::strtol(p + 1, nullptr, 10);
+    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
+    std::string out = neg ? "-" : "";
+    const double a = std::fabs((double)x);
+    if (a >= 1e-3 && a < 1e7) {
+        if (ex >= 0) {
+            while ((int)digits.size() < ex + 1) digits += '0';
+            out += digits.substr(0, (size_t)ex + 1) + "." + ((int)digits.size() > ex + 1 ? digits.substr((size_t)ex + 1) : "0");
+        } else {
+            out += "0." + std::string((size_t)(-ex - 1), '0') + digits;
+        }
+    } else {
+        out += digits.substr(0, 1) + "." + (digits.size() > 1 ? digits.substr(1) : "0") + "E" + std::to_string(ex);
+    }
+    return out;
+}
+
 static std::string evalInfo(const Measures &m, const Conf &conf) { // Recommender.getEvalInfo (Recommender.java:437-499)
     char buf[1024];
     if (conf.isRankingPred) { // the reference's separators are irregular; kept as they are
@@ -113,6 +148,13 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
         // SLIM is a top-N model (item.ranking -diverse is refused with every model, by Conf), on one GPU
         if (a == "slim" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": SLIM runs on one GPU");
+        // RankALS: a top-N model on one GPU; its constructor calls checkBinary() (RankALS.java:63, Recommender.java:1154-1160)
+        if (a == "rankals" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": RankALS runs on one GPU");
+        if (a == "rankals" && conf.binThold < 0) {
+            const std::string t = java_float_string((float)conf.binThold); // the "{}" of Logs.error: Float.toString
+            throw std::runtime_error("val.binary.threshold=" + t + ", ratings must be binarized first! Try set a non-negative value.");
+        }
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
@@ -147,7 +189,8 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     const std::string algoName = LineConfiger(cf.getString("recommender")).getMainParam();
     {   // the similarity-based CAMF recommenders are top-N models: their constructors switch the (static) isRankingPred on
         const std::string a = lower(algoName);
-        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim") conf.isRankingPred = true; // SLIM.java:68
+        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals")
+            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61
     }
     log("With Setup: " + cf.getString("evaluation.setup"));
     std::vector<Measures> all;

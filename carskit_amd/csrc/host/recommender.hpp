@@ -161,6 +161,8 @@ struct Conf {
     // SLIM=-l1 -l2 -k (SLIM.java:71-74): the regularisers are Java floats, held here as the doubles they widen to
     double slimL1 = 0, slimL2 = 0;
     int slimKnn = 0;
+    // RankALS=-sw on|off (RankALS.java:71: algoOptions.isOn("-sw")); without the RankALS key the reference's algoOptions is null
+    bool rankalsSw = false, rankalsSet = false;
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
         if (cf.contains("learn.rate")) {
@@ -216,6 +218,10 @@ struct Conf {
             slimL1 = sl.getFloat("-l1", 0);
             slimL2 = sl.getFloat("-l2", 0);
             slimKnn = sl.getInt("-k", 0);
+        }
+        if (cf.contains("RankALS")) {
+            rankalsSet = true;
+            rankalsSw = cf.getParamOptions("RankALS").isOn("-sw", false);
         }
         if (cf.contains("FM")) {
             LineConfiger fm = cf.getParamOptions("FM");
@@ -655,10 +661,11 @@ class FM : public IterativeRecommender {
     cmi_fm_handle fm_ = nullptr;
 };
 
-// What ItemKNN, UserKNN, SlopeOne and NMF share: a model of the 2-D train matrix behind a handle H of the C ABI, rating prediction only,
-// nothing to initialise (NMF draws its own W and H) and nothing to save (the reference's saveModel() of the memory-based models is
-// empty); evaluation through the generic
-// evalRatings recipe on bounded predictions.
+// What ItemKNN, UserKNN, SlopeOne, NMF, SLIM and RankALS share: a model of the 2-D train matrix behind a handle H of the C ABI.  The
+// defaults here are those of the rating models: nothing to initialise, nothing to save (the reference's saveModel() of the memory-based
+// models is empty), evaluation through the generic evalRatings recipe on bounded predictions.  NMF, SLIM and RankALS draw their own
+// model in initModel(); the top-N models SLIM and RankALS evaluate through evalRankings() and refuse predictBounded(); RankALS saves
+// the P and Q it trains.
 template <typename H, int (*destroy)(H), const char *(*last_error)(H),
           int (*set_ratings)(H, int64_t, const int32_t *, const int32_t *, const double *)>
 class PairRecommender : public IterativeRecommender {
@@ -875,6 +882,81 @@ class SLIM : public PairRecommender<cmi_slim_handle, cmi_slim_destroy, cmi_slim_
     void predictBounded(double *) override { throw std::runtime_error("SLIM is a top-N recommender: it has no rating evaluation"); }
 };
 
+// src/carskit/alg/baseline/ranking/RankALS.java: P and Q by alternating least squares for ranking over the 2-D train matrix, for top-N.
+// Parameters: num.factors, num.max.iter, RankALS=-sw on|off.  The constructor sets the static isRankingPred = true (RankALS.java:61),
+// so execute() evaluates with evalRankings() whatever item.ranking says, and calls checkBinary() (:63; the driver refuses there).
+class RankALS : public PairRecommender<cmi_rankals_handle, cmi_rankals_destroy, cmi_rankals_last_error, cmi_rankals_set_ratings> {
+  public:
+    RankALS(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("RankALS", tr, te, fold, c, log) {
+        conf_.isRankingPred = true;
+    }
+    // RankALS.java:67-80: super.initModel() draws P and Q, gaussian (IterativeRecommender.java:235-241; initByNorm stays true); s and
+    // sum_s are the library's (cmi_rankals_set_ratings)
+    void initModel() override {
+        if (!conf_.rankalsSet) // algoOptions = getModelParams("RankALS") is null without the key: algoOptions.isOn throws
+            throw std::runtime_error("null (RankALS is not set: RankALS=-sw on|off)");
+        JavaRandom rnd(conf_.randSeed);
+        const size_t nu = (size_t)trainMatrix.n_users, ni = (size_t)trainMatrix.n_items, k = (size_t)conf_.numFactors;
+        P.resize(nu * k);
+        Q.resize(ni * k);
+        for (double &x : P) x = 0.0 + 0.1 * rnd.nextGaussian();
+        for (double &x : Q) x = 0.0 + 0.1 * rnd.nextGaussian();
+    }
+    void buildModel() override { // RankALS.java:83-206: for (iter = 1; iter < numIters; iter++), no loss, no convergence test
+        check(cmi_rankals_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, 0, &h_), "cmi_rankals_create");
+        setRatings("cmi_rankals_set_ratings");
+        check(cmi_rankals_set_model(h_, P.data(), Q.data()), "cmi_rankals_set_model");
+        for (int iter = 1; iter < conf_.numIters; ++iter) {
+            if (conf_.verbose && log_)
+                log_(algoName + (fold_ > 0 ? " fold [" + std::to_string(fold_) + "]" : "") + " runs at iter = " + std::to_string(iter) + "/" +
+                     std::to_string(conf_.numIters));
+            check(cmi_rankals_iterate(h_, conf_.rankalsSw ? 1 : 0), "cmi_rankals_iterate");
+            itersDone = iter;
+        }
+        check(cmi_rankals_get_model(h_, P.data(), Q.data()), "cmi_rankals_get_model");
+    }
+    Measures evalRankings() override { // Recommender.java:668-964 with IterativeRecommender.predict(u, j)
+        static const char *names[CMI_RANK_MEASURES] = {"Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN",
+                                                       "MAP5", "MAP10", "MAPN", "NDCG5", "NDCG10", "NDCGN", "MRR5", "MRR10",
+                                                       "MRRN", "D5", "D10", "DN"};
+        double out[CMI_RANK_MEASURES];
+        int64_t nq = 0;
+        check(cmi_rankals_eval_rankings(h_, trainMatrix.n(), trainMatrix.u.data(), trainMatrix.j.data(), trainMatrix.ctx.data(),
+                                        trainMatrix.r.data(), testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(),
+                                        testMatrix.r.data(), conf_.binThold, conf_.numRecs, conf_.numIgnore,
+                                        conf_.evalStrategy == "uc" ? CMI_RANK_UC : CMI_RANK_UCU, out, &nq, nullptr, nullptr, nullptr, nullptr,
+                                        nullptr), "cmi_rankals_eval_rankings");
+        Measures m;
+        for (int i = 0; i < CMI_RANK_MEASURES; ++i) m[names[i]] = out[i];
+        return m;
+    }
+    // IterativeRecommender.java:249-270 writes P and Q, which this model trains: they go through the writer of the MF classes, as the
+    // states of a PMF handle with fp64 state (the same two containers, no bit lost), into modelPath()
+    void saveModel() override {
+        cmi_handle m = nullptr;
+        if (cmi_create(CMI_MODEL_PMF, conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, 0, conf_.device, CMI_FLAG_STATE_F64,
+                       &m) != CMI_OK)
+            throw std::runtime_error(std::string("cmi_create: ") + cmi_last_error(nullptr));
+        try {
+            carskit::check(cmi_set_state(m, CMI_STATE_P, P.data(), (int64_t)P.size(), CMI_DTYPE_F64), m, "cmi_set_state");
+            carskit::check(cmi_set_state(m, CMI_STATE_Q, Q.data(), (int64_t)Q.size(), CMI_DTYPE_F64), m, "cmi_set_state");
+            const std::string mk = "mkdir -p '" + conf_.workingPath + algoName + "'";
+            if (std::system(mk.c_str()) != 0) throw std::runtime_error("cannot create " + conf_.workingPath + algoName);
+            carskit::check(cmi_save_model(m, modelPath().c_str(), lRate, last_loss, itersDone), m, "cmi_save_model");
+        } catch (...) {
+            cmi_destroy(m);
+            throw;
+        }
+        cmi_destroy(m);
+        if (log_) log_("Learned models are saved to folder \"" + conf_.workingPath + algoName + "/\"");
+    }
+    std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
+
+  private:
+    void predictBounded(double *) override { throw std::runtime_error("RankALS is a top-N recommender: it has no rating evaluation"); }
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -895,7 +977,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
     if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
     if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, itemknn, userknn, slopeone, nmf)");
+    if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -1,6 +1,7 @@
 // pair_host.hpp -- the host side that the pair-co-occurrence handles share (cmi_knn_*: knn_api.cpp, cmi_slope_*: slopeone_api.cpp,
-// cmi_nmf_*: nmf_api.cpp, cmi_slim_*: slim_api.cpp): the handle's common state, the ingest of the 2-D train matrix, librec's contains()
-// flags and its zero-cell filter, the dense-matrix reservation and the timed build (the prediction batch is abi_predict).
+// cmi_nmf_*: nmf_api.cpp, cmi_slim_*: slim_api.cpp, cmi_rankals_*: rankals_api.cpp): the handle's common state, the ingest of the 2-D
+// train matrix, librec's contains() flags and its zero-cell filter, the dense-matrix reservation and the timed build (the prediction
+// batch is abi_predict).
 // Every function that can fail takes the C function's name, `fn`, which opens its messages.  Internal.
 #pragma once
 #include <algorithm>

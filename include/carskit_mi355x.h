@@ -719,6 +719,47 @@ int cmi_slim_last_build_ms(cmi_slim_handle h, float *ms);
 /* device time of the last cmi_slim_iterate, by events: ms[0] the sweep (SLIM.java:130-176), ms[1] the loss chain (:160) */
 int cmi_slim_last_iter_ms(cmi_slim_handle h, float ms[2]);
 
+/* ---- RankALS (src/carskit/alg/baseline/ranking/RankALS.java; rankals_api.cpp, rankals_kernels.hip) ---------------------------------
+ * Takacs & Tikk's alternating least squares for personalised ranking over the 2-D train matrix, fp64, bit-exact to the reference: per
+ * iteration one k x k solve per user of train.rows() and one per item, every sum one left-to-right chain from 0.0 without FMA, the
+ * solve librec's DenseMatrix.inv() (Gauss-Jordan, first-strictly-greater pivot, the identity as it stands when a column has no pivot)
+ * followed by mult().  A cell whose value is 0 takes no part.  The four sums of the Q step that do not read the item are formed once
+ * per iteration, in the reference's order, instead of once per item.  No CPU fallback: without a device cmi_rankals_create returns
+ * CMI_E_NO_DEVICE. */
+typedef struct cmi_rankals_instance *cmi_rankals_handle;
+/* RankALS.java:47-79, IterativeRecommender.java:235-236 (numFactors, the shapes of P and Q).  The solve keeps `mat` and `I` in LDS,
+ * 16 k^2 bytes: k > 64 -> CMI_E_UNSUPPORTED */
+int cmi_rankals_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_rankals_handle *out);
+int cmi_rankals_destroy(cmi_rankals_handle h);
+const char *cmi_rankals_last_error(cmi_rankals_handle h);
+/* Recommender.java:1076-1081 (train) and RankALS.java:73-79 (s_i = train.columnSize(i) or 1, sum_s): the 2-D train matrix as n cells;
+ * a duplicate (u, i) or an id out of range -> CMI_E_INVALID; n >= 2^31 -> CMI_E_UNSUPPORTED */
+int cmi_rankals_set_ratings(cmi_rankals_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* IterativeRecommender.java:235-241: P (n_users x k) and Q (n_items x k), row-major, drawn by the caller.  Either may be NULL (left as
+ * it is) after the first call */
+int cmi_rankals_set_model(cmi_rankals_handle h, const double *P, const double *Q);
+int cmi_rankals_get_model(cmi_rankals_handle h, double *P, double *Q);
+/* RankALS.java:84-205, one pass of buildModel's loop: sum_sq and sum_sqq (:91-98), P[u] = M.inv().mult(y) for every user of rows()
+ * (:100-137), the per-user m_* values (:140-166), Q[i] = M.inv().mult(y) for every item (:168-204).  support_weight: -sw
+ * (RankALS.java:71,76) */
+int cmi_rankals_iterate(cmi_rankals_handle h, int support_weight);
+/* IterativeRecommender.java:126-128, predict(u, j) = DenseMatrix.rowMult(P, u, Q, j) of n tuples: unbounded, context-free */
+int cmi_rankals_predict_batch(cmi_rankals_handle h, int64_t n, const int32_t *u, const int32_t *j, double *out);
+/* Recommender.evalRankings (Recommender.java:668-964) with that predict as the scorer: arguments, outputs and semantics exactly as
+ * cmi_slim_eval_rankings above.  The scores of a user are computed once and serve all of the user's contexts */
+int cmi_rankals_eval_rankings(cmi_rankals_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                              const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
+                              const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy, double out[21],
+                              int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items,
+                              double *top_scores);
+/* device time by events: of the last cmi_rankals_iterate ms[0] the item moments (RankALS.java:91-98), ms[1] the user solves (:100-166),
+ * ms[2] the item-independent sums of the Q step (:184-189), ms[3] the item solves (:168-204), 0 before an iteration; ms[4] the scoring
+ * and selection of the last cmi_rankals_eval_rankings, 0 before one.  Before both an iteration and an evaluation -> CMI_E_INVALID */
+int cmi_rankals_last_iter_ms(cmi_rankals_handle h, float ms[5]);
+/* librec DenseMatrix.inv() of n_mats n x n row-major matrices, A -> out, by the device routine both solves use: the pivot paths can be
+ * tested directly.  n > 64 -> CMI_E_UNSUPPORTED */
+int cmi_rankals_invert(cmi_rankals_handle h, int n_mats, int n, const double *A, double *out);
+
 #ifdef __cplusplus
 }
 #endif
