@@ -213,6 +213,26 @@ SYMBOLS = [
                                             C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
     ("cmi_rankals_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_rankals_invert", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp]),
+    ("cmi_bpr_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_bpr_destroy", C.c_int, [_vp]),
+    ("cmi_bpr_last_error", C.c_char_p, [_vp]),
+    ("cmi_bpr_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_bpr_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_bpr_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_bpr_set_random_state", C.c_int, [_vp, _i64]),
+    ("cmi_bpr_get_random_state", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("cmi_bpr_sample", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.POINTER(_i64)]),
+    ("cmi_bpr_iterate", C.c_int, [_vp, _dbl, _dbl, _dbl, C.POINTER(_dbl)]),
+    ("cmi_bpr_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_bpr_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                        C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_bpr_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_bpr_last_schedule", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("cmi_bpr_levels", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
+    ("cmi_bpr_sample_host", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, C.POINTER(_i64), _i64, _vp, _vp, _vp]),
+    ("cmi_bpr_rank_block", C.c_int, []),
+    ("cmi_java_next_ints", C.c_int, [C.POINTER(_i64), _i32, _i64, _vp, C.c_int]),
+    ("cmi_java_exp_log", C.c_int, [_i64, _vp, _vp, _vp, C.c_int]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -1208,3 +1228,119 @@ class RankALSInstance(_FactorModel):
         out = np.empty_like(A)
         self._chk(self.L.cmi_rankals_invert(self.h, A.shape[0], A.shape[1], _p(A), _p(out)))
         return out
+
+
+BPR_FLAG_STRICT, BPR_FLAG_HOST_SAMPLER, BPR_FLAG_MIN_SLACK = 0x1, 0x2, 0x4
+JAVA_LCG_MASK = (1 << 48) - 1
+
+
+def java_random_state(seed):
+    """the 48-bit state of `new java.util.Random(seed)`"""
+    return (int(seed) ^ 0x5DEECE66D) & JAVA_LCG_MASK
+
+
+def _bpr_chk(rc, fn):
+    if rc != OK:
+        raise CmiError(rc, (lib().cmi_bpr_last_error(None) or fn.encode()).decode())
+
+
+def java_next_ints(state, bound, n, on_device=False):
+    """Host-only unless on_device: n values of java.util.Random.nextInt(bound) from the 48-bit `state`; (values, state after)"""
+    st, out = _i64(int(state)), np.empty(max(int(n), 1), np.int32)
+    _bpr_chk(lib().cmi_java_next_ints(C.byref(st), int(bound), int(n), _p(out), 1 if on_device else 0), "cmi_java_next_ints")
+    return out[:int(n)], st.value
+
+
+def java_exp_log(x, on_device=False):
+    """Host-only unless on_device: (StrictMath.exp(x), StrictMath.log(x)), fdlibm's algorithms"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    e, l = np.empty(max(len(x), 1)), np.empty(max(len(x), 1))
+    _bpr_chk(lib().cmi_java_exp_log(len(x), _p(x), _p(e), _p(l), 1 if on_device else 0), "cmi_java_exp_log")
+    return e[:len(x)], l[:len(x)]
+
+
+def bpr_levels(n_users, n_items, u, i, j):
+    """Host-only: BPR's level schedule of the triples: (order, level_of, n_levels, max_chain)"""
+    u = np.ascontiguousarray(u, dtype=np.int32)
+    i = np.ascontiguousarray(i, dtype=np.int32)
+    j = np.ascontiguousarray(j, dtype=np.int32)
+    order, level_of = np.empty(max(len(u), 1), np.int32), np.empty(max(len(u), 1), np.int32)
+    nl, chain = _i32(), _i64()
+    _bpr_chk(lib().cmi_bpr_levels(int(n_users), int(n_items), len(u), _p(u), _p(i), _p(j), _p(order), _p(level_of), C.byref(nl),
+                                  C.byref(chain)), "cmi_bpr_levels")
+    return order[:len(u)], level_of[:len(u)], nl.value, chain.value
+
+
+def bpr_sample_host(n_users, n_items, u, i, r, state, n_samples):
+    """Host-only: BPR.java's sequential sampler over the cells' matrix from the 48-bit `state`: (u, i, j, state after)"""
+    u = np.ascontiguousarray(u, dtype=np.int32)
+    i = np.ascontiguousarray(i, dtype=np.int32)
+    r = np.ascontiguousarray(r, dtype=np.float64)
+    st = _i64(int(state))
+    ou, oi, oj = (np.empty(max(int(n_samples), 1), np.int32) for _ in range(3))
+    _bpr_chk(lib().cmi_bpr_sample_host(int(n_users), int(n_items), len(r), _p(u), _p(i), _p(r), C.byref(st), int(n_samples), _p(ou),
+                                       _p(oi), _p(oj)), "cmi_bpr_sample_host")
+    n = int(n_samples)
+    return ou[:n], oi[:n], oj[:n], st.value
+
+
+class BPRInstance(_FactorModel):
+    """The reference's BPR on one GPU (a `cmi_bpr_handle`): P is (n_users, k), Q is (n_items, k), 1 <= k <= 128."""
+
+    _api = ("cmi_bpr_create", "cmi_bpr_destroy", "cmi_bpr_last_error")
+    _prefix = "cmi_bpr"
+
+    def set_model(self, P=None, Q=None):
+        P = self._shaped(P, (self.n_users, self.k), "P")
+        Q = self._shaped(Q, (self.n_items, self.k), "Q")
+        self._chk(self.L.cmi_bpr_set_model(self.h, None if P is None else _p(P), None if Q is None else _p(Q)))
+
+    def model(self):
+        """(P, Q)"""
+        P, Q = np.empty((self.n_users, self.k)), np.empty((self.n_items, self.k))
+        self._chk(self.L.cmi_bpr_get_model(self.h, _p(P), _p(Q)))
+        return P, Q
+
+    def set_random_state(self, state):
+        self._chk(self.L.cmi_bpr_set_random_state(self.h, int(state)))
+
+    def random_state(self):
+        st = _i64()
+        self._chk(self.L.cmi_bpr_get_random_state(self.h, C.byref(st)))
+        return st.value
+
+    def sample(self, on_device=True):
+        """one iteration's triples from the current stream state, which stays: (u, i, j, state after)"""
+        n = self.n_users * 100
+        u, i, j, st = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), _i64()
+        self._chk(self.L.cmi_bpr_sample(self.h, 1 if on_device else 0, _p(u), _p(i), _p(j), C.byref(st)))
+        return u, i, j, st.value
+
+    def iterate(self, lrate, reg_u, reg_i):
+        """one iteration of buildModel's loop (sample, level build, epoch, loss); returns the loss (NaN / Inf raises E_NUMERIC)"""
+        loss = _dbl()
+        self._chk(self.L.cmi_bpr_iterate(self.h, float(lrate), float(reg_u), float(reg_i), C.byref(loss)))
+        return loss.value
+
+    def predict(self, u, j):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_bpr_predict_batch(self.h, len(u), _p(u), _p(j), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_bpr_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_iter_ms(self):
+        """(sampler, level build, epoch, loss) milliseconds of the last iterate() -- the first two host wall time, the others device
+        time -- and the scoring loop of the last eval_rankings(); 0.0 for whichever of the two has not run yet"""
+        ms = (C.c_float * 5)()
+        self._chk(self.L.cmi_bpr_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+    def last_schedule(self):
+        out = (_i64 * 5)()
+        self._chk(self.L.cmi_bpr_last_schedule(self.h, out))
+        return dict(zip(("levels", "alone", "runs", "widest", "sampler_fallbacks"), (int(x) for x in out)))

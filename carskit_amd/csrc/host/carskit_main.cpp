@@ -155,6 +155,9 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
             const std::string t = java_float_string((float)conf.binThold); // the "{}" of Logs.error: Float.toString
             throw std::runtime_error("val.binary.threshold=" + t + ", ratings must be binarized first! Try set a non-negative value.");
         }
+        // BPR: a top-N model on one GPU
+        if (a == "bpr" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": BPR runs on one GPU");
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
@@ -189,9 +192,10 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     const std::string algoName = LineConfiger(cf.getString("recommender")).getMainParam();
     {   // the similarity-based CAMF recommenders are top-N models: their constructors switch the (static) isRankingPred on
         const std::string a = lower(algoName);
-        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals")
-            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61
+        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals" || a == "bpr")
+            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61, BPR.java:42
     }
+    conf.bprStream = std::make_shared<int64_t>((int64_t)cmi::java_lcg_scramble(conf.randSeed));
     log("With Setup: " + cf.getString("evaluation.setup"));
     std::vector<Measures> all;
     std::string name;
@@ -218,7 +222,15 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     if (mode == "cv") {
         int k = 0;
         const std::vector<int> labels = split_folds(data.n(), ev.getInt("-k", 5), conf.randSeed, &k);
-        const bool parallel = ev.isOn("-p", true); // one thread per fold (CARSKit.java:395-412); each fold = its own cmi_handle/stream
+        bool parallel = ev.isOn("-p", true); // one thread per fold (CARSKit.java:395-412); each fold = its own cmi_handle/stream
+        if (lower(algoName) == "bpr") {
+            // BPR draws its triples from happy.coding's static Randoms stream.  The splitter drew from it first, but the first
+            // recommender's constructor then seeds it again (Recommender.java:194-234: resetStatics, set by CARSKit.java:150, makes
+            // the constructor call Randoms.seed(--rand-seed), a new java.util.Random): fold 1 starts at the seed's state, which
+            // conf.bprStream holds, and every later fold goes on where the one before stopped.  So the folds run in sequence, the
+            // reference's `cv -p off` order
+            parallel = false;
+        }
         std::vector<std::thread> ts;
         std::vector<RatingData> trs((size_t)k), tes((size_t)k);
         for (int f = 1; f <= k; ++f) {

@@ -1,7 +1,8 @@
 // recommender.hpp -- C++ host layer above the C ABI, mirroring the reference's plugin interface for the accelerated
 // path (same class names, hooks and lifecycle as src/carskit/generic/{Recommender,IterativeRecommender,
 // ContextRecommender}.java and the model classes).  It uses ONLY include/carskit_mi355x.h -- it is what a JVM-less
-// deployment links, and it shows the boundary is sufficient for a complete host.
+// deployment links, and it shows the boundary is sufficient for a complete host -- and ../java_math.hpp, the header-only JDK
+// arithmetic (fdlibm log, the java.util.Random LCG and its jump-ahead) that the library's host and device code share.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -18,43 +19,14 @@
 #include <vector>
 
 #include "../../../include/carskit_mi355x.h"
+#include "../java_math.hpp"
 #include "configer.hpp"
 
 namespace carskit {
 
-// StrictMath.log = fdlibm __ieee754_log (published algorithm), for finite positive normal x: glibc's log is correctly
-// rounded and differs from fdlibm in the last ulp for some arguments, which would desynchronise nextGaussian().
-inline double fdlibm_log(double x) {
-    static const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10,
-                        Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
-                        Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
-                        Lg7 = 1.479819860511658591e-01;
-    uint64_t bits;
-    static_assert(sizeof bits == sizeof x, "");
-    std::memcpy(&bits, &x, 8);
-    int32_t hx = (int32_t)(bits >> 32), k = 0;
-    if (hx < 0x00100000 || hx >= 0x7ff00000) return std::log(x);
-    k += (hx >> 20) - 1023;
-    hx &= 0x000fffff;
-    const int32_t i0 = (hx + 0x95f64) & 0x100000;
-    bits = ((uint64_t)(uint32_t)(hx | (i0 ^ 0x3ff00000)) << 32) | (bits & 0xffffffffULL);
-    std::memcpy(&x, &bits, 8);
-    k += i0 >> 20;
-    const double f = x - 1.0, dk = (double)k;
-    if ((0x000fffff & (2 + hx)) < 3) {
-        if (f == 0.0) return k == 0 ? 0.0 : dk * ln2_hi + dk * ln2_lo;
-        const double R = f * f * (0.5 - 0.33333333333333333 * f);
-        return k == 0 ? f - R : dk * ln2_hi - ((R - dk * ln2_lo) - f);
-    }
-    const double s = f / (2.0 + f), z = s * s, w = z * z;
-    const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6)), t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
-    const double R = t2 + t1;
-    if (((hx - 0x6147a) | (0x6b851 - hx)) > 0) {
-        const double hfsq = 0.5 * f * f;
-        return k == 0 ? f - (hfsq - s * (hfsq + R)) : dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
-    }
-    return k == 0 ? f - s * (f - R) : dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
-}
+// StrictMath.log = fdlibm __ieee754_log (java_math.hpp, shared with the device): glibc's log is correctly rounded and differs from
+// fdlibm in the last ulp for some arguments, which would desynchronise nextGaussian().
+using cmi::fdlibm_log;
 
 // java.util.Random (published algorithm): fold assignment follows the reference's stream
 // (happy.coding.math.Randoms.seed(n) -> new Random(n); uniform() -> nextDouble()).
@@ -66,6 +38,12 @@ class JavaRandom {
         return (int32_t)((int64_t)seed_ >> (48 - bits));
     }
     double nextDouble() { return (double)(((int64_t)next(26) << 27) + next(27)) * 0x1.0p-53; }
+    int32_t nextInt(int32_t bound) { // bound > 0: java_math.hpp's one statement of the JDK algorithm, on this stream
+        cmi::JavaStream s{seed_, 0};
+        const int32_t r = s.nextInt(bound, INT64_MAX);
+        seed_ = s.state;
+        return r;
+    }
     double nextGaussian() { // polar method with StrictMath.log / StrictMath.sqrt
         if (have_) {
             have_ = false;
@@ -163,6 +141,7 @@ struct Conf {
     int slimKnn = 0;
     // RankALS=-sw on|off (RankALS.java:71: algoOptions.isOn("-sw")); without the RankALS key the reference's algoOptions is null
     bool rankalsSw = false, rankalsSet = false;
+    std::shared_ptr<int64_t> bprStream; // BPR: the 48-bit state of happy.coding's Randoms stream, shared by the folds of a run (null: from randSeed)
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
         if (cf.contains("learn.rate")) {
@@ -691,6 +670,42 @@ class PairRecommender : public IterativeRecommender {
         to2d(trainMatrix, u2, j2, r2);
         check(set_ratings(h_, (int64_t)r2.size(), u2.data(), j2.data(), r2.data()), what);
     }
+    // Recommender.java:668-964 with the handle's predict(u, j) as the scorer (eval: the handle's cmi_*_eval_rankings)
+    template <typename Eval>
+    Measures evalRankingsWith(Eval eval, const char *what) {
+        static const char *names[CMI_RANK_MEASURES] = {"Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN",
+                                                       "MAP5", "MAP10", "MAPN", "NDCG5", "NDCG10", "NDCGN", "MRR5", "MRR10",
+                                                       "MRRN", "D5", "D10", "DN"};
+        double out[CMI_RANK_MEASURES];
+        int64_t nq = 0;
+        check(eval(h_, trainMatrix.n(), trainMatrix.u.data(), trainMatrix.j.data(), trainMatrix.ctx.data(), trainMatrix.r.data(),
+                   testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(), testMatrix.r.data(), conf_.binThold,
+                   conf_.numRecs, conf_.numIgnore, conf_.evalStrategy == "uc" ? CMI_RANK_UC : CMI_RANK_UCU, out, &nq, nullptr, nullptr,
+                   nullptr, nullptr, nullptr), what);
+        Measures m;
+        for (int i = 0; i < CMI_RANK_MEASURES; ++i) m[names[i]] = out[i];
+        return m;
+    }
+    // IterativeRecommender.java:249-270 writes P and Q, which the factor models of this family train: they go through the writer of the
+    // MF classes, as the states of a PMF handle with fp64 state (the same two containers, no bit lost), into modelPath()
+    void saveFactors(const std::vector<double> &P, const std::vector<double> &Q) {
+        cmi_handle m = nullptr;
+        if (cmi_create(CMI_MODEL_PMF, conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, 0, conf_.device, CMI_FLAG_STATE_F64,
+                       &m) != CMI_OK)
+            throw std::runtime_error(std::string("cmi_create: ") + cmi_last_error(nullptr));
+        try {
+            carskit::check(cmi_set_state(m, CMI_STATE_P, P.data(), (int64_t)P.size(), CMI_DTYPE_F64), m, "cmi_set_state");
+            carskit::check(cmi_set_state(m, CMI_STATE_Q, Q.data(), (int64_t)Q.size(), CMI_DTYPE_F64), m, "cmi_set_state");
+            const std::string mk = "mkdir -p '" + conf_.workingPath + algoName + "'";
+            if (std::system(mk.c_str()) != 0) throw std::runtime_error("cannot create " + conf_.workingPath + algoName);
+            carskit::check(cmi_save_model(m, modelPath().c_str(), lRate, last_loss, itersDone), m, "cmi_save_model");
+        } catch (...) {
+            cmi_destroy(m);
+            throw;
+        }
+        cmi_destroy(m);
+        if (log_) log_("Learned models are saved to folder \"" + conf_.workingPath + algoName + "/\"");
+    }
     void check(int rc, const char *what) { // (a failed create leaves h_ null: the thread's message)
         if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + last_error(h_));
     }
@@ -916,45 +931,58 @@ class RankALS : public PairRecommender<cmi_rankals_handle, cmi_rankals_destroy, 
         }
         check(cmi_rankals_get_model(h_, P.data(), Q.data()), "cmi_rankals_get_model");
     }
-    Measures evalRankings() override { // Recommender.java:668-964 with IterativeRecommender.predict(u, j)
-        static const char *names[CMI_RANK_MEASURES] = {"Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN",
-                                                       "MAP5", "MAP10", "MAPN", "NDCG5", "NDCG10", "NDCGN", "MRR5", "MRR10",
-                                                       "MRRN", "D5", "D10", "DN"};
-        double out[CMI_RANK_MEASURES];
-        int64_t nq = 0;
-        check(cmi_rankals_eval_rankings(h_, trainMatrix.n(), trainMatrix.u.data(), trainMatrix.j.data(), trainMatrix.ctx.data(),
-                                        trainMatrix.r.data(), testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(),
-                                        testMatrix.r.data(), conf_.binThold, conf_.numRecs, conf_.numIgnore,
-                                        conf_.evalStrategy == "uc" ? CMI_RANK_UC : CMI_RANK_UCU, out, &nq, nullptr, nullptr, nullptr, nullptr,
-                                        nullptr), "cmi_rankals_eval_rankings");
-        Measures m;
-        for (int i = 0; i < CMI_RANK_MEASURES; ++i) m[names[i]] = out[i];
-        return m;
-    }
-    // IterativeRecommender.java:249-270 writes P and Q, which this model trains: they go through the writer of the MF classes, as the
-    // states of a PMF handle with fp64 state (the same two containers, no bit lost), into modelPath()
-    void saveModel() override {
-        cmi_handle m = nullptr;
-        if (cmi_create(CMI_MODEL_PMF, conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, 0, conf_.device, CMI_FLAG_STATE_F64,
-                       &m) != CMI_OK)
-            throw std::runtime_error(std::string("cmi_create: ") + cmi_last_error(nullptr));
-        try {
-            carskit::check(cmi_set_state(m, CMI_STATE_P, P.data(), (int64_t)P.size(), CMI_DTYPE_F64), m, "cmi_set_state");
-            carskit::check(cmi_set_state(m, CMI_STATE_Q, Q.data(), (int64_t)Q.size(), CMI_DTYPE_F64), m, "cmi_set_state");
-            const std::string mk = "mkdir -p '" + conf_.workingPath + algoName + "'";
-            if (std::system(mk.c_str()) != 0) throw std::runtime_error("cannot create " + conf_.workingPath + algoName);
-            carskit::check(cmi_save_model(m, modelPath().c_str(), lRate, last_loss, itersDone), m, "cmi_save_model");
-        } catch (...) {
-            cmi_destroy(m);
-            throw;
-        }
-        cmi_destroy(m);
-        if (log_) log_("Learned models are saved to folder \"" + conf_.workingPath + algoName + "/\"");
-    }
+    Measures evalRankings() override { return evalRankingsWith(cmi_rankals_eval_rankings, "cmi_rankals_eval_rankings"); }
+    void saveModel() override { saveFactors(P, Q); }
     std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
 
   private:
     void predictBounded(double *) override { throw std::runtime_error("RankALS is a top-N recommender: it has no rating evaluation"); }
+};
+
+// src/carskit/alg/baseline/ranking/BPR.java: P and Q by stochastic gradient steps over numUsers * 100 sampled (u, i, j) triples an
+// iteration, for top-N.  Parameters: num.factors, num.max.iter, learn.rate, reg.lambda -u -i.  The constructor sets the static
+// isRankingPred = true (BPR.java:42) and initByNorm = false (:43).  The triples come from happy.coding's static Randoms stream, which
+// the first recommender's constructor seeds with --rand-seed (Recommender.java:194-234, after the splitter's draws): conf.bprStream
+// starts at the seed's state and carries the stream from fold to fold.
+class BPR : public PairRecommender<cmi_bpr_handle, cmi_bpr_destroy, cmi_bpr_last_error, cmi_bpr_set_ratings> {
+  public:
+    BPR(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("BPR", tr, te, fold, c, log) {
+        conf_.isRankingPred = true;
+    }
+    // IterativeRecommender.java:235-241 with initByNorm = false: P.init(), Q.init() = Randoms.uniform() per cell, row by row
+    void initModel() override {
+        JavaRandom rnd(conf_.randSeed);
+        P.resize((size_t)trainMatrix.n_users * (size_t)conf_.numFactors);
+        Q.resize((size_t)trainMatrix.n_items * (size_t)conf_.numFactors);
+        for (double &x : P) x = rnd.nextDouble();
+        for (double &x : Q) x = rnd.nextDouble();
+    }
+    void buildModel() override { // BPR.java:55-109
+        // the loss as the reference's one chain (6 ns a term on an MI355X, profiles/bpr_bench.json) up to 2^18 terms, under 2 ms;
+        // else the fixed tree
+        const bool small = (int64_t)trainMatrix.n_users * 100 * (conf_.numFactors + 1) <= ((int64_t)1 << 18);
+        check(cmi_bpr_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, small ? CMI_BPR_FLAG_STRICT : 0u, &h_),
+              "cmi_bpr_create");
+        setRatings("cmi_bpr_set_ratings");
+        check(cmi_bpr_set_model(h_, P.data(), Q.data()), "cmi_bpr_set_model");
+        const int64_t start = conf_.bprStream ? *conf_.bprStream : (int64_t)cmi::java_lcg_scramble(conf_.randSeed);
+        check(cmi_bpr_set_random_state(h_, start), "cmi_bpr_set_random_state");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_bpr_iterate(h_, lRate, conf_.regU, conf_.regI, &loss);
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_bpr_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        if (conf_.bprStream) check(cmi_bpr_get_random_state(h_, conf_.bprStream.get()), "cmi_bpr_get_random_state");
+        check(cmi_bpr_get_model(h_, P.data(), Q.data()), "cmi_bpr_get_model");
+    }
+    Measures evalRankings() override { return evalRankingsWith(cmi_bpr_eval_rankings, "cmi_bpr_eval_rankings"); }
+    void saveModel() override { saveFactors(P, Q); }
+    std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
+
+  private:
+    void predictBounded(double *) override { throw std::runtime_error("BPR is a top-N recommender: it has no rating evaluation"); }
 };
 
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
@@ -978,7 +1006,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
     if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
     if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, itemknn, userknn, slopeone, nmf)");
+    if (n == "bpr") return std::unique_ptr<IterativeRecommender>(new BPR(tr, te, fold, c, log));
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

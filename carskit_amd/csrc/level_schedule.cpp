@@ -472,4 +472,35 @@ bool build_chain_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t
     return true;
 }
 
+int32_t build_triple_levels(int64_t n, const int32_t *u, const int32_t *i, const int32_t *j, int32_t n_users, int32_t n_items,
+                            std::vector<int32_t> &order, std::vector<int32_t> &level_ptr, int64_t *max_chain) {
+    // the last level of every row: n_users + n_items words, which stay in cache
+    std::vector<int32_t> last_u((size_t)n_users, 0), last_i((size_t)n_items, 0), level((size_t)n);
+    int32_t n_levels = 0;
+    for (int64_t s = 0; s < n; ++s) {
+        int32_t &lu = last_u[(size_t)u[s]], &li = last_i[(size_t)i[s]], &lj = last_i[(size_t)j[s]];
+        const int32_t lv = 1 + std::max(lu, std::max(li, lj));
+        lu = li = lj = lv;
+        level[(size_t)s] = lv;
+        n_levels = std::max(n_levels, lv);
+    }
+    level_ptr.assign((size_t)n_levels + 1, 0);
+    for (int64_t s = 0; s < n; ++s) ++level_ptr[(size_t)level[(size_t)s]];
+    for (int32_t l = 0; l < n_levels; ++l) level_ptr[(size_t)l + 1] += level_ptr[(size_t)l];
+    order.resize((size_t)n);
+    std::vector<int32_t> at(level_ptr.begin(), level_ptr.end() - (n_levels > 0 ? 1 : 0));
+    for (int64_t s = 0; s < n; ++s) order[(size_t)at[(size_t)level[(size_t)s] - 1]++] = (int32_t)s;
+    if (max_chain) {
+        std::vector<int64_t> cu((size_t)n_users, 0), ci((size_t)n_items, 0);
+        int64_t m = 0;
+        for (int64_t s = 0; s < n; ++s) {
+            m = std::max(m, ++cu[(size_t)u[s]]);
+            m = std::max(m, ++ci[(size_t)i[s]]);
+            if (j[s] != i[s]) m = std::max(m, ++ci[(size_t)j[s]]);
+        }
+        *max_chain = m;
+    }
+    return n_levels;
+}
+
 } // namespace cmi

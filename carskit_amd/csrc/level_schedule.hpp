@@ -72,4 +72,11 @@ int64_t build_narrow_runs(const std::vector<int64_t> &level_off, int64_t max_tup
 void build_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int max_block,
                                 std::vector<int32_t> &off);
 
+// BPR's triple schedule: the level of sample s is 1 + the largest level of an earlier sample that touched P[u], Q[i] or Q[j], so the
+// samples of a level are pairwise row-disjoint and the levels in sequence give the sequential result.  order: the samples sorted by
+// level (counting sort: ascending inside a level); level_ptr: n_levels + 1 offsets into order.  max_chain: the largest number of
+// samples that touch one row (a lower bound of the number of levels).  Returns the number of levels.
+int32_t build_triple_levels(int64_t n, const int32_t *u, const int32_t *i, const int32_t *j, int32_t n_users, int32_t n_items,
+                            std::vector<int32_t> &order, std::vector<int32_t> &level_ptr, int64_t *max_chain = nullptr);
+
 } // namespace cmi

@@ -760,6 +760,62 @@ int cmi_rankals_last_iter_ms(cmi_rankals_handle h, float ms[5]);
  * tested directly.  n > 64 -> CMI_E_UNSUPPORTED */
 int cmi_rankals_invert(cmi_rankals_handle h, int n_mats, int n, const double *A, double *out);
 
+/* ---- BPR (src/carskit/alg/baseline/ranking/BPR.java; bpr_api.cpp, bpr_kernels.hip, java_math.hpp) -------------------------------------
+ * Bayesian personalised ranking on the 2-D train matrix, fp64, bit-exact against the reference with Math.exp / Math.log defined as
+ * StrictMath's (fdlibm).  Every iteration draws n_users * 100 triples (u, i, j) from one java.util.Random stream -- on the device by
+ * speculation at every stream position and list ranking, or by the sequential host walk, which defines the sampler and takes over
+ * whenever the device form's reservation, draw cap or memory does not suffice -- and applies them in the reference's order by
+ * levels of row-disjoint samples.  1 <= k <= 128.  No CPU fallback: without a device cmi_bpr_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_bpr_instance *cmi_bpr_handle;
+#define CMI_BPR_FLAG_STRICT 0x1u       /* the loss as one chain in (sample, term) order: the reference's sum bit for bit (small data) */
+#define CMI_BPR_FLAG_HOST_SAMPLER 0x2u /* every iteration's triples by the host walk */
+#define CMI_BPR_FLAG_MIN_SLACK 0x4u    /* reserve 3 draws a sample and no more: three redraws or more in an iteration send it to the host walk (tests) */
+int cmi_bpr_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_bpr_handle *out);
+int cmi_bpr_destroy(cmi_bpr_handle h);
+const char *cmi_bpr_last_error(cmi_bpr_handle h);
+/* the 2-D train matrix as n cells (zero-valued cells take no part, as in train.row(u)); a duplicate (u, i) or an id out of range ->
+ * CMI_E_INVALID; a user whose row holds every item (the reference would draw j for ever), or no user with a cell -> CMI_E_INVALID */
+int cmi_bpr_set_ratings(cmi_bpr_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+int cmi_bpr_set_model(cmi_bpr_handle h, const double *P, const double *Q);
+int cmi_bpr_get_model(cmi_bpr_handle h, double *P, double *Q);
+/* the 48-bit state of the java.util.Random stream the sampler draws from (a seed's state is (seed ^ 0x5DEECE66D) & (2^48 - 1)): the
+ * driver's fold splitter and BPR share one stream */
+int cmi_bpr_set_random_state(cmi_bpr_handle h, int64_t state);
+int cmi_bpr_get_random_state(cmi_bpr_handle h, int64_t *state);
+/* one iteration's n_users * 100 triples from the handle's stream state, which stays as it is; on_device: the device form (falling
+ * back as cmi_bpr_iterate does), else the host walk.  *state_after: the state after the last consumed draw */
+int cmi_bpr_sample(cmi_bpr_handle h, int on_device, int32_t *u, int32_t *i, int32_t *j, int64_t *state_after);
+/* BPR.java:59-103: one iteration (sample, level build, epoch, loss); the stream state moves on.  NaN/Inf loss -> CMI_E_NUMERIC with
+ * *loss set */
+int cmi_bpr_iterate(cmi_bpr_handle h, double lrate, double regU, double regI, double *loss);
+int cmi_bpr_predict_batch(cmi_bpr_handle h, int64_t n, const int32_t *u, const int32_t *j, double *out);
+/* arguments, outputs and semantics exactly as cmi_slim_eval_rankings above */
+int cmi_bpr_eval_rankings(cmi_bpr_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                          const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx, const double *sr,
+                          double bin_thold, int num_recs, int num_ignore, int strategy, double out[21], int64_t *n_queries,
+                          int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items, double *top_scores);
+/* of the last cmi_bpr_iterate: ms[0] the sampler, ms[1] the level build (host), ms[2] the epoch, ms[3] the loss (0 before an
+ * iteration); ms[4] the last cmi_bpr_eval_rankings.  Before both -> CMI_E_INVALID */
+int cmi_bpr_last_iter_ms(cmi_bpr_handle h, float ms[5]);
+/* of the last cmi_bpr_iterate: out[0] levels, out[1] levels launched alone, out[2] runs of narrow levels, out[3] the widest level;
+ * out[4] the iterations and samplings so far that asked for the device form and were sampled by the host walk (the list left the
+ * reservation, met an overflow, or the reservation could not be allocated); a handle created with CMI_BPR_FLAG_HOST_SAMPLER never
+ * counts: its device form is switched off, nothing falls back */
+int cmi_bpr_last_schedule(cmi_bpr_handle h, int64_t out[5]);
+/* without a device or a handle: the level schedule of n triples (order: n sample ids sorted by level; level_of: n levels, 1-based);
+ * *n_levels, *max_chain (the most samples on one row) */
+int cmi_bpr_levels(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const int32_t *j, int32_t *order,
+                   int32_t *level_of, int32_t *n_levels, int64_t *max_chain);
+/* without a device or a handle: the host walk over n_samples samples of the n cells' matrix from *state, which moves on */
+int cmi_bpr_sample_host(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const double *r, int64_t *state,
+                        int64_t n_samples, int32_t *ou, int32_t *oi, int32_t *oj);
+/* stream positions per ranking block of the device sampler */
+int cmi_bpr_rank_block(void);
+/* probes of java_math.hpp: n values of java.util.Random.nextInt(bound) from *state, which moves on; StrictMath.exp and log of n
+ * arguments.  on_device: by the device's functions (nextInt at every position by jump-ahead, the list walked on the host) */
+int cmi_java_next_ints(int64_t *state, int32_t bound, int64_t n, int32_t *out, int on_device);
+int cmi_java_exp_log(int64_t n, const double *x, double *exp_out, double *log_out, int on_device);
+
 #ifdef __cplusplus
 }
 #endif
