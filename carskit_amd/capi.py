@@ -233,6 +233,21 @@ SYMBOLS = [
     ("cmi_bpr_rank_block", C.c_int, []),
     ("cmi_java_next_ints", C.c_int, [C.POINTER(_i64), _i32, _i64, _vp, C.c_int]),
     ("cmi_java_exp_log", C.c_int, [_i64, _vp, _vp, _vp, C.c_int]),
+    ("cmi_lrmf_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_lrmf_destroy", C.c_int, [_vp]),
+    ("cmi_lrmf_last_error", C.c_char_p, [_vp]),
+    ("cmi_lrmf_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_lrmf_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_lrmf_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_lrmf_iterate", C.c_int, [_vp, _dbl, _dbl, _dbl, C.POINTER(_dbl)]),
+    ("cmi_lrmf_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_lrmf_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                         C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_lrmf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_lrmf_last_schedule", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("cmi_lrmf_levels", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
+    ("cmi_lrmf_lds_rows", C.c_int, [C.c_int]),
+    ("cmi_lrmf_block", C.c_int, []),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -1344,3 +1359,76 @@ class BPRInstance(_FactorModel):
         out = (_i64 * 5)()
         self._chk(self.L.cmi_bpr_last_schedule(self.h, out))
         return dict(zip(("levels", "alone", "runs", "widest", "sampler_fallbacks"), (int(x) for x in out)))
+
+
+LRMF_FLAG_STRICT, LRMF_FLAG_GLOBAL_ROWS = 0x1, 0x2
+
+
+def lrmf_lds_rows(k):
+    """Host-only: the most cells of a unit that keeps its item rows in LDS at k factors"""
+    return int(lib().cmi_lrmf_lds_rows(int(k)))
+
+
+def lrmf_block():
+    """Host-only: the threads of an LRMF workgroup, the item lanes of one pass of a cell's sum"""
+    return int(lib().cmi_lrmf_block())
+
+
+def lrmf_levels(n_users, n_items, u, i):
+    """Host-only: LRMF's unit schedule of the cells: (order, level_of, n_levels, max_chain); order holds the users that store a cell"""
+    u = np.ascontiguousarray(u, dtype=np.int32)
+    i = np.ascontiguousarray(i, dtype=np.int32)
+    order, level_of = np.empty(max(int(n_users), 1), np.int32), np.zeros(max(int(n_users), 1), np.int32)
+    nl, chain = _i32(), _i64()
+    rc = lib().cmi_lrmf_levels(int(n_users), int(n_items), len(u), _p(u), _p(i), _p(order), _p(level_of), C.byref(nl), C.byref(chain))
+    if rc != OK:
+        raise CmiError(rc, (lib().cmi_lrmf_last_error(None) or b"cmi_lrmf_levels").decode())
+    level_of = level_of[:max(int(n_users), 0)]
+    return order[:int(np.count_nonzero(level_of))], level_of, nl.value, chain.value
+
+
+class LRMFInstance(_FactorModel):
+    """The reference's LRMF on one GPU (a `cmi_lrmf_handle`): P is (n_users, k), Q is (n_items, k), 1 <= k <= 128."""
+
+    _api = ("cmi_lrmf_create", "cmi_lrmf_destroy", "cmi_lrmf_last_error")
+    _prefix = "cmi_lrmf"
+
+    def set_model(self, P=None, Q=None):
+        P = self._shaped(P, (self.n_users, self.k), "P")
+        Q = self._shaped(Q, (self.n_items, self.k), "Q")
+        self._chk(self.L.cmi_lrmf_set_model(self.h, None if P is None else _p(P), None if Q is None else _p(Q)))
+
+    def model(self):
+        """(P, Q)"""
+        P, Q = np.empty((self.n_users, self.k)), np.empty((self.n_items, self.k))
+        self._chk(self.L.cmi_lrmf_get_model(self.h, _p(P), _p(Q)))
+        return P, Q
+
+    def iterate(self, lrate, reg_u, reg_i):
+        """one iteration of buildModel's loop (epoch, loss); returns the loss (NaN / Inf raises E_NUMERIC)"""
+        loss = _dbl()
+        self._chk(self.L.cmi_lrmf_iterate(self.h, float(lrate), float(reg_u), float(reg_i), C.byref(loss)))
+        return loss.value
+
+    def predict(self, u, j):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_lrmf_predict_batch(self.h, len(u), _p(u), _p(j), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_lrmf_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_iter_ms(self):
+        """(epoch, loss) device milliseconds of the last iterate() and the scoring loop of the last eval_rankings(); 0.0 for whichever
+        of the two has not run yet"""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.cmi_lrmf_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+    def last_schedule(self):
+        out = (_i64 * 5)()
+        self._chk(self.L.cmi_lrmf_last_schedule(self.h, out))
+        return dict(zip(("levels", "alone", "runs", "widest", "global_units"), (int(x) for x in out)))

@@ -158,6 +158,9 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
         // BPR: a top-N model on one GPU
         if (a == "bpr" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": BPR runs on one GPU");
+        // LRMF: a top-N model on one GPU
+        if (a == "lrmf" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": LRMF runs on one GPU");
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
@@ -192,8 +195,8 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     const std::string algoName = LineConfiger(cf.getString("recommender")).getMainParam();
     {   // the similarity-based CAMF recommenders are top-N models: their constructors switch the (static) isRankingPred on
         const std::string a = lower(algoName);
-        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals" || a == "bpr")
-            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61, BPR.java:42
+        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals" || a == "bpr" || a == "lrmf")
+            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61, BPR.java:42, LRMF.java:49
     }
     conf.bprStream = std::make_shared<int64_t>((int64_t)cmi::java_lcg_scramble(conf.randSeed));
     log("With Setup: " + cf.getString("evaluation.setup"));

@@ -985,6 +985,47 @@ class BPR : public PairRecommender<cmi_bpr_handle, cmi_bpr_destroy, cmi_bpr_last
     void predictBounded(double *) override { throw std::runtime_error("BPR is a top-N recommender: it has no rating evaluation"); }
 };
 
+// src/carskit/alg/baseline/ranking/LRMF.java: P and Q by list-wise gradient steps over every stored cell of the 2-D train matrix, for
+// top-N.  Parameters: num.factors, num.max.iter, learn.rate, reg.lambda -u -i.  The constructor sets the static isRankingPred = true
+// (LRMF.java:49) and initByNorm = false (:50); userExp (:55-67) is the library's (cmi_lrmf_set_ratings).
+class LRMF : public PairRecommender<cmi_lrmf_handle, cmi_lrmf_destroy, cmi_lrmf_last_error, cmi_lrmf_set_ratings> {
+  public:
+    LRMF(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("LRMF", tr, te, fold, c, log) {
+        conf_.isRankingPred = true;
+    }
+    // IterativeRecommender.java:239-245 with initByNorm = false: P.init(), Q.init() = Randoms.uniform() per cell, row by row
+    void initModel() override {
+        JavaRandom rnd(conf_.randSeed);
+        P.resize((size_t)trainMatrix.n_users * (size_t)conf_.numFactors);
+        Q.resize((size_t)trainMatrix.n_items * (size_t)conf_.numFactors);
+        for (double &x : P) x = rnd.nextDouble();
+        for (double &x : Q) x = rnd.nextDouble();
+    }
+    void buildModel() override { // LRMF.java:70-110
+        // the loss as the reference's one chain up to 2^18 terms, as BPR; else the fixed tree.  The 2-D matrix has at most as many
+        // cells as the train set has tuples
+        const bool small = (int64_t)trainMatrix.n() * (conf_.numFactors + 1) <= ((int64_t)1 << 18);
+        check(cmi_lrmf_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, small ? CMI_LRMF_FLAG_STRICT : 0u, &h_),
+              "cmi_lrmf_create");
+        setRatings("cmi_lrmf_set_ratings");
+        check(cmi_lrmf_set_model(h_, P.data(), Q.data()), "cmi_lrmf_set_model");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_lrmf_iterate(h_, lRate, conf_.regU, conf_.regI, &loss);
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_lrmf_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        check(cmi_lrmf_get_model(h_, P.data(), Q.data()), "cmi_lrmf_get_model");
+    }
+    Measures evalRankings() override { return evalRankingsWith(cmi_lrmf_eval_rankings, "cmi_lrmf_eval_rankings"); }
+    void saveModel() override { saveFactors(P, Q); }
+    std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
+
+  private:
+    void predictBounded(double *) override { throw std::runtime_error("LRMF is a top-N recommender: it has no rating evaluation"); }
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -1007,7 +1048,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
     if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
     if (n == "bpr") return std::unique_ptr<IterativeRecommender>(new BPR(tr, te, fold, c, log));
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, itemknn, userknn, slopeone, nmf)");
+    if (n == "lrmf") return std::unique_ptr<IterativeRecommender>(new LRMF(tr, te, fold, c, log));
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, lrmf, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -503,4 +503,36 @@ int32_t build_triple_levels(int64_t n, const int32_t *u, const int32_t *i, const
     return n_levels;
 }
 
+int32_t build_unit_levels(int32_t n_users, int32_t n_items, const int32_t *ptr, const int32_t *idx, std::vector<int32_t> &order,
+                          std::vector<int32_t> &level_ptr, std::vector<int32_t> *level_of, int64_t *max_chain) {
+    // the level of the last user that stores every column: n_items words
+    std::vector<int32_t> last((size_t)n_items, 0), level((size_t)n_users, 0);
+    int32_t n_levels = 0;
+    for (int32_t u = 0; u < n_users; ++u) {
+        if (ptr[u + 1] == ptr[u]) continue; // no cell: no unit
+        int32_t lv = 0;
+        for (int32_t c = ptr[u]; c < ptr[u + 1]; ++c) lv = std::max(lv, last[(size_t)idx[c]]);
+        ++lv;
+        for (int32_t c = ptr[u]; c < ptr[u + 1]; ++c) last[(size_t)idx[c]] = lv;
+        level[(size_t)u] = lv;
+        n_levels = std::max(n_levels, lv);
+    }
+    level_ptr.assign((size_t)n_levels + 1, 0);
+    for (int32_t u = 0; u < n_users; ++u)
+        if (level[(size_t)u]) ++level_ptr[(size_t)level[(size_t)u]];
+    for (int32_t l = 0; l < n_levels; ++l) level_ptr[(size_t)l + 1] += level_ptr[(size_t)l];
+    order.resize((size_t)(n_levels > 0 ? level_ptr[(size_t)n_levels] : 0));
+    std::vector<int32_t> at(level_ptr.begin(), level_ptr.end() - (n_levels > 0 ? 1 : 0));
+    for (int32_t u = 0; u < n_users; ++u)
+        if (level[(size_t)u]) order[(size_t)at[(size_t)level[(size_t)u] - 1]++] = u;
+    if (max_chain) {
+        std::fill(last.begin(), last.end(), 0); // now: the users that store every column
+        int64_t m = 0;
+        for (int32_t c = 0; c < ptr[n_users]; ++c) m = std::max<int64_t>(m, ++last[(size_t)idx[c]]);
+        *max_chain = m;
+    }
+    if (level_of) *level_of = std::move(level);
+    return n_levels;
+}
+
 } // namespace cmi

@@ -79,4 +79,12 @@ void build_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, i
 int32_t build_triple_levels(int64_t n, const int32_t *u, const int32_t *i, const int32_t *j, int32_t n_users, int32_t n_items,
                             std::vector<int32_t> &order, std::vector<int32_t> &level_ptr, int64_t *max_chain = nullptr);
 
+// LRMF's unit schedule.  A unit is one user's cells (ptr / idx: the train matrix by user, columns ascending, stored zeros included);
+// it reads and writes P[u] and Q[i] of every stored column i.  level(u) = 1 + the largest level among the last earlier users that store
+// one of its columns: the units of a level share no row and the levels in sequence give the sequential result.  order: the users with a
+// cell sorted by level (counting sort: ascending inside a level); level_ptr: n_levels + 1 offsets into order; level_of: per user, 1-based,
+// 0 without a cell; max_chain: the most users that store one column (a lower bound of the number of levels).  Returns the number of levels.
+int32_t build_unit_levels(int32_t n_users, int32_t n_items, const int32_t *ptr, const int32_t *idx, std::vector<int32_t> &order,
+                          std::vector<int32_t> &level_ptr, std::vector<int32_t> *level_of = nullptr, int64_t *max_chain = nullptr);
+
 } // namespace cmi

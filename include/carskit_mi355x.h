@@ -816,6 +816,50 @@ int cmi_bpr_rank_block(void);
 int cmi_java_next_ints(int64_t *state, int32_t bound, int64_t n, int32_t *out, int on_device);
 int cmi_java_exp_log(int64_t n, const double *x, double *exp_out, double *log_out, int on_device);
 
+/* ---- LRMF (src/carskit/alg/baseline/ranking/LRMF.java; lrmf_api.cpp, lrmf_host.hpp, lrmf_kernels.hip) -------------------------------
+ * List-wise matrix factorisation on the 2-D train matrix, fp64, bit-exact against the reference with Math.exp / Math.log defined as
+ * StrictMath's (fdlibm).  An iteration visits every stored cell (u, j, r) in the matrix iterator's order -- stored zeros included -- and
+ * recomputes uexp = sum_i exp(P[u] . Q[i]) over getColumns(u) -- stored zeros excluded -- for each.  A unit is one user's cells; one
+ * workgroup runs a unit with P[u] and the user's item rows in LDS (or, past cmi_lrmf_lds_rows(k) cells, the rows in memory), and the
+ * units run by levels that share no row.  1 <= k <= 128.  No CPU fallback: without a device cmi_lrmf_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_lrmf_instance *cmi_lrmf_handle;
+#define CMI_LRMF_FLAG_STRICT 0x1u      /* the loss as one chain in (cell, term) order: the reference's sum bit for bit (small data) */
+#define CMI_LRMF_FLAG_GLOBAL_ROWS 0x2u /* every unit leaves its item rows in memory (the form of a unit too large for LDS) */
+/* LRMF.java:46-53.  k > 128 -> CMI_E_UNSUPPORTED */
+int cmi_lrmf_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_lrmf_handle *out);
+int cmi_lrmf_destroy(cmi_lrmf_handle h);
+const char *cmi_lrmf_last_error(cmi_lrmf_handle h);
+/* the 2-D train matrix as n cells, zero-valued cells among them; a duplicate (u, i) or an id out of range -> CMI_E_INVALID.
+ * LRMF.java:55-67 (userExp) and the model-independent part of :70-110: A = Math.exp(r) / userExp[u] per cell by the host's fdlibm exp,
+ * the unit schedule.  A user whose only cells are stored zeros is accepted: its uexp is 0.0 and the iteration reports CMI_E_NUMERIC */
+int cmi_lrmf_set_ratings(cmi_lrmf_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* IterativeRecommender.java:239-245 (initByNorm = false): the caller draws P (n_users x k) and Q (n_items x k); NULL keeps one */
+int cmi_lrmf_set_model(cmi_lrmf_handle h, const double *P, const double *Q);
+int cmi_lrmf_get_model(cmi_lrmf_handle h, double *P, double *Q);
+/* LRMF.java:74-104: one iteration (the epoch, then the loss).  NaN/Inf loss -> CMI_E_NUMERIC with *loss set */
+int cmi_lrmf_iterate(cmi_lrmf_handle h, double lrate, double regU, double regI, double *loss);
+/* IterativeRecommender.predict(u, j) = DenseMatrix.rowMult(P, u, Q, j) */
+int cmi_lrmf_predict_batch(cmi_lrmf_handle h, int64_t n, const int32_t *u, const int32_t *j, double *out);
+/* Recommender.java:630-860; arguments, outputs and semantics exactly as cmi_slim_eval_rankings above */
+int cmi_lrmf_eval_rankings(cmi_lrmf_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                           const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx, const double *sr,
+                           double bin_thold, int num_recs, int num_ignore, int strategy, double out[21], int64_t *n_queries,
+                           int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items, double *top_scores);
+/* device time by events: ms[0] the epoch and ms[1] the loss of the last cmi_lrmf_iterate (0 before an iteration); ms[2] the last
+ * cmi_lrmf_eval_rankings.  Before both -> CMI_E_INVALID */
+int cmi_lrmf_last_iter_ms(cmi_lrmf_handle h, float ms[3]);
+/* of the matrix set: out[0] levels, out[1] levels launched alone (several units, a workgroup each), out[2] runs of consecutive
+ * single-unit levels (one workgroup each), out[3] the widest level, out[4] the units that run in the global form */
+int cmi_lrmf_last_schedule(cmi_lrmf_handle h, int64_t out[5]);
+/* without a device or a handle: the unit schedule of n cells (order: the users that store a cell sorted by level, at most n_users
+ * of them; level_of: n_users levels, 1-based, 0 for a user without a cell); *n_levels, *max_chain (the most users on one column) */
+int cmi_lrmf_levels(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, int32_t *order, int32_t *level_of,
+                    int32_t *n_levels, int64_t *max_chain);
+/* the most cells of a unit that keeps its item rows in LDS at k factors, from the kernel's LDS use (0: k out of range); the threads
+ * of its workgroup (the item lanes of one pass of a cell's sum) */
+int cmi_lrmf_lds_rows(int k);
+int cmi_lrmf_block(void);
+
 #ifdef __cplusplus
 }
 #endif
