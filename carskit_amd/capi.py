@@ -248,6 +248,26 @@ SYMBOLS = [
     ("cmi_lrmf_levels", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i32), C.POINTER(_i64)]),
     ("cmi_lrmf_lds_rows", C.c_int, [C.c_int]),
     ("cmi_lrmf_block", C.c_int, []),
+    ("cmi_ranksgd_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_ranksgd_destroy", C.c_int, [_vp]),
+    ("cmi_ranksgd_last_error", C.c_char_p, [_vp]),
+    ("cmi_ranksgd_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_ranksgd_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_ranksgd_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_ranksgd_set_random_state", C.c_int, [_vp, _i64]),
+    ("cmi_ranksgd_get_random_state", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("cmi_ranksgd_sample", C.c_int, [_vp, C.c_int, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    ("cmi_ranksgd_iterate", C.c_int, [_vp, _dbl, C.POINTER(_dbl)]),
+    ("cmi_ranksgd_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_ranksgd_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                            C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_ranksgd_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_ranksgd_last_schedule", C.c_int, [_vp, C.POINTER(_i64)]),
+    ("cmi_ranksgd_item_table", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, C.c_uint, _vp, _vp, C.POINTER(_i32)]),
+    ("cmi_ranksgd_tries", C.c_int, [_i64, _i32, _vp, _vp, _i64, _vp, C.c_int]),
+    ("cmi_ranksgd_assign_host", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64)]),
+    ("cmi_ranksgd_sample_host", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, C.c_uint, C.POINTER(_i64), _vp, _vp, _vp, _vp,
+                                          C.POINTER(_i64), C.POINTER(_i64)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -1359,6 +1379,126 @@ class BPRInstance(_FactorModel):
         out = (_i64 * 5)()
         self._chk(self.L.cmi_bpr_last_schedule(self.h, out))
         return dict(zip(("levels", "alone", "runs", "widest", "sampler_fallbacks"), (int(x) for x in out)))
+
+
+RANKSGD_FLAG_STRICT, RANKSGD_FLAG_HOST_SAMPLER, RANKSGD_FLAG_NUM_RATES_SIZE = 0x1, 0x2, 0x4
+
+
+def _ranksgd_chk(rc, fn):
+    if rc != OK:
+        raise CmiError(rc, (lib().cmi_ranksgd_last_error(None) or fn.encode()).decode())
+
+
+def _ranksgd_cells(u, i, r):
+    return (np.ascontiguousarray(u, dtype=np.int32), np.ascontiguousarray(i, dtype=np.int32), np.ascontiguousarray(r, dtype=np.float64))
+
+
+def ranksgd_item_table(n_users, n_items, u, i, r, flags=0):
+    """Host-only: RankSGD.java:66-75 of the cells' matrix: (the list's items, the running sums along it).  flags: 0 divides by the
+    reference's unassigned numRates (0), RANKSGD_FLAG_NUM_RATES_SIZE by the number of non-zero cells"""
+    u, i, r = _ranksgd_cells(u, i, r)
+    item, cum, n = np.empty(max(int(n_items), 1), np.int32), np.empty(max(int(n_items), 1)), _i32()
+    _ranksgd_chk(lib().cmi_ranksgd_item_table(int(n_users), int(n_items), len(r), _p(u), _p(i), _p(r), int(flags), _p(item), _p(cum),
+                                              C.byref(n)), "cmi_ranksgd_item_table")
+    return item[:n.value], cum[:n.value]
+
+
+def ranksgd_tries(state, item, cum, n, on_device=False):
+    """Host-only unless on_device: the item (or -1) of the n tries that start 0, 2, 4, ... draws after the 48-bit `state`"""
+    item, cum = np.ascontiguousarray(item, dtype=np.int32), np.ascontiguousarray(cum, dtype=np.float64)
+    out = np.empty(max(int(n), 1), np.int32)
+    _ranksgd_chk(lib().cmi_ranksgd_tries(int(state), len(item), _p(item), _p(cum), int(n), _p(out), 1 if on_device else 0),
+                 "cmi_ranksgd_tries")
+    return out[:int(n)]
+
+
+def ranksgd_assign_host(n_users, n_items, u, i, r, try_item):
+    """Host-only: RankSGD.java:85-112 with the tries given: (j per non-zero cell in cell order, tries consumed)"""
+    u, i, r = _ranksgd_cells(u, i, r)
+    tries = np.ascontiguousarray(try_item, dtype=np.int32)
+    j, used = np.empty(max(len(r), 1), np.int32), _i64()
+    _ranksgd_chk(lib().cmi_ranksgd_assign_host(int(n_users), int(n_items), len(r), _p(u), _p(i), _p(r), len(tries), _p(tries), _p(j),
+                                               C.byref(used)), "cmi_ranksgd_assign_host")
+    return j[:int(np.count_nonzero(r))], used.value
+
+
+def ranksgd_sample_host(n_users, n_items, u, i, r, state, flags=0):
+    """Host-only: one iteration's samples of the cells' matrix from the 48-bit `state`: (u, i, j, rui, state after, tries consumed)"""
+    u, i, r = _ranksgd_cells(u, i, r)
+    n = max(len(r), 1)
+    ou, oi, oj, orr = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n)
+    st, cells, used = _i64(int(state)), _i64(), _i64()
+    _ranksgd_chk(lib().cmi_ranksgd_sample_host(int(n_users), int(n_items), len(r), _p(u), _p(i), _p(r), int(flags), C.byref(st), _p(ou),
+                                               _p(oi), _p(oj), _p(orr), C.byref(cells), C.byref(used)), "cmi_ranksgd_sample_host")
+    c = cells.value
+    return ou[:c], oi[:c], oj[:c], orr[:c], st.value, used.value
+
+
+class RankSGDInstance(_FactorModel):
+    """The reference's RankSGD on one GPU (a `cmi_ranksgd_handle`): P is (n_users, k), Q is (n_items, k), 1 <= k <= 128."""
+
+    _api = ("cmi_ranksgd_create", "cmi_ranksgd_destroy", "cmi_ranksgd_last_error")
+    _prefix = "cmi_ranksgd"
+
+    def set_ratings(self, u, i, r):
+        super().set_ratings(u, i, r)
+        self.n_cells = int(np.count_nonzero(np.asarray(r, dtype=np.float64)))
+
+    def set_model(self, P=None, Q=None):
+        P = self._shaped(P, (self.n_users, self.k), "P")
+        Q = self._shaped(Q, (self.n_items, self.k), "Q")
+        self._chk(self.L.cmi_ranksgd_set_model(self.h, None if P is None else _p(P), None if Q is None else _p(Q)))
+
+    def model(self):
+        """(P, Q)"""
+        P, Q = np.empty((self.n_users, self.k)), np.empty((self.n_items, self.k))
+        self._chk(self.L.cmi_ranksgd_get_model(self.h, _p(P), _p(Q)))
+        return P, Q
+
+    def set_random_state(self, state):
+        self._chk(self.L.cmi_ranksgd_set_random_state(self.h, int(state)))
+
+    def random_state(self):
+        st = _i64()
+        self._chk(self.L.cmi_ranksgd_get_random_state(self.h, C.byref(st)))
+        return st.value
+
+    def sample(self, on_device=True, max_device_tries=0):
+        """one iteration's samples from the current stream state, which stays: (u, i, j, rui, state after)"""
+        n = max(getattr(self, "n_cells", 0), 1)
+        u, i, j, r, st = np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n, np.int32), np.empty(n), _i64()
+        self._chk(self.L.cmi_ranksgd_sample(self.h, 1 if on_device else 0, int(max_device_tries), _p(u), _p(i), _p(j), _p(r), C.byref(st)))
+        c = getattr(self, "n_cells", 0)
+        return u[:c], i[:c], j[:c], r[:c], st.value
+
+    def iterate(self, lrate):
+        """one iteration of buildModel's loop (tries, walk, level build, epoch, loss); returns the loss"""
+        loss = _dbl()
+        self._chk(self.L.cmi_ranksgd_iterate(self.h, float(lrate), C.byref(loss)))
+        return loss.value
+
+    def predict(self, u, j):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_ranksgd_predict_batch(self.h, len(u), _p(u), _p(j), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_ranksgd_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_iter_ms(self):
+        """(device tries, host walk, level build, epoch, loss) milliseconds of the last iterate() -- the first three host wall time, the
+        others device time -- and the scoring loop of the last eval_rankings()"""
+        ms = (C.c_float * 6)()
+        self._chk(self.L.cmi_ranksgd_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+    def last_schedule(self):
+        out = (_i64 * 5)()
+        self._chk(self.L.cmi_ranksgd_last_schedule(self.h, out))
+        return dict(zip(("levels", "alone", "runs", "widest", "host_tries"), (int(x) for x in out)))
 
 
 LRMF_FLAG_STRICT, LRMF_FLAG_GLOBAL_ROWS = 0x1, 0x2

@@ -316,20 +316,10 @@ static int bpr_iterate_impl(cmi_bpr_handle h, double lrate, double regU, double 
     CMI_HIP(h, hipMemcpyAsync(h->d_level_ptr, h->level_ptr.data(), h->level_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     CMI_HIP(h, hipEventRecord(h->ev[0], h->stream));
     // a level wider than one workgroup's samples on its own; a run of consecutive narrower levels in one launch of one workgroup
-    int64_t alone = 0, runs = 0, widest = 0;
-    for (int32_t l = 0; l < n_levels;) {
-        const int32_t w = h->level_ptr[(size_t)l + 1] - h->level_ptr[(size_t)l];
-        widest = std::max<int64_t>(widest, w);
-        if (w > BPR_WG_SAMPLES) {
-            CMI_HIP(h, bpr_launch_level(a, h->level_ptr[(size_t)l], h->level_ptr[(size_t)l + 1], h->stream));
-            ++alone, ++l;
-            continue;
-        }
-        int32_t e = l + 1;
-        while (e < n_levels && h->level_ptr[(size_t)e + 1] - h->level_ptr[(size_t)e] <= BPR_WG_SAMPLES) ++e;
-        CMI_HIP(h, bpr_launch_run(a, l, e, h->stream));
-        ++runs, l = e;
-    }
+    int64_t sched[4] = {0, 0, 0, 0};
+    CMI_HIP(h, launch_triple_levels(
+                   h->level_ptr, n_levels, BPR_WG_SAMPLES, [&](int32_t b0, int32_t b1) { return bpr_launch_level(a, b0, b1, h->stream); },
+                   [&](int32_t l0, int32_t l1) { return bpr_launch_run(a, l0, l1, h->stream); }, sched));
     CMI_HIP(h, hipEventRecord(h->ev[1], h->stream));
     CMI_HIP(h, bpr_launch_loss(h->d_slots, h->S * (int64_t)(h->k + 1), (h->flags & CMI_BPR_FLAG_STRICT) != 0, h->d_parts, h->d_loss, h->stream));
     CMI_HIP(h, hipEventRecord(h->ev[2], h->stream));
@@ -339,7 +329,7 @@ static int bpr_iterate_impl(cmi_bpr_handle h, double lrate, double regU, double 
     CMI_HIP(h, hipEventElapsedTime(&h->iter_ms[2], h->ev[0], h->ev[1]));
     CMI_HIP(h, hipEventElapsedTime(&h->iter_ms[3], h->ev[1], h->ev[2]));
     h->state = after;
-    h->sched[0] = n_levels, h->sched[1] = alone, h->sched[2] = runs, h->sched[3] = widest;
+    std::copy(sched, sched + 4, h->sched);
     h->iterated = true;
     if (loss) *loss = l;
     if (!std::isfinite(l)) CMI_FAIL(h, CMI_E_NUMERIC, "%s: loss = %g", fn, l);

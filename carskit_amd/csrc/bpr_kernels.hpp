@@ -2,7 +2,9 @@
 // the host sampler and the device sampler share.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
+#include <vector>
 
 #include "java_math.hpp"
 
@@ -91,6 +93,30 @@ struct BprEpoch {
 // (one workgroup, a barrier between levels).  begin / end: offsets into order of a level launched alone
 hipError_t bpr_launch_level(const BprEpoch &a, int32_t begin, int32_t end, hipStream_t s);
 hipError_t bpr_launch_run(const BprEpoch &a, int32_t l0, int32_t l1, hipStream_t s);
+// the launch list of a level schedule: a level wider than wg_samples on its own (level(begin, end): offsets into order), a run of
+// consecutive narrower levels in one launch of one workgroup (run(l0, l1)).  sched: levels, levels alone, runs, the widest level
+template <class Level, class Run>
+inline hipError_t launch_triple_levels(const std::vector<int32_t> &level_ptr, int32_t n_levels, int32_t wg_samples, Level &&level, Run &&run,
+                                       int64_t sched[4]) {
+    int64_t alone = 0, runs = 0, widest = 0;
+    for (int32_t l = 0; l < n_levels;) {
+        const int32_t w = level_ptr[(size_t)l + 1] - level_ptr[(size_t)l];
+        widest = std::max<int64_t>(widest, w);
+        if (w > wg_samples) {
+            if (hipError_t e = level(level_ptr[(size_t)l], level_ptr[(size_t)l + 1])) return e;
+            ++alone, ++l;
+            continue;
+        }
+        int32_t e = l + 1;
+        for (; e < n_levels && level_ptr[(size_t)e + 1] - level_ptr[(size_t)e] <= wg_samples; ++e)
+            widest = std::max<int64_t>(widest, level_ptr[(size_t)e + 1] - level_ptr[(size_t)e]);
+        if (hipError_t err = run(l, e)) return err;
+        ++runs, l = e;
+    }
+    sched[0] = n_levels, sched[1] = alone, sched[2] = runs, sched[3] = widest;
+    return hipSuccess;
+}
+
 // loss: strict = one chain over the n slots in order (the reference's sum bit for bit); else a fixed tree (parts: BPR_LOSS_PARTS doubles)
 hipError_t bpr_launch_loss(const double *slots, int64_t n, bool strict, double *parts, double *out, hipStream_t s);
 

@@ -161,6 +161,13 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
         // LRMF: a top-N model on one GPU
         if (a == "lrmf" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": LRMF runs on one GPU");
+        // RankSGD: a top-N model on one GPU; its constructor calls checkBinary() (RankSGD.java:58, Recommender.java:1154-1160)
+        if (a == "ranksgd" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": RankSGD runs on one GPU");
+        if (a == "ranksgd" && conf.binThold < 0) {
+            const std::string t = java_float_string((float)conf.binThold); // the "{}" of Logs.error: Float.toString
+            throw std::runtime_error("val.binary.threshold=" + t + ", ratings must be binarized first! Try set a non-negative value.");
+        }
     }
     if (iters_override > 0) conf.numIters = iters_override;
     // preset + readData
@@ -195,8 +202,8 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     const std::string algoName = LineConfiger(cf.getString("recommender")).getMainParam();
     {   // the similarity-based CAMF recommenders are top-N models: their constructors switch the (static) isRankingPred on
         const std::string a = lower(algoName);
-        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals" || a == "bpr" || a == "lrmf")
-            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61, BPR.java:42, LRMF.java:49
+        if (a == "camf_ics" || a == "camf_lcs" || a == "camf_mcs" || a == "slim" || a == "rankals" || a == "bpr" || a == "lrmf" || a == "ranksgd")
+            conf.isRankingPred = true; // SLIM.java:68, RankALS.java:61, BPR.java:42, LRMF.java:49, RankSGD.java:56
     }
     conf.bprStream = std::make_shared<int64_t>((int64_t)cmi::java_lcg_scramble(conf.randSeed));
     log("With Setup: " + cf.getString("evaluation.setup"));
@@ -226,8 +233,8 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
         int k = 0;
         const std::vector<int> labels = split_folds(data.n(), ev.getInt("-k", 5), conf.randSeed, &k);
         bool parallel = ev.isOn("-p", true); // one thread per fold (CARSKit.java:395-412); each fold = its own cmi_handle/stream
-        if (lower(algoName) == "bpr") {
-            // BPR draws its triples from happy.coding's static Randoms stream.  The splitter drew from it first, but the first
+        if (lower(algoName) == "bpr" || lower(algoName) == "ranksgd") {
+            // BPR draws its triples (and RankSGD its items, RankSGD.java:97) from happy.coding's static Randoms stream.  The splitter drew from it first, but the first
             // recommender's constructor then seeds it again (Recommender.java:194-234: resetStatics, set by CARSKit.java:150, makes
             // the constructor call Randoms.seed(--rand-seed), a new java.util.Random): fold 1 starts at the seed's state, which
             // conf.bprStream holds, and every later fold goes on where the one before stopped.  So the folds run in sequence, the

@@ -141,6 +141,9 @@ struct Conf {
     int slimKnn = 0;
     // RankALS=-sw on|off (RankALS.java:71: algoOptions.isOn("-sw")); without the RankALS key the reference's algoOptions is null
     bool rankalsSw = false, rankalsSet = false;
+    // RankSGD=-numrates size|reference: what RankSGD.java:71 divides by.  `reference` (and the absent key) is the reference as it stands:
+    // numRates is never assigned (Recommender.java:141), so the divisor is 0; `size` is the number of ratings of the 2-D train matrix
+    bool ranksgdNumRatesSize = false;
     std::shared_ptr<int64_t> bprStream; // BPR: the 48-bit state of happy.coding's Randoms stream, shared by the folds of a run (null: from randSeed)
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
@@ -201,6 +204,11 @@ struct Conf {
         if (cf.contains("RankALS")) {
             rankalsSet = true;
             rankalsSw = cf.getParamOptions("RankALS").isOn("-sw", false);
+        }
+        if (cf.contains("RankSGD")) {
+            const std::string v = lower(cf.getParamOptions("RankSGD").getString("-numrates", "reference"));
+            if (v != "size" && v != "reference") throw std::runtime_error("RankSGD=-numrates " + v + ": size or reference");
+            ranksgdNumRatesSize = v == "size";
         }
         if (cf.contains("FM")) {
             LineConfiger fm = cf.getParamOptions("FM");
@@ -1026,6 +1034,51 @@ class LRMF : public PairRecommender<cmi_lrmf_handle, cmi_lrmf_destroy, cmi_lrmf_
     void predictBounded(double *) override { throw std::runtime_error("LRMF is a top-N recommender: it has no rating evaluation"); }
 };
 
+// src/carskit/alg/baseline/ranking/RankSGD.java: P and Q by one stochastic gradient step per rated cell against an item drawn by
+// popularity, for top-N.  Parameters: num.factors, num.max.iter, learn.rate; RankSGD=-numrates size|reference (see Conf).  The
+// constructor sets the static isRankingPred = true (RankSGD.java:56) and calls checkBinary() (:58; the driver refuses there);
+// initByNorm stays true.  The draws come from happy.coding's static Randoms stream, as BPR's do: conf.bprStream.
+class RankSGD : public PairRecommender<cmi_ranksgd_handle, cmi_ranksgd_destroy, cmi_ranksgd_last_error, cmi_ranksgd_set_ratings> {
+  public:
+    RankSGD(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("RankSGD", tr, te, fold, c, log) {
+        conf_.isRankingPred = true;
+    }
+    // RankSGD.java:62-63: super.initModel() draws P and Q, gaussian (IterativeRecommender.java:235-241); the item list (:65-75) is the
+    // library's (cmi_ranksgd_set_ratings)
+    void initModel() override {
+        JavaRandom rnd(conf_.randSeed);
+        P.resize((size_t)trainMatrix.n_users * (size_t)conf_.numFactors);
+        Q.resize((size_t)trainMatrix.n_items * (size_t)conf_.numFactors);
+        for (double &x : P) x = 0.0 + 0.1 * rnd.nextGaussian();
+        for (double &x : Q) x = 0.0 + 0.1 * rnd.nextGaussian();
+    }
+    void buildModel() override { // RankSGD.java:79-141
+        // the loss as the reference's one chain up to 2^18 terms, as BPR; else the fixed tree
+        const bool small = (int64_t)trainMatrix.n() <= ((int64_t)1 << 18);
+        const unsigned flags = (small ? CMI_RANKSGD_FLAG_STRICT : 0u) | (conf_.ranksgdNumRatesSize ? CMI_RANKSGD_FLAG_NUM_RATES_SIZE : 0u);
+        check(cmi_ranksgd_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, flags, &h_), "cmi_ranksgd_create");
+        setRatings("cmi_ranksgd_set_ratings");
+        check(cmi_ranksgd_set_model(h_, P.data(), Q.data()), "cmi_ranksgd_set_model");
+        const int64_t start = conf_.bprStream ? *conf_.bprStream : (int64_t)cmi::java_lcg_scramble(conf_.randSeed);
+        check(cmi_ranksgd_set_random_state(h_, start), "cmi_ranksgd_set_random_state");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_ranksgd_iterate(h_, lRate, &loss);
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_ranksgd_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        if (conf_.bprStream) check(cmi_ranksgd_get_random_state(h_, conf_.bprStream.get()), "cmi_ranksgd_get_random_state");
+        check(cmi_ranksgd_get_model(h_, P.data(), Q.data()), "cmi_ranksgd_get_model");
+    }
+    Measures evalRankings() override { return evalRankingsWith(cmi_ranksgd_eval_rankings, "cmi_ranksgd_eval_rankings"); }
+    void saveModel() override { saveFactors(P, Q); }
+    std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
+
+  private:
+    void predictBounded(double *) override { throw std::runtime_error("RankSGD is a top-N recommender: it has no rating evaluation"); }
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -1049,7 +1102,8 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
     if (n == "bpr") return std::unique_ptr<IterativeRecommender>(new BPR(tr, te, fold, c, log));
     if (n == "lrmf") return std::unique_ptr<IterativeRecommender>(new LRMF(tr, te, fold, c, log));
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, lrmf, itemknn, userknn, slopeone, nmf)");
+    if (n == "ranksgd") return std::unique_ptr<IterativeRecommender>(new RankSGD(tr, te, fold, c, log));   // CARSKit.java:479-480
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, lrmf, ranksgd, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -159,6 +159,15 @@ struct JavaStream {
         }
         return r;
     }
+    // java.util.Random.nextDouble(): (((long) next(26) << 27) + next(27)) * 0x1.0p-53, two draws
+    CMI_JM_HD double nextDouble() {
+        state = (state * JAVA_LCG_A + JAVA_LCG_C) & JAVA_LCG_MASK;
+        const int64_t hi = (int64_t)(state >> 22);
+        state = (state * JAVA_LCG_A + JAVA_LCG_C) & JAVA_LCG_MASK;
+        const int64_t lo = (int64_t)(state >> 21);
+        used += 2;
+        return (double)((hi << 27) + lo) * 0x1.0p-53;
+    }
 };
 
 } // namespace cmi

@@ -860,6 +860,77 @@ int cmi_lrmf_levels(int n_users, int n_items, int64_t n, const int32_t *u, const
 int cmi_lrmf_lds_rows(int k);
 int cmi_lrmf_block(void);
 
+/* ---- RankSGD (src/carskit/alg/baseline/ranking/RankSGD.java; ranksgd_api.cpp, ranksgd_host.hpp, ranksgd_kernels.hip) ----------------
+ * Pairwise ranking SGD on the 2-D train matrix, fp64, bit-exact against the reference.  An iteration visits every non-zero cell (u, i,
+ * rui) in row order, draws an item j from the popularity list (RankSGD.java:66-75, :94-112) until !Ru.contains(j), and applies
+ * e = (pui - puj) - rui to P[u], Q[i], Q[j] (:113-132).  The tries of the draw are computed at every stream position on the device;
+ * the walk that assigns them to cells is sequential and stays on the host; the updates run in the reference's order by levels of
+ * row-disjoint samples.  1 <= k <= 128.  No CPU fallback: without a device cmi_ranksgd_create returns CMI_E_NO_DEVICE.
+ *
+ * numRates: Recommender.java:141 declares the field that RankSGD.java:71 divides by, and no file of the reference assigns it.  So by
+ * default the divisor is 0, as there: every item with a cell has probability +Infinity, the list is in java.util.HashMap iteration
+ * order and EVERY draw returns its first item; a matrix in which some user's row contains() that item is refused, because the
+ * reference would not end.  CMI_RANKSGD_FLAG_NUM_RATES_SIZE divides by the number of non-zero cells instead (LibRec's numRates =
+ * trainMatrix.size(), what the algorithm's description means): a popularity-weighted draw. */
+typedef struct cmi_ranksgd_instance *cmi_ranksgd_handle;
+#define CMI_RANKSGD_FLAG_STRICT 0x1u         /* the loss as one chain in cell order: the reference's sum bit for bit (small data) */
+#define CMI_RANKSGD_FLAG_HOST_SAMPLER 0x2u   /* every try by the host */
+#define CMI_RANKSGD_FLAG_NUM_RATES_SIZE 0x4u /* RankSGD.java:71 divides by the number of non-zero cells, not by the unassigned field */
+/* RankSGD.java:53-59.  k > 128 -> CMI_E_UNSUPPORTED */
+int cmi_ranksgd_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_ranksgd_handle *out);
+int cmi_ranksgd_destroy(cmi_ranksgd_handle h);
+const char *cmi_ranksgd_last_error(cmi_ranksgd_handle h);
+/* the 2-D train matrix as n cells (zero-valued cells take no part: not in columnSize(), rows() or row(u)) and RankSGD.java:62-76, the
+ * item list.  A duplicate (u, i), an id out of range, no non-zero cell, or a user whose row contains() every item a draw can return
+ * (the reference would draw for ever) -> CMI_E_INVALID; items that would treeify the HashMap, or more than 2^31-1 expected tries ->
+ * CMI_E_UNSUPPORTED */
+int cmi_ranksgd_set_ratings(cmi_ranksgd_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* IterativeRecommender.java:235-241 (initByNorm = true): the caller draws P (n_users x k) and Q (n_items x k); NULL keeps one */
+int cmi_ranksgd_set_model(cmi_ranksgd_handle h, const double *P, const double *Q);
+int cmi_ranksgd_get_model(cmi_ranksgd_handle h, double *P, double *Q);
+/* the 48-bit state of the java.util.Random stream that Randoms.random() draws from (RankSGD.java:97), as cmi_bpr_set_random_state */
+int cmi_ranksgd_set_random_state(cmi_ranksgd_handle h, int64_t state);
+int cmi_ranksgd_get_random_state(cmi_ranksgd_handle h, int64_t *state);
+/* RankSGD.java:85-112 of one iteration from the handle's stream state, which stays as it is: (u, i, j, rui) per non-zero cell in cell
+ * order (arrays of as many entries as non-zero cells were set).  on_device: the first max_device_tries tries (0: the handle's
+ * reservation) by the device, the rest by the host; else all by the host.  *state_after: the state after the last consumed draw */
+int cmi_ranksgd_sample(cmi_ranksgd_handle h, int on_device, int64_t max_device_tries, int32_t *u, int32_t *i, int32_t *j, double *r,
+                       int64_t *state_after);
+/* RankSGD.java:80-137: one iteration (tries, walk, level build, epoch, loss); the stream state moves on.  NaN/Inf loss, or no list
+ * entry reaching the random number on a cell's first try (:116 would predict(u, -1)) -> CMI_E_NUMERIC */
+int cmi_ranksgd_iterate(cmi_ranksgd_handle h, double lrate, double *loss);
+/* IterativeRecommender.predict(u, j) = DenseMatrix.rowMult(P, u, Q, j) */
+int cmi_ranksgd_predict_batch(cmi_ranksgd_handle h, int64_t n, const int32_t *u, const int32_t *j, double *out);
+/* Recommender.java:630-860; arguments, outputs and semantics exactly as cmi_slim_eval_rankings above */
+int cmi_ranksgd_eval_rankings(cmi_ranksgd_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                              const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
+                              const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy, double out[21],
+                              int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items,
+                              double *top_scores);
+/* of the last cmi_ranksgd_iterate: ms[0] the device tries and their copy (:97-107), ms[1] the host walk (:85-112), ms[2] the level
+ * build (host), ms[3] the epoch (:113-132), ms[4] the loss (0 before an iteration); ms[5] the last cmi_ranksgd_eval_rankings.  Before
+ * both -> CMI_E_INVALID */
+int cmi_ranksgd_last_iter_ms(cmi_ranksgd_handle h, float ms[6]);
+/* of the last cmi_ranksgd_iterate: out[0] levels, out[1] levels launched alone, out[2] runs of narrow levels, out[3] the widest level;
+ * out[4] the tries so far that the walk needed past the device's and the host supplied (a handle created with
+ * CMI_RANKSGD_FLAG_HOST_SAMPLER never counts) */
+int cmi_ranksgd_last_schedule(cmi_ranksgd_handle h, int64_t out[5]);
+/* without a device or a handle.  RankSGD.java:66-75 of the n cells' matrix: the list's keys and the running sums of :102 along it
+ * (n_items entries of room), *n_out entries.  flags: CMI_RANKSGD_FLAG_NUM_RATES_SIZE or 0 */
+int cmi_ranksgd_item_table(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const double *r, unsigned flags,
+                           int32_t *item_out, double *cum_out, int32_t *n_out);
+/* RankSGD.java:97-107: out[t], t < n <= 2^24: the item of the try that starts 2t draws after `state` over the given list, or -1 when
+ * no sum reaches the random number.  on_device: by the device's kernel (CMI_E_NO_DEVICE without one) */
+int cmi_ranksgd_tries(int64_t state, int32_t n_table, const int32_t *item, const double *cum, int64_t n, int32_t *out, int on_device);
+/* RankSGD.java:85-112 over the n cells' matrix with the tries given as an array: j per non-zero cell in cell order, *tries_used.
+ * -1 on a cell's first try -> CMI_E_NUMERIC; the array used up -> CMI_E_UNSUPPORTED */
+int cmi_ranksgd_assign_host(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const double *r, int64_t n_tries,
+                            const int32_t *try_item, int32_t *j_out, int64_t *tries_used);
+/* cmi_ranksgd_sample by the host alone, with cmi_ranksgd_set_ratings' refusals: outputs of n entries of room, *n_cells of them set;
+ * *state moves on */
+int cmi_ranksgd_sample_host(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const double *r, unsigned flags,
+                            int64_t *state, int32_t *ou, int32_t *oi, int32_t *oj, double *orr, int64_t *n_cells, int64_t *tries_used);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,358 @@
+"""RankSGD on the GPU: the golden runs of the reference through the C ABI (the reference as it stands, numRates unassigned, and the
+runs with numRates = size()), the device tries against the host's, the device and host samplers, the forced host continuation, the level
+epoch against tests/ranksgd_ref.py, the two loss forms, the top-N evaluation, the refusals and the driver."""
+import functools
+
+import numpy as np
+import pytest
+
+from carskit_amd import capi
+from tests import ranksgd_ref as rr
+from tests.test_bpr_capi_cpu import edge_cells, pow2_cells
+from tests.test_gpu_bpr import long_cells
+from tests.test_gpu_rankals import all_tuples, check_rankings, contextual_split
+from tests.test_ranksgd_capi_cpu import TABLES, cols, flags_of
+from tests.util import same_bits_exact
+
+pytestmark = pytest.mark.gpu
+
+RUNS = rr.golden_runs()
+LR = 0.05
+SIZE, STRICT, HOST = capi.RANKSGD_FLAG_NUM_RATES_SIZE, capi.RANKSGD_FLAG_STRICT, capi.RANKSGD_FLAG_HOST_SAMPLER
+
+
+def instance(k, nu, ni, cells, P=None, Q=None, flags=STRICT | SIZE, state=None):
+    h = capi.RankSGDInstance(k, nu, ni, flags=flags)
+    h.set_ratings(*cols(cells))
+    if P is not None:
+        h.set_model(P, Q)
+    if state is not None:
+        h.set_random_state(state)
+    return h
+
+
+@pytest.mark.parametrize("run", RUNS, ids=[r["name"] for r in RUNS])
+def test_golden_runs_match_the_reference_run(run):
+    nu, ni = run["n_users"], run["n_items"]
+    h = instance(run["k"], nu, ni, run["cells"], run["P0"], run["Q0"], flags=STRICT | flags_of(run), state=rr.random_state(run["seed"]))
+    nz = sorted(c for c in run["cells"] if c[2] != 0.0)
+    for n, it in enumerate(run["iters"]):
+        u, i, j, r, after = h.sample()                               # the iteration's samples; the stream state stays
+        assert list(zip(u.tolist(), i.tolist(), r.tolist())) == nz
+        assert j.tolist() == it["j"] and after == it["state"], n
+        loss = h.iterate(run["lrate"])
+        P, Q = h.model()
+        assert same_bits_exact(P, it["P"]), (n, np.argwhere(P != it["P"])[:5])
+        assert same_bits_exact(Q, it["Q"]), (n, np.argwhere(Q != it["Q"])[:5])
+        assert same_bits_exact([loss], [it["loss"]]), (n, loss, it["loss"])
+        assert h.random_state() == it["state"]
+    ms = h.last_iter_ms()
+    assert len(ms) == 6 and all(x >= 0.0 for x in ms) and sum(ms[:5]) > 0.0
+    assert h.last_schedule()["host_tries"] == 0
+    h.close()
+
+
+@pytest.mark.parametrize("name", sorted(TABLES))
+def test_device_tries_equal_the_host(name):
+    """5 000 tries from a start state: the positions cross workgroups (256 lanes) and 2t crosses 2^13"""
+    item, cum = TABLES[name]()
+    st = rr.random_state(20270320)
+    host = capi.ranksgd_tries(st, item, cum, 5000)
+    dev = capi.ranksgd_tries(st, item, cum, 5000, on_device=True)
+    assert np.array_equal(host, dev)
+    assert (-1 in dev.tolist()) == (name == "half")
+
+
+def sampled(h, on_device, max_device_tries=0):
+    u, i, j, r, st = h.sample(on_device=on_device, max_device_tries=max_device_tries)
+    return list(zip(u.tolist(), i.tolist(), j.tolist(), r.tolist())), st
+
+
+@pytest.mark.parametrize("make", [edge_cells, pow2_cells, long_cells], ids=["edge 37x60", "pow2 64x128", "700x300"])
+def test_device_and_host_sampler_agree(make):
+    nu, ni, cells = make()
+    st = rr.random_state(20270321)
+    h = instance(4, nu, ni, cells, flags=SIZE, state=st)
+    m = rr.RankSGD(nu, ni, cells, rr.NUM_RATES_SIZE)
+    rnd = rr.JavaStream(st)
+    for _ in range(2):                                               # two iterations' worth, on one continued stream
+        dev, dst = sampled(h, True)
+        host, hst = sampled(h, False)
+        want, _ = m.sample_iteration(rnd)
+        assert dev == host == want and dst == hst == rnd.state
+        h.set_random_state(hst)
+    if make is edge_cells:                                            # an empty user, a stored-zero user, a one-entry user, and user 2,
+        users = {t[0] for t in host}                                 # who holds every item of the list but item 31
+        assert 0 not in users and 3 not in users and {1, 2} <= users
+        assert len(m.rows[2]) == 59 and sorted(set(m.items) - set(m.rows[2])) == [31]
+        assert any(t[0] == 2 and t[2] != 31 for t in host)           # contains() misses entries of the long row
+    h.close()
+
+
+def test_forced_host_continuation_gives_the_same_samples():
+    """max_device_tries = the number of cells: every rejection pushes the walk past the device's tries, which the host supplies"""
+    nu, ni, cells = pow2_cells()
+    st = rr.random_state(20270322)
+    h = instance(4, nu, ni, cells, flags=SIZE, state=st)
+    full, fst = sampled(h, True)
+    assert h.last_schedule()["host_tries"] == 0                      # the reservation sufficed
+    cut, cst = sampled(h, True, max_device_tries=len(full))
+    supplied = h.last_schedule()["host_tries"]
+    want, used = rr.RankSGD(nu, ni, cells, rr.NUM_RATES_SIZE).sample_iteration(rr.JavaStream(st))
+    assert cut == full == want and cst == fst
+    assert supplied == used - len(full) > 0
+    tiny, tst = sampled(h, True, max_device_tries=1)
+    assert tiny == full and tst == fst and h.last_schedule()["host_tries"] == supplied + used - 1
+    h.close()
+
+
+# ---- the epoch ----------------------------------------------------------------------------------------------------------------------
+EPOCH_STATE = rr.random_state(20270323)
+
+
+@functools.lru_cache(maxsize=None)
+def epoch_matrix():
+    """300 x 260, 650 cells.  A sample's level follows the longest chain through its three rows, and the cells run in user order, so
+    a level is wide only where rows are short and items spread out: four users in five hold one or two cells (the first levels are 23
+    and 26 samples wide: two workgroups).  Every fifth user holds four items below 200 and item 259, which is the fifth entry of a row
+    of five, where contains() misses it: item 259 is popular (60 of 650 cells), is accepted as j for those users, j == i among them,
+    and threads a chain of narrow levels through the epoch.  Users 7, 67, ... are empty; (7, 3) is a stored zero"""
+    rng = np.random.default_rng(20270325)
+    cells = []
+    for u in range(300):
+        if u % 60 == 7:
+            continue
+        if u % 5 == 0:
+            js = rng.choice(200, size=4, replace=False).tolist() + [259]
+        else:
+            js = rng.choice(259, size=1 + u % 2, replace=False).tolist()
+        cells += [(u, int(j), float(rng.integers(3, 16)) / 3.0) for j in js]
+    cells.append((7, 3, 0.0))
+    return 300, 260, sorted(cells)
+
+
+@functools.lru_cache(maxsize=None)
+def epoch_samples():
+    """two iterations' samples of the 300 x 260 epoch matrix by the host sampler (equal to the restatement's: CPU tests)"""
+    nu, ni, cells = epoch_matrix()
+    out, st = [], EPOCH_STATE
+    for _ in range(2):
+        u, i, j, r, st, _ = capi.ranksgd_sample_host(nu, ni, *cols(cells), st, flags=SIZE)
+        out.append((list(zip(u.tolist(), i.tolist(), j.tolist(), r.tolist())), st))
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def epoch_reference(k):
+    """two iterations of the restatement on the 300 x 260 epoch matrix: per iteration (P, Q, strict loss, terms, state, samples)"""
+    nu, ni, _ = epoch_matrix()
+    rng = np.random.default_rng(20270324 + k)
+    P0, Q0 = 0.1 * rng.standard_normal((nu, k)), 0.1 * rng.standard_normal((ni, k))
+    P, Q = P0.copy(), Q0.copy()
+    out = []
+    for tri, after in epoch_samples():
+        loss, terms = rr.epoch_by_levels(P, Q, tri, LR)
+        out.append((P.copy(), Q.copy(), loss, terms, after, tri))
+    return P0, Q0, out
+
+
+def test_epoch_matrix_has_wide_levels_runs_and_a_sample_with_j_equal_i():
+    nu, ni, _ = epoch_matrix()
+    for tri, _ in epoch_samples():
+        widths = np.bincount(rr.levels(nu, ni, tri))[1:]
+        narrow = widths <= 16
+        assert np.any(~narrow) and np.any(narrow[1:] & narrow[:-1])
+    assert sum(t[1] == t[2] for tri, _ in epoch_samples() for t in tri) >= 1
+
+
+@pytest.mark.parametrize("k", [1, 16, 17, 128])
+def test_epoch_matches_the_restatement(k):
+    nu, ni, cells = epoch_matrix()
+    P0, Q0, ref = epoch_reference(k)
+    h = instance(k, nu, ni, cells, P0, Q0, state=EPOCH_STATE)
+    for n, (P, Q, loss, _, after, tri) in enumerate(ref):
+        got = h.iterate(LR)
+        gP, gQ = h.model()
+        assert same_bits_exact(gP, P), (n, np.argwhere(gP != P)[:5])
+        assert same_bits_exact(gQ, Q), (n, np.argwhere(gQ != Q)[:5])
+        assert same_bits_exact([got], [loss]), (n, got, loss)
+        assert h.random_state() == after
+        s = h.last_schedule()
+        widths = np.bincount(rr.levels(nu, ni, tri))[1:]
+        narrow = widths <= 16
+        assert s["levels"] == len(widths) and s["widest"] == widths.max()
+        assert s["alone"] == int(np.sum(~narrow)) >= 1
+        assert s["runs"] == int(np.sum(narrow[1:] & ~narrow[:-1]) + narrow[0]) >= 1
+    h.close()
+
+
+def test_default_loss_within_the_derived_bound_and_reproducible():
+    """the fixed tree against the strict chain: every term e * e is >= 0, so both lie within n * 2^-53 * loss of the exact sum (first
+    order) and within 2 * n * 2^-53 * loss of each other, n = the cells; the halving is exact.  Two identical runs give identical bits"""
+    k = 17
+    nu, ni, cells = epoch_matrix()
+    P0, Q0, ref = epoch_reference(k)
+    outs = []
+    for _ in range(2):
+        h = instance(k, nu, ni, cells, P0, Q0, flags=SIZE, state=EPOCH_STATE)
+        losses = [h.iterate(LR) for _ in range(2)]
+        outs.append((losses, h.model(), h.random_state()))
+        h.close()
+    (la, (Pa, Qa), sa), (lb, (Pb, Qb), sb) = outs
+    assert same_bits_exact(la, lb) and same_bits_exact(Pa, Pb) and same_bits_exact(Qa, Qb) and sa == sb
+    assert same_bits_exact(Pa, ref[1][0]) and same_bits_exact(Qa, ref[1][1]) and sa == ref[1][4]
+    for got, (_, _, strict, terms, _, _) in zip(la, ref):
+        n = len(terms)
+        assert np.all(terms >= 0.0)
+        print("default loss %r strict %r bound %r" % (got, strict, 2 * n * 2.0 ** -53 * strict))
+        assert abs(got - strict) <= 2 * n * 2.0 ** -53 * strict
+
+
+def test_host_sampler_flag_gives_the_same_run():
+    k = 16
+    nu, ni, cells = epoch_matrix()
+    P0, Q0, ref = epoch_reference(k)
+    h = instance(k, nu, ni, cells, P0, Q0, flags=STRICT | SIZE | HOST, state=EPOCH_STATE)
+    loss = h.iterate(LR)
+    P, Q = h.model()
+    assert same_bits_exact(P, ref[0][0]) and same_bits_exact(Q, ref[0][1]) and same_bits_exact([loss], [ref[0][2]])
+    assert h.random_state() == ref[0][4]
+    h.sample(on_device=True)                                         # the device form is switched off on this handle
+    assert h.last_schedule()["host_tries"] == 0                      # chosen, not supplied in the device's place
+    h.close()
+
+
+# ---- top-N and refusals ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name,seed", [("knn_matrix k=3 size", 11), ("knn_matrix k=10 size", 11), ("handmade k=2 size", 14)])
+def test_eval_rankings_on_golden_models(name, seed):
+    run = next(r for r in RUNS if r["name"] == name)
+    nu, ni = run["n_users"], run["n_items"]
+    P, Q = run["iters"][-1]["P"], run["iters"][-1]["Q"]
+    h = instance(run["k"], nu, ni, run["cells"], P, Q)
+    scores = rr.bpr_ref.scores(P.tolist(), Q.tolist())               # rowMult, one chain per cell
+    tu, tj = all_tuples(nu, ni)
+    assert same_bits_exact(h.predict(tu, tj).reshape(nu, ni), scores)
+    with pytest.raises(capi.CmiError) as e:
+        h.last_iter_ms()
+    assert e.value.code == capi.E_INVALID
+    train, test = contextual_split(run["cells"], 4, seed)
+    for kw in (dict(bin_thold=-1.0, num_recs=10), dict(bin_thold=-1.0, num_recs=5, strategy="uc"), dict(bin_thold=0.05, num_recs=10, num_ignore=3)):
+        check_rankings(h, scores, train, test, **kw)
+    ms = h.last_iter_ms()
+    assert ms[:5] == (0.0, 0.0, 0.0, 0.0, 0.0) and ms[5] > 0.0
+    h.close()
+
+
+def test_refusals():
+    h = capi.RankSGDInstance(4, 5, 6, flags=SIZE)
+    with pytest.raises(capi.CmiError) as e:
+        h.iterate(0.1)
+    assert e.value.code == capi.E_INVALID and "no ratings" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0, 0, 1], [0, 1, 1], [1.0, 1.0, 2.0])         # user 0 holds both items of the list
+    assert e.value.code == capi.E_INVALID and "user 0 holds every item a draw can return" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0], [1], [0.0])
+    assert e.value.code == capi.E_INVALID and "no non-zero cell" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0, 5], [0, 1], [1.0, 1.0])
+    assert e.value.code == capi.E_INVALID and "out of range" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_ratings([0, 0], [1, 1], [1.0, 2.0])
+    assert e.value.code == capi.E_INVALID and "duplicate" in str(e.value)
+    h.set_ratings([0, 1, 2], [0, 1, 0], [1.0, 2.0, 3.0])
+    with pytest.raises(capi.CmiError) as e:
+        h.iterate(0.1)
+    assert e.value.code == capi.E_INVALID and "no model" in str(e.value)
+    with pytest.raises(capi.CmiError) as e:
+        h.set_random_state(1 << 48)
+    assert e.value.code == capi.E_INVALID
+    with pytest.raises(capi.CmiError) as e:
+        h.predict([0], [0])
+    assert e.value.code == capi.E_INVALID
+    h.close()
+    ref = capi.RankSGDInstance(4, 5, 6)                              # the reference as it stands: every draw returns the list's first item
+    with pytest.raises(capi.CmiError) as e:
+        ref.set_ratings([0, 1, 2], [0, 1, 0], [1.0, 2.0, 3.0])
+    assert e.value.code == capi.E_INVALID and "never assigns numRates" in str(e.value) and "item 0" in str(e.value)
+    ref.close()
+
+
+# ---- the driver ------------------------------------------------------------------------------------------------------------------
+def _depaul_conf(tmp_path, extra):
+    import os
+    import shutil
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shutil.copyfile(os.path.join(root, "tests", "golden", "depaul_ratings_compact.csv"), tmp_path / "ratings.txt")
+    conf = open(os.path.join(root, "tests", "golden", "depaul_setting.conf")).read().replace("PLACEHOLDER_SET_BY_TEST", str(tmp_path / "ratings.txt"))
+    assert "num.max.iter=100" in conf and "num.factors=10" in conf and "cv -k 5 -p off --rand-seed 1" in conf and "-threshold -1" in conf
+    assert "learn.rate=2e-2 -max -1 -bold-driver" in conf
+    conf = conf.replace("recommender=biasedmf", "recommender=ranksgd").replace("num.max.iter=100", "num.max.iter=3")
+    conf = conf.replace("-threshold -1", "-threshold 0").replace("-verbose off", "-verbose off --save-model").replace("-p off", "-p on")
+    (tmp_path / "ranksgd.conf").write_text(conf + "\n" + "\n".join(extra) + "\n")
+    return os.path.join(root, "carskit_amd", "bin", "carskit-mi355x"), str(tmp_path / "ranksgd.conf")
+
+
+def test_driver_follows_the_reference_and_refuses_depaul(tmp_path):
+    """without RankSGD=-numrates the divisor is the reference's unassigned numRates: every draw returns the list's first item, which
+    some user of every fold holds, so the reference would not end; the driver says so"""
+    import subprocess
+    exe, conf = _depaul_conf(tmp_path, [])
+    p = subprocess.run([exe, "-c", conf], capture_output=True, text=True, timeout=300)
+    assert "holds every item a draw can return" in p.stdout + p.stderr and "never assigns numRates" in p.stdout + p.stderr
+    assert "Final Results by RankSGD" not in p.stdout
+
+
+def test_driver_parity_depaul(tmp_path):
+    """cv -k 5 --rand-seed 1, num.max.iter = 3 with the bold driver and RankSGD=-numrates size.  As for BPR, fold 1 draws from the
+    seed's own state and folds 2..5 go on where the fold before stopped: the run equals the restatement over the same folds on that
+    stream; --save-model leaves the last fold's P and Q"""
+    import os
+    import re
+    import subprocess
+
+    from carskit_amd import dao
+    from oracle import oracle_np, rank_oracle
+    from tests.hostmirror import splitter
+    from tests.util import to2d
+
+    k, iters = 10, 3
+    exe, conf = _depaul_conf(tmp_path, ["RankSGD=-numrates size"])
+    p = subprocess.run([exe, "-c", conf, "--precise"], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr
+    m = re.search(r"PRECISE RankSGD folds=5 Pre10=(\S+) Rec10=(\S+) AUC10=(\S+) MAP10=(\S+) NDCG10=(\S+) MRR10=(\S+)", p.stdout)
+    assert m and "Final Results by RankSGD, Pre5: " in p.stdout, p.stdout[-500:]
+    dao.transform(str(tmp_path / "ratings.txt"), str(tmp_path / "train.csv"))
+    d = dao.DataDAO(str(tmp_path / "train.csv")).rating_data()
+    labels, nf = splitter.split_folds(d.n, 5, 1)
+    state = rr.random_state(1)
+    lr0 = float(np.float32(2e-2))
+    want = {}
+    for f in range(1, nf + 1):
+        tr, te = splitter.kth_fold(d, labels, f)
+        u, i, r = to2d(tr.u, tr.j, tr.r)
+        rnd = oracle_np.JavaRandom(1)                                # initByNorm = true: P.init(0.0, 0.1), then Q
+        P = np.array([0.0 + 0.1 * rnd.next_gaussian() for _ in range(d.n_users * k)]).reshape(d.n_users, k)
+        Q = np.array([0.0 + 0.1 * rnd.next_gaussian() for _ in range(d.n_items * k)]).reshape(d.n_items, k)
+        lrate, last_loss = lr0, 0.0
+        for it in range(1, iters + 1):
+            su, si, sj, sr, state, _ = capi.ranksgd_sample_host(d.n_users, d.n_items, u, i, r, state, flags=SIZE)
+            loss, _ = rr.epoch_by_levels(P, Q, list(zip(su.tolist(), si.tolist(), sj.tolist(), sr.tolist())), lrate)
+            assert abs(loss) >= 1e-5                                 # isConverged: not converged; then updateLRate's bold driver
+            if it > 1:
+                lrate = lrate * 1.05 if abs(last_loss) > abs(loss) else lrate * 0.5
+            last_loss = loss
+        scores = rr.bpr_ref.scores(P.tolist(), Q.tolist())
+        tup = lambda x: list(zip(x.u.tolist(), x.j.tolist(), x.ctx.tolist(), x.r.tolist()))  # noqa: E731
+        res, _ = rank_oracle.eval_rankings(lambda a, b, c: float(scores[a, b]), tup(tr), tup(te), bin_thold=0.0, num_recs=10)
+        for name in ("Pre10", "Rec10", "AUC10", "MAP10", "NDCG10", "MRR10"):
+            want[name] = want.get(name, 0.0) + res[name] / nf
+    for g, name in zip(m.groups(), ("Pre10", "Rec10", "AUC10", "MAP10", "NDCG10", "MRR10")):
+        print(name, g, want[name])
+        assert abs(float(g) - want[name]) <= 1e-12, (name, g, want[name])
+    saved = tmp_path / "CARSKit.Workspace" / "RankSGD" / ("model fold [%d].cmi" % nf)
+    assert saved.exists(), os.listdir(tmp_path / "CARSKit.Workspace")
+    pmf = capi.Instance("PMF", k, d.n_users, d.n_items, 0, flags=capi.FLAG_STATE_F64)
+    pmf.load_model(str(saved))
+    assert same_bits_exact(pmf.get_state("P").reshape(P.shape), P) and same_bits_exact(pmf.get_state("Q").reshape(Q.shape), Q)
+    pmf.close()
