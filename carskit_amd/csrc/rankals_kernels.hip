@@ -350,14 +350,15 @@ hipError_t rankals_launch_predict(const double *P, const double *Q, int k, int64
 }
 
 // A workgroup per (group of queries of one user, block of RANKALS_BLOCK candidates): the user's row of P in LDS, a lane per candidate with
-// its own chain over f, the score written to every query of the group inside [q0, q0 + nq).
+// its own chain over f, the score written to every query of the group inside [q0, q0 + nq).  BPR, LRMF and RankSGD fill their slabs with
+// it too, so the row has RANK_SCORE_MAX_K doubles, not RANKALS_MAX_K, and is staged by a strided loop that holds for any k up to that.
 __global__ __launch_bounds__(RANKALS_BLOCK) void rankals_score_kernel(const double *P, const double *Q, int k, const int32_t *cand, int nc,
                                                                       const int32_t *gu, const int32_t *gq0, int g0, int64_t q0, int64_t nq,
                                                                       double *S) {
-    __shared__ double s_p[RANKALS_MAX_K];
+    __shared__ double s_p[RANK_SCORE_MAX_K];
     const int g = g0 + (int)blockIdx.x;
     const int u = gu[g];
-    if ((int)threadIdx.x < k) s_p[threadIdx.x] = P[(int64_t)u * k + threadIdx.x];
+    for (int f = (int)threadIdx.x; f < k; f += RANKALS_BLOCK) s_p[f] = P[(int64_t)u * k + f];
     __syncthreads();
     const int c = (int)blockIdx.y * RANKALS_BLOCK + (int)threadIdx.x;
     if (c >= nc) return;
@@ -370,6 +371,7 @@ __global__ __launch_bounds__(RANKALS_BLOCK) void rankals_score_kernel(const doub
 
 hipError_t rankals_launch_score(const double *P, const double *Q, int k, const int32_t *cand, int nc, const int32_t *gu, const int32_t *gq0,
                                 int g0, int g1, int64_t q0, int64_t nq, double *S, hipStream_t s) {
+    if (k < 1 || k > RANK_SCORE_MAX_K) return hipErrorInvalidValue; // the row of P would not fit the kernel's LDS array
     if (g1 <= g0 || nc <= 0 || nq <= 0) return hipSuccess;
     const dim3 grid((unsigned)(g1 - g0), (unsigned)((nc + RANKALS_BLOCK - 1) / RANKALS_BLOCK));
     rankals_score_kernel<<<grid, dim3(RANKALS_BLOCK), 0, s>>>(P, Q, k, cand, nc, gu, gq0, g0, q0, nq, S);

@@ -12,6 +12,10 @@ constexpr int RANKALS_BLOCK = 256;  // threads per workgroup
 constexpr int RANKALS_CHUNK = 64;   // entries of a row or column staged per pass
 constexpr int RANKALS_TILE = 16;    // users or items per pass of the moment kernels
 constexpr int RANKALS_STAGE_MIN = 1024; // doubles of LDS at least in which a solve stages the rows of a chunk (I's room, before I exists)
+// the widest row of P rankals_launch_score takes: its kernel keeps the row in a static LDS array of this many doubles (1 KiB).  The other
+// factor models that fill their score slab with it (BPR, LRMF, RankSGD) assert their own k limit against it next to the call.
+constexpr int RANK_SCORE_MAX_K = 128;
+static_assert(RANKALS_MAX_K <= RANK_SCORE_MAX_K, "RankALS scores with rankals_launch_score: its row of P must fit the kernel's LDS row");
 
 // everything one iteration reads and writes, on the device
 struct RankAlsState {
@@ -42,7 +46,7 @@ hipError_t rankals_launch_invert(const double *A, double *out, int n_mats, int n
 hipError_t rankals_launch_predict(const double *P, const double *Q, int k, int64_t n, const int32_t *u, const int32_t *j, double *out,
                                   hipStream_t s);
 // the score slab of the queries [q0, q0 + nq) (rank_run_device_slab): S[(q - q0) * nc + c] = predict(gu[g], cand[c]) for every query of
-// group g inside the range
+// group g inside the range; hipErrorInvalidValue for k outside 1 .. RANK_SCORE_MAX_K
 hipError_t rankals_launch_score(const double *P, const double *Q, int k, const int32_t *cand, int nc, const int32_t *gu, const int32_t *gq0,
                                 int g0, int g1, int64_t q0, int64_t nq, double *S, hipStream_t s);
 

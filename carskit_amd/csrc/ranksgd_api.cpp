@@ -368,6 +368,7 @@ extern "C" int cmi_ranksgd_eval_rankings(cmi_ranksgd_handle h, int64_t n_train, 
         auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
             const RankSlabFn fill = [h](double *dS, const int32_t *dcand, int nc, const int32_t *dgu, const int32_t *dgq0, int g0, int g1,
                                         int64_t q0, int64_t nq, hipStream_t s) {
+                static_assert(BPR_MAX_K <= RANK_SCORE_MAX_K, "RankSGD scores with RankALS's kernel: its rows must fit that kernel's LDS row");
                 return rankals_launch_score(h->d_P, h->d_Q, h->k, dcand, nc, dgu, dgq0, g0, g1, q0, nq, dS, s);
             };
             return rank_run_device_slab(h->stream, h->rank_ws, plan, fill, bin_thold, num_recs, on_batch, &h->iter_ms[5]);

@@ -266,6 +266,7 @@ def test_host_sampler_flag_gives_the_same_run():
 
 
 # ---- top-N and refusals ---------------------------------------------------------------------------------------------------------------
+# (these golden models have k = 2, 3 and 10; the evaluation's k range up to 128 is held in tests/test_gpu_topn_score_edges.py)
 @pytest.mark.parametrize("name,seed", [("knn_matrix k=3", 11), ("knn_matrix k=10", 11), ("handmade k=2", 14)])
 def test_eval_rankings_on_golden_models(name, seed):
     run = next(r for r in RUNS if r["name"] == name)

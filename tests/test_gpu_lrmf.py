@@ -285,6 +285,7 @@ def test_predict_batch_equals_row_mult():
     h.close()
 
 
+# (these golden models have k = 3 and 10; the evaluation's k range up to 128 is held in tests/test_gpu_topn_score_edges.py)
 @pytest.mark.parametrize("name,seed", [("knn_matrix k=3", 11), ("knn_matrix k=10", 11)])
 def test_eval_rankings_on_golden_models(name, seed):
     run = next(r for r in RUNS if r["name"] == name)

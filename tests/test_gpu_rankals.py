@@ -284,20 +284,20 @@ def test_eval_rankings_on_golden_models(name, seed):
 
 
 @functools.lru_cache(maxsize=None)
-def score_model():
-    """8 users x 520 items at k = 10, drawn; user 7 has no train cell and a zero row: every score 0.0, ties in candidate order"""
+def score_model(k=10):
+    """8 users x 520 items at k factors, drawn; user 7 has no train cell and a zero row: every score 0.0, ties in candidate order"""
     rng = np.random.default_rng(20261110)
-    nu, ni, k = 8, 520, 10
+    nu, ni = 8, 520
     P, Q = rng.standard_normal((nu, k)), rng.standard_normal((ni, k))
     P[7] = 0.0
     return nu, ni, k, P, Q, rref.scores(P, Q)
 
 
-@pytest.mark.parametrize("n_cand,num_recs", [(63, 10), (64, 70), (65, 10), (513, 70), (513, 10)])
-def test_score_kernel_and_selection_edges(n_cand, num_recs):
-    """63, 64, 65 and 513 candidates (513: three blocks of the score kernel); lists of 10 (the streaming selection) and 70 (one pass per
-    rank); a user with four contexts whose exclusions differ; a user without a row"""
-    nu, ni, k, P, Q, scores = score_model()
+@functools.lru_cache(maxsize=None)
+def score_split(n_cand):
+    """(train, test, cells) over score_model()'s 8 x 520 matrix with n_cand candidates, the items of the training tuples: user 4 has
+    four contexts with a different exclusion set in each, user 7 no train cell; every case of one n_cand shares these arrays"""
+    nu, ni = 8, 520
     rng = np.random.default_rng(n_cand)
     cand = sorted(rng.choice(ni, n_cand, replace=False).tolist())
     tr, te = [], []
@@ -317,7 +317,16 @@ def test_score_kernel_and_selection_edges(n_cand, num_recs):
     test = tuple(np.array(x, dt) for x, dt in zip(zip(*sorted(set(te))), (np.int32, np.int32, np.int32, np.float64)))
     cells = sorted(set((u, j, 3.0) for u, j, _ in tr))
     assert not any(u == 7 for u, _, _ in cells)
-    h = instance(k, nu, ni, cells, P, Q)
+    return train, test, cells
+
+
+def check_score_kernel_and_selection_edges(factory, k, n_cand, num_recs):
+    """`factory(k, nu, ni, cells, P, Q)` returns a handle of a factor model whose predict is rowMult, with the cells and the model set
+    and no iteration run.  Its predict over all 8 x 520 cells and its evaluation of score_split(n_cand) (lists, score bits, measures,
+    whole and in batches of 3 queries) against the restatement's scores of score_model(k)."""
+    nu, ni, k, P, Q, scores = score_model(k)
+    train, test, cells = score_split(n_cand)
+    h = factory(k, nu, ni, cells, P, Q)
     tu, tj = all_tuples(nu, ni)
     assert same_bits_exact(h.predict(tu, tj).reshape(nu, ni), scores)
     lists = check_rankings(h, scores, train, test, bin_thold=-1e9, num_recs=num_recs)
@@ -331,6 +340,14 @@ def test_score_kernel_and_selection_edges(n_cand, num_recs):
     batched = with_env(lambda: h.eval_rankings(train, test, bin_thold=-1e9, num_recs=num_recs, with_lists=True), CMI_RANK_BATCH=3)
     assert batched[1] == lists                                     # batches that cut user 4's group: the same lists
     h.close()
+
+
+@pytest.mark.parametrize("n_cand,num_recs", [(63, 10), (64, 70), (65, 10), (513, 70), (513, 10)])
+def test_score_kernel_and_selection_edges(n_cand, num_recs):
+    """63, 64, 65 and 513 candidates (513: three blocks of the score kernel); lists of 10 (the streaming selection) and 70 (one pass per
+    rank); a user with four contexts whose exclusions differ; a user without a row.  The factor counts up to the kernel's limit, the
+    block border and the selection switch, for this model and the three that share the kernel: tests/test_gpu_topn_score_edges.py"""
+    check_score_kernel_and_selection_edges(instance, 10, n_cand, num_recs)
 
 
 def test_a_reused_handle_answers_like_a_fresh_one():
