@@ -816,6 +816,8 @@ hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan
     if (flops) *flops = 2.0 * (double)nq * (double)nc * (double)kp;
     f.units = nq, f.batch = bq;
     f.buffers = {{W::DB, up128(nc) * kp * sizeof(T)}, {W::DA, up128(bq) * kp * sizeof(T)}, {W::DS, (size_t)bq * (size_t)nc * sizeof(T)}, {W::DRC, (size_t)bq * sizeof(T)}};
+    const bool has_hot = ops.hot1 > ops.hot0;
+    if (has_hot) f.buffers.push_back({W::DHOT, ((size_t)nc + 1) * sizeof(int32_t)});
     f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DQU, plan.qu), plan_array(W::DQC, plan.qc), plan_array(W::DEXPTR, plan.excl_ptr),
                      plan_array(W::DEXCL, plan.excl_idx)};
     // This form uploads the plan's arrays on every evaluation, as it always did.  With the uploads skipped, one evaluation of every process
@@ -823,14 +825,19 @@ hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan
     // stream with no host-to-device copy in front of it; the split form, whose lists come back on its selection stream, has never shown
     // it (profiles/rank_driver_refactor_speed.json).  The tags are still set, so the split form finds resident what this form uploaded.
     f.upload_always = true;
-    f.prepare = [&] { return ops.build_items(ws.d<T>(W::DB), ws.d<int32_t>(W::DCAND), nc, kp, stream); };
+    f.prepare = [&] {
+        hipError_t e = ops.build_items(ws.d<T>(W::DB), ws.d<int32_t>(W::DCAND), nc, kp, stream);
+        if (e == hipSuccess && has_hot) e = rank_launch_list_nonfinite<T>(ws.d<T>(W::DB), nc, kp, RankHot{ops.hot0, ops.hot1, nullptr}, ws.d<int32_t>(W::DHOT), stream);
+        return e;
+    };
     f.enqueue = [&](size_t, int64_t q0, int64_t q1, RankBatch &r) {
         const int n = (int)(q1 - q0);
         r.q0 = q0, r.q1 = q1;
         hipError_t e = ops.build_queries(ws.d<T>(W::DA), ws.d<T>(W::DRC), ws.d<int32_t>(W::DQU) + q0, ws.d<int32_t>(W::DQC) + q0, n, kp, stream);
         if (e == hipSuccess)
             e = rank_launch_score<T>(ws.d<T>(W::DA), ws.d<T>(W::DB), ws.d<T>(W::DRC), ws.d<T>(W::DS), n, nc, kp, ws.d<int64_t>(W::DEXPTR), ws.d<int32_t>(W::DEXCL),
-                                     (int)q0, thold, topn, ws.d<int32_t>(W::DTOP), ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), stream);
+                                     (int)q0, thold, topn, ws.d<int32_t>(W::DTOP), ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), stream,
+                                     has_hot ? RankHot{ops.hot0, ops.hot1, ws.d<int32_t>(W::DHOT)} : RankHot());
         return e;
     };
     return rank_run_batches(stream, ws, plan, topn, f, on_batch, ms);
@@ -921,6 +928,7 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
     if (two && prune) f.buffers.push_back({W::DM1B, m_bytes});
     if (s2) f.buffers.insert(f.buffers.end(), {{W::DB2, up128(nc) * a.kp2 * 4}, {W::DA2, up128(n_dc) * a.kp2 * 4}, {W::DS2, (size_t)n_dc * (size_t)nc * 4 + RANK_SLAB_SLACK}});
     if (s2 && prune) f.buffers.push_back({W::DM2, (size_t)n_dc * nt64 * 4});
+    if (s2) f.buffers.push_back({W::DHOT, ((size_t)nc + 1) * sizeof(int32_t)});
     f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DQU, plan.qu), plan_array(W::DQC, plan.qc), plan_array(W::DQG, plan.qg),
                      plan_array(W::DGU, plan.gu), plan_array(W::DEXPTR, plan.excl_ptr), plan_array(W::DEXCL, plan.excl_idx)};
     if (s2) f.plan_arrays.insert(f.plan_arrays.end(), {plan_array(W::DDC, dctx), plan_array(W::DQD, qd)}); // (derived from the plan's qc)
@@ -937,12 +945,17 @@ hipError_t rank_run_device_split(hipStream_t stream, RankWorkspace &ws, const Ra
         a.A2 = ws.d<float>(W::DA2);
         a.rc = ws.d<float>(W::DRC);
         if (e == hipSuccess) e = rank_launch_split_operands(a, stream);
+        if (e == hipSuccess && s2) e = rank_launch_list_nonfinite<float>(a.B2, nc, a.kp2, RankHot{0, a.n_conds, nullptr}, ws.d<int32_t>(W::DHOT), stream);
         return e;
     };
-    // S2: once per evaluation (row constant = the zeroed scratch)
+    // S2: once per evaluation (row constant = the zeroed scratch).  Every column of its operands is one-hot: the scores that took a
+    // 0 * Inf term are computed again, and their tiles' maxima with them
     if (s2)
         f.start = [&] {
-            return rank_launch_gemm<float>(a.A2, a.B2, ws.d<float>(W::DSCR), ws.d<float>(W::DS2), n_dc, nc, a.kp2, stream, nullptr, prune ? ws.d<float>(W::DM2) : nullptr);
+            float *dS2 = ws.d<float>(W::DS2), *dscr = ws.d<float>(W::DSCR), *dM2 = prune ? ws.d<float>(W::DM2) : nullptr;
+            hipError_t e = rank_launch_gemm<float>(a.A2, a.B2, dscr, dS2, n_dc, nc, a.kp2, stream, nullptr, dM2);
+            if (e == hipSuccess) e = rank_launch_fix_onehot<float>(a.A2, a.B2, dscr, dS2, n_dc, nc, a.kp2, RankHot{0, a.n_conds, ws.d<int32_t>(W::DHOT)}, stream, dM2);
+            return e;
         };
     // (the contraction of batch b + 1 made to wait for the selection of batch b -- the kernels never side by side, only the lists' copies
     // overlapped -- measured the same 6.3 ms as the overlapped form: docs/history/r06.md 3)
@@ -1023,6 +1036,7 @@ template <typename T>
 static RankOperands<T> mf_operands(cmi_instance *h, int k_logical, bool contextual, bool ic_used) {
     RankOperands<T> ops;
     ops.k_logical = k_logical;
+    if (ic_used) ops.hot0 = h->k + 1, ops.hot1 = h->k + 1 + h->n_conds; // the one-hot of the context's conditions against the icBias row
     ops.build_items = [h](T *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
         RankItemsArgs<T> ia{(const T *)h->state[CMI_STATE_Q], (const T *)h->state[CMI_STATE_ITEM_BIAS],
                             (const T *)h->state[CMI_STATE_IC_BIAS], dcand, dB, nc, h->k, kp, h->n_conds};

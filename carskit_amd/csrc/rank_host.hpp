@@ -41,6 +41,7 @@ void rank_build_plan(int n_users, int n_items, const RankTuples &train, const Ra
 template <typename T>
 struct RankOperands {
     int k_logical; // un-padded operand length
+    int hot0 = 0, hot1 = 0; // its one-hot columns [hot0, hot1), the last of the k_logical (RankHot, rank_kernels.hpp); hot1 <= hot0: none
     std::function<hipError_t(T *dB, const int32_t *dcand, int nc, int kp, hipStream_t)> build_items;
     std::function<hipError_t(T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t)> build_queries;
 };
@@ -78,6 +79,7 @@ struct RankWorkspace {
         DCOLC,                                 // split form: itemBias of the candidates (the S1 contraction adds it at the end)
         DSB, DAB,                              // split form: the second slab / operand buffer (batch b + 1 is contracted while batch b is selected)
         DM1, DM1B, DM2,                        // split form: per-row maxima of S1 (per slab) / S2 over tiles of 64 candidates (the selection's tile pruning)
+        DHOT,                                  // the candidates whose one-hot columns hold an infinity or a NaN (RankHot::count_list)
         N_DEV
     };
     enum Pin { H_TOP, H_SCORE, H_COUNT, N_PIN }; // pinned host: the lists as they come back

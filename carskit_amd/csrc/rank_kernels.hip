@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <type_traits>
 
 #include "rank_kernels.hpp"
@@ -192,7 +193,8 @@ constexpr int RG_TPR = RG_BK / 4, RG_RPP = 256 / RG_TPR, RG_NP = RG_BM / RG_RPP;
 // Four independent maxima over lanes 0-31 (left in lanes 16-31) and lanes 32-63 (in lanes 48-63) at once: v_max_f32 with the DPP
 // operand on the instruction itself (row_ror 8 / 4 / 2 / 1: every lane of a 16-lane row holds the row's maximum; row_bcast:15 into
 // rows 1 and 3 adds the previous row's).  Written as one asm block because the compiler's fmaxf costs three instructions per step
-// (it quiets both operands first; the kernel runs in IEEE mode, where v_max_f32 already returns the non-NaN operand) -- 800
+// (it quiets both operands first; the kernel runs in IEEE mode, where v_max_f32 already returns the non-NaN operand -- and no NaN reaches
+// it: the epilogue's `val > m` never takes one; tests/test_gpu_rank_nonfinite.py runs NaN and infinite scores through it) -- 800
 // instructions per tile instead of 200.  The four chains are interleaved, so a result is read by its next DPP step three
 // instructions later (VALU write -> DPP read needs two wait states); s_nop 1 covers the values coming in.
 __device__ __forceinline__ void rg_max32x4(float &a, float &b, float &c, float &d) {
@@ -335,7 +337,7 @@ __global__ __launch_bounds__(256, CMI_RG_WAVES) void rank_gemm_mfma_f32(const fl
                         const float val = (col_const ? acc[i][j][r] + cc[j] : acc[i][j][r]) + rc;
                         if (FULL || (q < nq && c < nc)) {
                             S[(size_t)q * nc + c] = val;
-                            m[d] = val > m[d] ? val : m[d]; // (a NaN score is never taken: it cannot enter a list either)
+                            m[d] = val > m[d] ? val : m[d]; // (a NaN score is never taken: it cannot enter a list either; tests/test_gpu_rank_nonfinite.py)
                         }
                     }
                 }
@@ -372,6 +374,67 @@ __global__ __launch_bounds__(256) void rank_tile_max(const T *__restrict__ S, in
     if ((threadIdx.x & 63) == 0) tile_max[w] = m;
 }
 
+// ---- one-hot columns against entries that are no numbers --------------------------------------------------------------------------
+// The contraction multiplies EVERY column of a one-hot row: a context that does not hold condition f contributes 0 * icBias[j][f], and
+// that is a NaN when the entry is an infinity or a NaN.  The reference adds the entries of the context's own conditions only
+// (CAMF_CI.java, CAMF_CUCI.java: predict) and never reads the others: its score stays what the other terms make it.  A diverged model
+// has such entries in a few items' rows, so the contraction stays as it is and the few scores it got wrong are computed again:
+// rank_list_nonfinite_rows lists the candidates whose one-hot columns [hot0, hot1) of B hold an entry that is no number; for every
+// row of A and listed candidate whose score took a 0 * (no number) term, rank_fix_onehot redoes the k-ordered chain without the terms
+// of the one-hot columns that are zero in A -- the same operations in the same order as the contraction for every other term -- and
+// rank_fix_tile_max takes the maxima of the tiles that hold one of them again.
+// tests/test_gpu_rank_nonfinite.py holds this (contexts 2 and 3 of its models do not hold the planted condition).
+template <typename T>
+__device__ __forceinline__ bool rank_no_number(T v) { return !(v - v == (T)0); } // Inf - Inf and NaN - NaN are NaN
+
+template <typename T>
+__global__ __launch_bounds__(256) void rank_list_nonfinite_rows(const T *__restrict__ B, int nc, int kp, int hot0, int hot1, int32_t *count_list) {
+    const int c = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (c >= nc) return;
+    bool bad = false;
+    for (int f = hot0; f < hot1; ++f) bad |= rank_no_number(B[(size_t)c * kp + f]);
+    if (bad) count_list[1 + atomicAdd(count_list, 1)] = c; // (at most nc entries; their order does not matter)
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void rank_fix_onehot(const T *__restrict__ A, const T *__restrict__ B, const T *__restrict__ row_const,
+                                                       T *__restrict__ S, int nq, int nc, int kp, int hot0, int hot1,
+                                                       const int32_t *__restrict__ count_list) {
+    const int64_t n = count_list[0], total = n * (int64_t)nq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int q = (int)(i / n), c = count_list[1 + i % n];
+        const T *a = A + (size_t)q * kp, *b = B + (size_t)c * kp;
+        bool wrong = false;
+        for (int f = hot0; f < hot1; ++f) wrong |= a[f] == (T)0 && rank_no_number(b[f]);
+        if (!wrong) continue;
+        T acc = 0;
+        for (int f = 0; f < hot0; ++f) acc = fma(a[f], b[f], acc);
+        for (int f = hot0; f < hot1; ++f)
+            if (a[f] != (T)0) acc = fma(a[f], b[f], acc);
+        S[(size_t)q * nc + c] = acc + row_const[q]; // (the columns from hot1 on are the zero padding)
+    }
+}
+
+// the tile maxima of a slab that rank_fix_onehot has mended: a wave per (row, listed candidate) takes the maximum of the candidate's tile
+// again (several listed candidates of one tile write the same value)
+template <typename T>
+__global__ __launch_bounds__(256) void rank_fix_tile_max(const T *__restrict__ S, int nq, int nc, int nt64, T *__restrict__ tile_max,
+                                                         const int32_t *__restrict__ count_list) {
+    const int64_t n = count_list[0], total = n * (int64_t)nq;
+    const int lane = threadIdx.x & 63;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < total; i += (int64_t)gridDim.x * 4) {
+        const int q = (int)(i / n), t = count_list[1 + i % n] >> 6, c = t * 64 + lane;
+        T m = c < nc ? S[(size_t)q * nc + c] : (T)-INFINITY;
+        if (m != m) m = (T)-INFINITY; // as rank_tile_max and the contraction's epilogue: a NaN score is never taken
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            const T x = __shfl_xor(m, o, 64);
+            m = x > m ? x : m;
+        }
+        if (lane == 0) tile_max[(size_t)q * nt64 + t] = m;
+    }
+}
+
 // ---- exclusions: items the user already rated in this context (never candidates) -----------------------------------
 
 template <typename T>
@@ -397,7 +460,7 @@ __global__ __launch_bounds__(256) void rank_topn(T *S, int nq, int nc, double th
         int bi = 0x7fffffff;
         for (int c = lane; c < nc; c += 64) {
             const T v = row[c];
-            // candidates must satisfy `score > threshold` and not be NaN (Recommender.java:808-812)
+            // candidates must satisfy `score > threshold` and not be NaN (Recommender.java:808-812; tests/test_gpu_rank_nonfinite.py)
             if ((double)v > thold && (v > best || (v == best && c < bi))) {
                 best = v;
                 bi = c;
@@ -456,7 +519,8 @@ __global__ __launch_bounds__(256) void rank_topn_stream(const T *__restrict__ S,
         }
 #pragma unroll
         for (int u = 0; u < RT_U; ++u) {
-            // `score > threshold`, not NaN (Recommender.java:808-812); masked items are -inf
+            // `score > threshold`, not NaN (Recommender.java:808-812); masked items are -inf.  A list full of +Inf has t = +Inf and takes
+            // no later +Inf (tests/test_gpu_rank_nonfinite.py)
             unsigned long long m = __ballot((double)v[u] > thold && v[u] > -INFINITY && (count < topn || v[u] > t));
             while (m) {
                 const int l = __ffsll((long long)m) - 1;
@@ -557,7 +621,8 @@ __global__ __launch_bounds__(256) void rank_topn_split(const T *__restrict__ S1,
     T t = -INFINITY;
     // ONE comparison per score: `x > thr` with thr = tf while the list fills and the N-th best once it is full (every list entry is
     // > tf, so max(tf, t) = t) -- false for NaN, for masked / out-of-range entries (-inf) and for `score > threshold` failing
-    // (Recommender.java:808-812)
+    // (Recommender.java:808-812).  v = (n1 + n2) + c0 may be a NaN that is in neither slab (+Inf + -Inf): it fails like any other
+    // (tests/test_gpu_rank_nonfinite.py)
     T thr = tf;
     T n1[RT_U], n2[RT_U];
     auto request = [&](int base) {
@@ -633,8 +698,10 @@ __global__ __launch_bounds__(256) void rank_topn_split(const T *__restrict__ S1,
 // [64 t, 64 t + 64) (written by the contractions' epilogues).  ub = (M1 + M2) + c0 is an upper bound of every score of the tile in the
 // SAME floating-point operations as the score itself -- n1 <= M1 and n2 <= M2 give fl(n1 + n2) <= fl(M1 + M2), and adding c0 keeps
 // the order (rounding is monotone) -- so a tile with !(ub > thr) cannot contain a candidate that passes `v > thr` and is neither
-// loaded nor scanned.  thr only rises while a row is walked, tiles are still visited in ascending order, lanes in ascending order
-// inside a tile: the lists are those of rank_topn_split, entry for entry (tests/test_gpu_ranking.py compares the two forms bit for bit).
+// loaded nor scanned.  A NaN bound skips its tile too, and only tiles without a passing score have one: the maxima ignore NaN entries, so
+// ub is NaN only from opposite infinities among M1, M2 and c0 (or a NaN c0), and then every score of the tile is -Inf or NaN (DESIGN.md 5;
+// tests/test_nonfinite_scores.py checks it per query and tile, tests/test_gpu_rank_nonfinite.py the lists).
+// thr only rises while a row is walked, tiles are still visited in ascending order, lanes in ascending order inside a tile: the lists are those of rank_topn_split, entry for entry (tests/test_gpu_ranking.py compares the two forms bit for bit).
 // A top-10 list's threshold sits ~3.3 sigma out, a 64-candidate tile's maximum ~2.4: on the bench's data 60 % of the tiles are skipped.
 // Lane l of a chunk holds the bound of tile tb + l; the tiles that pass are fetched PU at a time (2 PU loads in flight, as before).
 // v of lane l for a WAVE-UNIFORM l (v_readlane with the lane number in an SGPR; __shfl goes through LDS)
@@ -787,11 +854,28 @@ hipError_t rank_launch_gemm(const T *A, const T *B, const T *row_const, T *S, in
     return hipGetLastError();
 }
 template <typename T>
+hipError_t rank_launch_list_nonfinite(const T *B, int nc, int kp, const RankHot &hot, int32_t *count_list, hipStream_t s) {
+    if (hipError_t e = hipMemsetAsync(count_list, 0, sizeof(int32_t), s)) return e;
+    if (nc <= 0 || hot.c1 <= hot.c0) return hipSuccess;
+    hipLaunchKernelGGL(rank_list_nonfinite_rows<T>, dim3((nc + 255) / 256), dim3(256), 0, s, B, nc, kp, hot.c0, hot.c1, count_list);
+    return hipGetLastError();
+}
+template <typename T>
+hipError_t rank_launch_fix_onehot(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp, const RankHot &hot, hipStream_t s, T *tile_max) {
+    if (nq <= 0 || nc <= 0 || !hot.count_list || hot.c1 <= hot.c0) return hipSuccess;
+    // fixed, small grids: with nothing listed (every model that has not diverged) each thread reads the count and returns
+    const dim3 grid((unsigned)std::min<int64_t>(1024, ((int64_t)nq + 3) / 4));
+    hipLaunchKernelGGL(rank_fix_onehot<T>, grid, dim3(256), 0, s, A, B, row_const, S, nq, nc, kp, hot.c0, hot.c1, hot.count_list);
+    if (tile_max) hipLaunchKernelGGL(rank_fix_tile_max<T>, grid, dim3(256), 0, s, (const T *)S, nq, nc, (nc + 63) / 64, tile_max, hot.count_list);
+    return hipGetLastError();
+}
+template <typename T>
 hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp,
                              const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
-                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s) {
+                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot) {
     if (nq <= 0 || nc <= 0) return hipSuccess;
     if (hipError_t e = rank_launch_gemm<T>(A, B, row_const, S, nq, nc, kp, s, nullptr, nullptr)) return e;
+    if (hipError_t e = rank_launch_fix_onehot<T>(A, B, row_const, S, nq, nc, kp, hot, s, nullptr)) return e;
     hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq);
     if (topn <= 64)
         hipLaunchKernelGGL(rank_topn_stream<T>, dim3((nq + 3) / 4), dim3(256), 0, s, (const T *)S, nq, nc, thold, topn, out_idx,
@@ -856,8 +940,10 @@ hipError_t rank_launch_split_select(const float *S1, const float *S2, const Rank
     template hipError_t rank_launch_build_items<T>(const RankItemsArgs<T> &, hipStream_t);                             \
     template hipError_t rank_launch_build_queries<T>(const RankQueryArgs<T> &, int, hipStream_t);                      \
     template hipError_t rank_launch_gemm<T>(const T *, const T *, const T *, T *, int, int, int, hipStream_t, const T *, T *);   \
+    template hipError_t rank_launch_list_nonfinite<T>(const T *, int, int, const RankHot &, int32_t *, hipStream_t);    \
+    template hipError_t rank_launch_fix_onehot<T>(const T *, const T *, const T *, T *, int, int, int, const RankHot &, hipStream_t, T *); \
     template hipError_t rank_launch_score<T>(const T *, const T *, const T *, T *, int, int, int, const int64_t *,     \
-                                             const int32_t *, int, double, int, int32_t *, double *, int32_t *, hipStream_t);
+                                             const int32_t *, int, double, int, int32_t *, double *, int32_t *, hipStream_t, const RankHot &);
 CMI_INST(float)
 CMI_INST(double)
 #undef CMI_INST

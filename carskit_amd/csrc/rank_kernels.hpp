@@ -44,11 +44,25 @@ template <typename T>
 hipError_t rank_launch_build_items(const RankItemsArgs<T> &a, hipStream_t s);
 template <typename T>
 hipError_t rank_launch_build_queries(const RankQueryArgs<T> &a, int nq, hipStream_t s);
-// S = A.B^T + row_const; mask the (q_base+q)-th exclusion list; top-N per row into out_*[(q_base+q)*topn + n]
+// One-hot columns [c0, c1) of the operands (the conditions of a query's context against the candidates' icBias rows; c1 <= c0: none).  A
+// zero of a one-hot row stands for a term the reference does not have, but 0 * Inf is a NaN: rank_launch_list_nonfinite lists the rows of
+// B whose one-hot columns hold an infinity or a NaN (count_list: [0] their number, then the rows; nc + 1 entries), and
+// rank_launch_fix_onehot computes again, without those terms, the scores of a finished contraction that took one, and the maxima of
+// their tiles if the contraction wrote tile maxima (rank_kernels.hip).
+struct RankHot {
+    int c0 = 0, c1 = 0;
+    const int32_t *count_list = nullptr;
+};
+template <typename T>
+hipError_t rank_launch_list_nonfinite(const T *B, int nc, int kp, const RankHot &hot, int32_t *count_list, hipStream_t s);
+template <typename T>
+hipError_t rank_launch_fix_onehot(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp, const RankHot &hot, hipStream_t s,
+                                  T *tile_max = nullptr);
+// S = A.B^T + row_const (one-hot terms as above); mask the (q_base+q)-th exclusion list; top-N per row into out_*[(q_base+q)*topn + n]
 template <typename T>
 hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp,
                              const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
-                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s);
+                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot = RankHot());
 
 // the exclusions masked and the top-N selected on a FINISHED slab S[nq][nc] (scores that are no contraction: SLIM): what
 // rank_launch_score does behind its contraction
