@@ -169,6 +169,10 @@ SYMBOLS = [
     ("cmi_knn_get_similarity", C.c_int, [_vp, C.c_int32, C.c_int32, _vp]),
     ("cmi_knn_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_knn_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_knn_ranking_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, _vp]),
+    ("cmi_knn_eval_rankings", C.c_int, [_vp, C.c_int, _dbl, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                        C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_knn_last_rank_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_slope_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
     ("cmi_slope_destroy", C.c_int, [_vp]),
     ("cmi_slope_last_error", C.c_char_p, [_vp]),
@@ -177,6 +181,9 @@ SYMBOLS = [
     ("cmi_slope_get_deviation", C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp]),
     ("cmi_slope_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, _dbl, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_slope_last_build_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_slope_eval_rankings", C.c_int, [_vp, _dbl, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                          C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_slope_last_rank_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_nmf_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
     ("cmi_nmf_destroy", C.c_int, [_vp]),
     ("cmi_nmf_last_error", C.c_char_p, [_vp]),
@@ -186,6 +193,9 @@ SYMBOLS = [
     ("cmi_nmf_iterate", C.c_int, [_vp, C.POINTER(_dbl)]),
     ("cmi_nmf_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, _dbl, _vp]),
     ("cmi_nmf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_topn_nmf_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                        C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_topn_nmf_last_rank_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
     ("cmi_slim_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
     ("cmi_slim_destroy", C.c_int, [_vp]),
     ("cmi_slim_last_error", C.c_char_p, [_vp]),
@@ -1035,6 +1045,18 @@ class _PairModel(_Handle):
         self._chk(self._fn("_last_build_ms")(self.h, C.byref(ms)))
         return ms.value
 
+    def _eval_rankings(self, lead, train, test, bin_thold, num_recs, num_ignore, strategy, with_lists):
+        """<prefix>_eval_rankings(h, *lead, <the arguments of cmi_slim_eval_rankings>) through the shared helper"""
+        fn = self._fn("_eval_rankings")
+        return _eval_rankings(lambda h, *rest: fn(h, *lead, *rest), self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_rank_ms(self):
+        """device milliseconds of the scoring and selection of the last eval_rankings()"""
+        ms = C.c_float()
+        self._chk(self._fn("_last_rank_ms")(self.h, C.byref(ms)))
+        return ms.value
+
 
 class KNNInstance(_PairModel):
     """The reference's ItemKNN (kind="item") or UserKNN (kind="user") on one GPU (a `cmi_knn_handle`)."""
@@ -1062,6 +1084,18 @@ class KNNInstance(_PairModel):
     def predict(self, u, j, knn, global_mean, bound=False, lo=1.0, hi=5.0):
         return self._predict(u, j, int(knn), global_mean=global_mean, bound=bound, lo=lo, hi=hi)
 
+    def ranking(self, u, j, knn, global_mean):
+        """Recommender.ranking(u, j): predict under isRankingPred (a neighbour needs a set, non-zero similarity of either sign), unbounded"""
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_knn_ranking_batch(self.h, len(u), _p(u), _p(j), int(knn), float(global_mean), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, knn, global_mean, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        """Recommender.evalRankings with ranking() as the scorer; keywords and return as SLIMInstance.eval_rankings"""
+        return self._eval_rankings((int(knn), float(global_mean)), train, test, bin_thold, num_recs, num_ignore, strategy, with_lists)
+
 
 class SlopeOneInstance(_PairModel):
     """The reference's SlopeOne on one GPU (a `cmi_slope_handle`)."""
@@ -1086,6 +1120,10 @@ class SlopeOneInstance(_PairModel):
 
     def predict(self, u, j, global_mean, bound=False, lo=1.0, hi=5.0):
         return self._predict(u, j, global_mean=global_mean, bound=bound, lo=lo, hi=hi)
+
+    def eval_rankings(self, train, test, global_mean, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        """Recommender.evalRankings with the unbounded predict as the scorer; keywords and return as SLIMInstance.eval_rankings"""
+        return self._eval_rankings((float(global_mean),), train, test, bin_thold, num_recs, num_ignore, strategy, with_lists)
 
 
 class _FactorModel(_PairModel):
@@ -1134,6 +1172,17 @@ class NMFInstance(_FactorModel):
         out = np.empty(len(u))
         self._chk(self.L.cmi_nmf_predict_batch(self.h, len(u), _p(u), _p(j), 1 if bound else 0, float(lo), float(hi), _p(out)))
         return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        """Recommender.evalRankings with the unbounded predict as the scorer (k <= 128); keywords and return as SLIMInstance.eval_rankings"""
+        return _eval_rankings(self.L.cmi_topn_nmf_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore,
+                              strategy, with_lists)
+
+    def last_rank_ms(self):
+        """device milliseconds of the scoring and selection of the last eval_rankings()"""
+        ms = C.c_float()
+        self._chk(self.L.cmi_topn_nmf_last_rank_ms(self.h, C.byref(ms)))
+        return ms.value
 
     def last_iter_ms(self):
         """(W phase, H phase, loss) device milliseconds of the last iterate()"""

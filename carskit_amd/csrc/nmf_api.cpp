@@ -12,6 +12,9 @@
 
 #include "nmf_kernels.hpp"
 #include "pair_host.hpp"
+#include "rank_host.hpp"
+#include "rank_kernels.hpp"
+#include "rankals_kernels.hpp"
 
 using namespace cmi;
 
@@ -28,6 +31,9 @@ struct cmi_nmf_instance : PairModelBase {
     bool have_model = false, iterated = false;
     hipEvent_t ev2 = nullptr, ev3 = nullptr;
     float iter_ms[3] = {0.f, 0.f, 0.f};
+    RankWorkspace rank_ws;
+    float rank_ms = 0.f; // scoring and selection of the last cmi_topn_nmf_eval_rankings
+    bool evaluated = false;
 };
 
 static thread_local std::string g_nmf_create_err;
@@ -43,6 +49,7 @@ static void nmf_free_all(cmi_nmf_instance *h) {
     nmf_free_ratings(h);
     abi_free(h->d_W, h->d_Ht);
     h->have_model = false;
+    h->rank_ws.release();
     if (h->ev2) (void)hipEventDestroy(h->ev2);
     if (h->ev3) (void)hipEventDestroy(h->ev3);
     h->ev2 = h->ev3 = nullptr;
@@ -206,6 +213,49 @@ extern "C" int cmi_nmf_predict_batch(cmi_nmf_handle h, int64_t n, const int32_t 
                                      double *out) {
     if (!h) return CMI_E_INVALID;
     return abi_barrier(h->err, "cmi_nmf_predict_batch", [&] { return nmf_predict_impl(h, n, u, j, bound, lo, hi, out); });
+}
+
+// NMF scores its slabs with rankals_launch_score, whose kernel keeps a row of W in an LDS array of RANK_SCORE_MAX_K doubles: the wider
+// models NMF trains (up to NMF_MAX_K) are refused by cmi_topn_nmf_eval_rankings
+static_assert(RANK_SCORE_MAX_K < NMF_MAX_K, "every k NMF trains fits rankals_launch_score: drop the refusal in cmi_topn_nmf_eval_rankings");
+
+// Recommender.evalRankings (Recommender.java:668-964) with ranking(u, j, c) = predict(u, j, c, false) (Recommender.java:1016-1018),
+// NMF.predict (NMF.java:142-145) = product(W, u, H, j) unbounded, as the scorer
+extern "C" int cmi_topn_nmf_eval_rankings(cmi_nmf_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx,
+                                     const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
+                                     const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy, double out[21],
+                                     int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items,
+                                     double *top_scores) {
+    if (!h) return CMI_E_INVALID;
+    return abi_barrier(h->err, "nmf_eval_rankings", [&] {
+        auto ready = [h]() -> int {
+            if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "nmf: call cmi_nmf_set_model first");
+            if (h->k > RANK_SCORE_MAX_K)
+                CMI_FAIL(h, CMI_E_UNSUPPORTED, "nmf_eval_rankings: k = %d: the scoring kernel keeps a user's row of W in LDS, k <= %d", h->k,
+                         RANK_SCORE_MAX_K);
+            CMI_HIP(h, hipSetDevice(h->device));
+            return CMI_OK;
+        };
+        auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
+            const RankSlabFn fill = [h](double *dS, const int32_t *dcand, int nc, const int32_t *dgu, const int32_t *dgq0, int g0, int g1,
+                                        int64_t q0, int64_t nq, hipStream_t s) {
+                return rankals_launch_score(h->d_W, h->d_Ht, h->k, dcand, nc, dgu, dgq0, g0, g1, q0, nq, dS, s);
+            };
+            return rank_run_device_slab(h->stream, h->rank_ws, plan, fill, bin_thold, num_recs, on_batch, &h->rank_ms);
+        };
+        const RankEvalIO io{{n_train, tu, tj, tctx, tr}, {n_test, su, sj, sctx, sr}, bin_thold, num_recs, num_ignore, strategy, out, n_queries,
+                            q_user, q_ctx, q_count, top_items, top_scores};
+        const int rc = rank_evaluate(h->err, "nmf_eval_rankings", h->rank_ws, h->n_users, h->n_items, INT64_MAX, io, ready, score);
+        if (rc == CMI_OK) h->evaluated = true;
+        return rc;
+    });
+}
+
+extern "C" int cmi_topn_nmf_last_rank_ms(cmi_nmf_handle h, float *ms) {
+    if (!h || !ms) return CMI_E_INVALID;
+    if (!h->evaluated) CMI_FAIL(h, CMI_E_INVALID, "cmi_topn_nmf_last_rank_ms: no evaluation yet");
+    *ms = h->rank_ms;
+    return CMI_OK;
 }
 
 extern "C" int cmi_nmf_last_iter_ms(cmi_nmf_handle h, float *ms) {

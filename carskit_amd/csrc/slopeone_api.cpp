@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pair_host.hpp"
+#include "rank_host.hpp"
 #include "slopeone_kernels.hpp"
 
 using namespace cmi;
@@ -17,6 +18,9 @@ struct cmi_slope_instance : PairModelBase {
     // cols: item -> (user, value), for the build; rows: user -> (item, value), for the prediction.  Both CSR, ascending.
     int32_t *d_cptr = nullptr, *d_cidx = nullptr, *d_rptr = nullptr, *d_ridx = nullptr, *d_card = nullptr;
     double *d_cval = nullptr, *d_rval = nullptr, *d_dev = nullptr;
+    RankWorkspace rank_ws;
+    float rank_ms = 0.f; // scoring and selection of the last cmi_slope_eval_rankings
+    bool evaluated = false;
 };
 
 static thread_local std::string g_slope_create_err;
@@ -28,7 +32,12 @@ static void slope_free_ratings(cmi_slope_instance *h) {
     h->have_ratings = h->built = false;
 }
 
-extern "C" int cmi_slope_destroy(cmi_slope_handle h) { return pair_destroy(h, slope_free_ratings); }
+static void slope_free_all(cmi_slope_instance *h) {
+    slope_free_ratings(h);
+    h->rank_ws.release();
+}
+
+extern "C" int cmi_slope_destroy(cmi_slope_handle h) { return pair_destroy(h, slope_free_all); }
 
 extern "C" int cmi_slope_create(int n_users, int n_items, int device, unsigned flags, cmi_slope_handle *out) {
     (void)flags;
@@ -112,6 +121,43 @@ extern "C" int cmi_slope_predict_batch(cmi_slope_handle h, int64_t n, const int3
                                        double lo, double hi, double *out) {
     if (!h) return CMI_E_INVALID;
     return abi_barrier(h->err, "cmi_slope_predict_batch", [&] { return slope_predict_impl(h, n, u, j, global_mean, bound, lo, hi, out); });
+}
+
+// Recommender.evalRankings (Recommender.java:668-964) with ranking(u, j, c) = predict(u, j, c, false) (Recommender.java:1016-1018),
+// SlopeOne.predict unbounded, as the scorer
+extern "C" int cmi_slope_eval_rankings(cmi_slope_handle h, double global_mean, int64_t n_train, const int32_t *tu, const int32_t *tj,
+                                       const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj,
+                                       const int32_t *sctx, const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy,
+                                       double out[21], int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count,
+                                       int32_t *top_items, double *top_scores) {
+    if (!h) return CMI_E_INVALID;
+    return abi_barrier(h->err, "slope_eval_rankings", [&] {
+        auto ready = [h]() -> int {
+            if (!h->built) CMI_FAIL(h, CMI_E_INVALID, "slope: call cmi_slope_set_ratings and cmi_slope_build first");
+            CMI_HIP(h, hipSetDevice(h->device));
+            return CMI_OK;
+        };
+        auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
+            const RankSlabFn fill = [h, global_mean](double *dS, const int32_t *dcand, int nc, const int32_t *dgu, const int32_t *dgq0, int g0,
+                                                     int g1, int64_t q0, int64_t nq, hipStream_t s) {
+                return slope_launch_score(PairCsr{h->d_rptr, h->d_ridx, h->d_rval}, h->d_dev, h->d_card, h->n_items, global_mean, dcand, nc,
+                                          dgu, dgq0, g0, g1, q0, nq, dS, s);
+            };
+            return rank_run_device_slab(h->stream, h->rank_ws, plan, fill, bin_thold, num_recs, on_batch, &h->rank_ms);
+        };
+        const RankEvalIO io{{n_train, tu, tj, tctx, tr}, {n_test, su, sj, sctx, sr}, bin_thold, num_recs, num_ignore, strategy, out, n_queries,
+                            q_user, q_ctx, q_count, top_items, top_scores};
+        const int rc = rank_evaluate(h->err, "slope_eval_rankings", h->rank_ws, h->n_users, h->n_items, INT64_MAX, io, ready, score);
+        if (rc == CMI_OK) h->evaluated = true;
+        return rc;
+    });
+}
+
+extern "C" int cmi_slope_last_rank_ms(cmi_slope_handle h, float *ms) {
+    if (!h || !ms) return CMI_E_INVALID;
+    if (!h->evaluated) CMI_FAIL(h, CMI_E_INVALID, "cmi_slope_last_rank_ms: no evaluation yet");
+    *ms = h->rank_ms;
+    return CMI_OK;
 }
 
 extern "C" int cmi_slope_last_build_ms(cmi_slope_handle h, float *ms) { return pair_last_build_ms(h, "cmi_slope_last_build_ms", ms); }

@@ -88,4 +88,56 @@ hipError_t slope_launch_predict(PairCsr rows, const double *dev, const int32_t *
     return hipGetLastError();
 }
 
+// ---- top-N scores --------------------------------------------------------------------------------------------------------------
+// ranking(u, j) = predict(u, j), unbounded (SlopeOne has no ranking branch).  A workgroup per (group of queries of one user, block of
+// SLOPE_SCORE_BLOCK candidates): the user's row is staged in LDS (a row longer than SLOPE_RTILE is read from global memory), a lane per
+// candidate walks it in ascending item order with slope_predict_kernel's chain, and the score goes to every query of the group inside
+// [q0, q0 + nq).
+template <class Idx, class Val>
+__device__ double slope_score_one(Idx idx, Val val, int len, const double *dj, const int32_t *cj, int j, double gm) {
+    double preds = 0.0, cards = 0.0;
+    for (int q = 0; q < len; ++q) {
+        const int i = idx[q];
+        const int32_t ci = cj[i];
+        if (i != j && ci > 0) { // train.row(u, j) leaves column j out
+            const double c = (double)ci;
+            preds += (dj[i] + val[q]) * c;
+            cards += c;
+        }
+    }
+    return cards > 0.0 ? preds / cards : gm;
+}
+
+__global__ __launch_bounds__(SLOPE_SCORE_BLOCK) void slope_score_kernel(PairCsr R, const double *dev, const int32_t *card, int n_items,
+                                                                        double gm, const int32_t *cand, int nc, const int32_t *gu,
+                                                                        const int32_t *gq0, int g0, int64_t q0, int64_t nq, double *S) {
+    __shared__ int32_t s_idx[SLOPE_RTILE];
+    __shared__ double s_val[SLOPE_RTILE];
+    const int g = g0 + (int)blockIdx.x;
+    const int u = gu[g];
+    const int r0 = R.ptr[u], len = R.ptr[u + 1] - r0;
+    const bool staged = len <= SLOPE_RTILE;
+    if (staged) {
+        for (int e = threadIdx.x; e < len; e += SLOPE_SCORE_BLOCK) s_idx[e] = R.idx[r0 + e], s_val[e] = R.val[r0 + e];
+        __syncthreads();
+    }
+    const int c = (int)blockIdx.y * SLOPE_SCORE_BLOCK + (int)threadIdx.x;
+    if (c >= nc) return;
+    const int j = cand[c];
+    const double *dj = dev + (int64_t)j * n_items;
+    const int32_t *cj = card + (int64_t)j * n_items;
+    const double pred = staged ? slope_score_one(s_idx, s_val, len, dj, cj, j, gm) : slope_score_one(R.idx + r0, R.val + r0, len, dj, cj, j, gm);
+    const int64_t qa = max((int64_t)gq0[g], q0), qb = min((int64_t)gq0[g + 1], q0 + nq);
+    for (int64_t q = qa; q < qb; ++q) S[(size_t)(q - q0) * (size_t)nc + (size_t)c] = pred;
+}
+
+hipError_t slope_launch_score(PairCsr rows, const double *dev, const int32_t *card, int n_items, double global_mean, const int32_t *cand,
+                              int nc, const int32_t *gu, const int32_t *gq0, int g0, int g1, int64_t q0, int64_t nq, double *S,
+                              hipStream_t s) {
+    if (g1 <= g0 || nc <= 0 || nq <= 0) return hipSuccess;
+    const dim3 grid((unsigned)(g1 - g0), (unsigned)((nc + SLOPE_SCORE_BLOCK - 1) / SLOPE_SCORE_BLOCK));
+    slope_score_kernel<<<grid, dim3(SLOPE_SCORE_BLOCK), 0, s>>>(rows, dev, card, n_items, global_mean, cand, nc, gu, gq0, g0, q0, nq, S);
+    return hipGetLastError();
+}
+
 } // namespace cmi

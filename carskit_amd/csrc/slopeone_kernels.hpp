@@ -16,5 +16,12 @@ hipError_t slope_launch_build(PairCsr cols, int n, double *dev, int32_t *card, h
 hipError_t slope_launch_predict(PairCsr rows, const double *dev, const int32_t *card, int n_items, int64_t n, const int32_t *u,
                                 const int32_t *j, double global_mean, int bound, double lo, double hi, double *out, int nwaves,
                                 hipStream_t s);
+// the candidates of a workgroup of slope_launch_score, and the entries of a user's row it stages in LDS (12 bytes each)
+constexpr int SLOPE_SCORE_BLOCK = 64, SLOPE_RTILE = 1024;
+// predict(gu[g], cand[c]), unbounded, of the groups g0 .. g1 -> S[(q - q0) * nc + c] for every query q of group g inside
+// [q0, q0 + nq): the fill of rank_run_device_slab
+hipError_t slope_launch_score(PairCsr rows, const double *dev, const int32_t *card, int n_items, double global_mean, const int32_t *cand,
+                              int nc, const int32_t *gu, const int32_t *gq0, int g0, int g1, int64_t q0, int64_t nq, double *S,
+                              hipStream_t s);
 
 } // namespace cmi

@@ -578,7 +578,7 @@ int cmi_owner_schedule(int64_t n, const int32_t *u, const int32_t *j, int32_t n_
                        int32_t *perm, int64_t *own_off, uint32_t *want, uint32_t *flags, int *hub_used);
 
 /* ---- ItemKNN / UserKNN (src/carskit/alg/baseline/cf/{ItemKNN,UserKNN}.java; knn_api.cpp, knn_kernels.hip) -------------------
- * Rating prediction of the two memory-based baselines over the 2-D train matrix (DataDAO.toTraditionalSparseMatrix: a (user, item)
+ * Rating prediction and top-N scores of the two memory-based baselines over the 2-D train matrix (DataDAO.toTraditionalSparseMatrix: a (user, item)
  * cell holds the mean of its ratings over contexts).  cmi_knn_build computes Recommender.buildCorrs on the device -- every pair
  * (a < b) of non-empty rows (UserKNN) or columns (ItemKNN), the reference's correlation() with its sums run sequentially in fp64 in
  * ascending order of the contracted index -- into a dense n x n fp64 matrix; NaN marks an unset entry (the diagonal, pairs with an
@@ -615,6 +615,27 @@ int cmi_knn_get_similarity(cmi_knn_handle h, int32_t row0, int32_t nrows, double
 int cmi_knn_predict_batch(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *j, int knn, double global_mean, int bound,
                           double lo, double hi, double *out);
 int cmi_knn_last_build_ms(cmi_knn_handle h, float *ms);
+/* Top-N (item.ranking=on).  Recommender.ranking(u, j, c) = predict(u, j, c, false) (Recommender.java:1016-1018): unbounded and
+ * context-free.  With isRankingPred set, ItemKNN.predict (ItemKNN.java:92-95) and UserKNN.predict (UserKNN.java:94-97) keep a neighbour
+ * on `rate > 0` alone, so negative similarities enter the map, the knn cut and the weighted sum.  The neighbours are the indices of
+ * corrs.row(target), and librec's SymmMatrix.row() leaves out the entries equal to zero (+0.0 and -0.0), so over the device matrix
+ * (NaN = unset) a neighbour is kept iff sim == sim && sim != 0.0 && rate > 0.  Everything after the filter is
+ * cmi_knn_predict_batch's: one device function with the keep rule as its parameter.
+ * cmi_knn_ranking_batch: ranking(u, j) of n tuples; the candidate limit as in cmi_knn_predict_batch; a tuple that would treeify a bin
+ * -> CMI_E_UNSUPPORTED, the message naming one such (user, item) */
+int cmi_knn_ranking_batch(cmi_knn_handle h, int64_t n, const int32_t *u, const int32_t *j, int knn, double global_mean, double *out);
+/* Recommender.evalRankings (Recommender.java:668-964) with that ranking(u, j) as the scorer, knn and global_mean as above: arguments,
+ * outputs and semantics exactly as cmi_slim_eval_rankings below.  The scores of a user are computed once and serve all of the user's
+ * contexts.  Before cmi_knn_build -> CMI_E_INVALID.  An owner list of the evaluation (ItemKNN: a query user's items, UserKNN: a
+ * candidate item's users) longer than CMI_KNN_MAX_CANDIDATES -> CMI_E_UNSUPPORTED before anything runs; a (user, item) that would
+ * treeify a bin -> CMI_E_UNSUPPORTED, the message naming one.  The driver (carskit-mi355x) still refuses item.ranking=on for itemknn,
+ * userknn, slopeone and nmf: this entry point and its Python binding are the public surface */
+int cmi_knn_eval_rankings(cmi_knn_handle h, int knn, double global_mean, int64_t n_train, const int32_t *tu, const int32_t *tj,
+                          const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx,
+                          const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy, double out[21],
+                          int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items, double *top_scores);
+/* device time by events of the scoring and selection of the last cmi_knn_eval_rankings; before one -> CMI_E_INVALID */
+int cmi_knn_last_rank_ms(cmi_knn_handle h, float *ms);
 
 /* ---- SlopeOne (src/carskit/alg/baseline/cf/SlopeOne.java; slopeone_api.cpp, slopeone_kernels.hip) ----------------------------
  * Rating prediction of the third memory-based baseline over the same 2-D train matrix as ItemKNN.  cmi_slope_build computes
@@ -638,6 +659,17 @@ int cmi_slope_get_deviation(cmi_slope_handle h, int32_t row0, int32_t nrows, dou
 int cmi_slope_predict_batch(cmi_slope_handle h, int64_t n, const int32_t *u, const int32_t *j, double global_mean, int bound,
                             double lo, double hi, double *out);
 int cmi_slope_last_build_ms(cmi_slope_handle h, float *ms);
+/* Recommender.evalRankings (Recommender.java:668-964) with ranking(u, j, c) = predict(u, j, c, false) (Recommender.java:1016-1018) as
+ * the scorer: SlopeOne.predict has no ranking branch, so the score is cmi_slope_predict_batch's without the bound.  Arguments, outputs
+ * and semantics exactly as cmi_slim_eval_rankings below; the scores of a user are computed once and serve all of the user's contexts.
+ * Before cmi_slope_build -> CMI_E_INVALID.  The driver still refuses item.ranking=on for slopeone (see cmi_knn_eval_rankings) */
+int cmi_slope_eval_rankings(cmi_slope_handle h, double global_mean, int64_t n_train, const int32_t *tu, const int32_t *tj,
+                            const int32_t *tctx, const double *tr, int64_t n_test, const int32_t *su, const int32_t *sj,
+                            const int32_t *sctx, const double *sr, double bin_thold, int num_recs, int num_ignore, int strategy,
+                            double out[21], int64_t *n_queries, int32_t *q_user, int32_t *q_ctx, int32_t *q_count, int32_t *top_items,
+                            double *top_scores);
+/* device time by events of the scoring and selection of the last cmi_slope_eval_rankings; before one -> CMI_E_INVALID */
+int cmi_slope_last_rank_ms(cmi_slope_handle h, float *ms);
 
 /* ---- NMF (src/carskit/alg/baseline/cf/NMF.java; nmf_api.cpp, nmf_kernels.hip) --------------------------------------------------
  * Lee & Seung's multiplicative updates over the 2-D train matrix V, fp64, bit-exact to the reference: every sum (product(W, u, H, j)
@@ -668,6 +700,19 @@ int cmi_nmf_predict_batch(cmi_nmf_handle h, int64_t n, const int32_t *u, const i
 /* device time of the last cmi_nmf_iterate, by events: ms[0] the W phase (NMF.java:72-89), ms[1] the H phase (:92-110), ms[2] the loss
  * (:113-126) */
 int cmi_nmf_last_iter_ms(cmi_nmf_handle h, float ms[3]);
+/* Top-N evaluation of NMF.  (The two names stand outside the cmi_nmf_ prefix: that prefix is the closed set of the training and
+ * rating-prediction ABI above.)
+ * Recommender.evalRankings (Recommender.java:668-964) with ranking(u, j, c) = predict(u, j, c, false) (Recommender.java:1016-1018) =
+ * product(W, u, H, j) (NMF.java:142-145) as the scorer.  Arguments, outputs and semantics exactly as cmi_slim_eval_rankings below; the
+ * scores of a user are computed once and serve all of the user's contexts.  Before cmi_nmf_set_model -> CMI_E_INVALID.  The scoring
+ * kernel keeps the user's row of W in LDS and takes k <= 128: a model of 129 <= k <= 256 -> CMI_E_UNSUPPORTED.  The driver still refuses
+ * item.ranking=on for nmf (see cmi_knn_eval_rankings) */
+int cmi_topn_nmf_eval_rankings(cmi_nmf_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx, const double *tr,
+                          int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
+                          int num_recs, int num_ignore, int strategy, double out[21], int64_t *n_queries, int32_t *q_user, int32_t *q_ctx,
+                          int32_t *q_count, int32_t *top_items, double *top_scores);
+/* device time by events of the scoring and selection of the last cmi_topn_nmf_eval_rankings; before one -> CMI_E_INVALID */
+int cmi_topn_nmf_last_rank_ms(cmi_nmf_handle h, float *ms);
 
 /* ---- SLIM (src/carskit/alg/baseline/ranking/SLIM.java; slim_api.cpp, slim_kernels.hip) -----------------------------------------
  * Ning & Karypis' sparse linear method for top-N over the 2-D train matrix, fp64, bit-exact to the reference: coordinate descent over
