@@ -17,6 +17,7 @@
 #include "mf_sgd_kernels.hpp"
 #include "sgd_device.hpp"
 
+#include <algorithm>
 #include <cmath>
 
 namespace cmi {
@@ -375,10 +376,19 @@ __global__ __launch_bounds__(256) void ext_eval_kernel(ExtEvalArgs<T> a, int64_t
 // ---------------------------------------------------------------------------------------------
 // operands of the ranking evaluation (rank_kernels.hip: score(q, j) = <a_q, b_j> + const_q)
 //   CAMF_ICS / LCS / MCS : predict = <P_u,Q_j> * s(c) with s the product of the context's similarities (or 1 - dist):
-//                          a_q = s(c) * P_u, b_j = Q_j, const = 0
+//                          a_q = s(c) * P_u, b_j = Q_j, const = 0.  An s(c) that is an infinity or a NaN is NOT folded in (it would make
+//                          Inf - Inf and 0 * Inf of a dot product the reference scales as a whole): a_q = P_u, row_scale[q] = s(c),
+//                          and rank_mask (rank_kernels.hip) multiplies the finished row before it masks it
 //   SVD++                : predict = gm + bu + bj + <Q_j, P_u + (sum_{k in N(u)} Y_k) / w>:
 //                          a_q = [P_u + ysum_u / w | 1], b_j = [Q_j | itemBias_j], const = gm + bu
 // ---------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ double seq_dot_f64(const T *a, const T *b, int k) {
+    double s = 0.0;
+    for (int f = 0; f < k; ++f) s += (double)a[f] * (double)b[f];
+    return s;
+}
+
 template <typename T>
 __global__ void ext_rank_items(ExtEvalArgs<T> a, const int32_t *cand, T *B, int kp) { // one block per candidate item
     const int j = cand[blockIdx.x];
@@ -392,7 +402,7 @@ __global__ void ext_rank_items(ExtEvalArgs<T> a, const int32_t *cand, T *B, int 
 }
 
 template <typename T>
-__global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int32_t *qc, T *A, T *row_const, int kp) { // one block per query
+__global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int32_t *qc, T *A, T *row_const, T *row_scale, int kp) { // one block per query
     const int u = qu[blockIdx.x], c = qc[blockIdx.x];
     T *dst = A + (size_t)blockIdx.x * kp;
     double scale = 1.0;
@@ -413,6 +423,7 @@ __global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int3
         }
         if (a.model == CAMF_MCS) scale = 1.0 - sqrt(dist);
     }
+    const bool late = !(scale - scale == 0.0); // an infinity or a NaN: applied to the finished row (SVD++: scale = 1, never)
     const int32_t ib = a.model == SVDPP ? a.ui_ptr[u] : 0, ie = a.model == SVDPP ? a.ui_ptr[u + 1] : 0;
     const double w = sqrt((double)(ie - ib));
     for (int f = threadIdx.x; f < kp; f += blockDim.x) {
@@ -423,7 +434,7 @@ __global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int3
                 double ys = 0.0;
                 for (int32_t q = ib; q < ie; ++q) ys += (double)a.Y[(size_t)a.ui_items[q] * a.k + f];
                 if (ie > ib) v += ys / w;
-            } else {
+            } else if (!late) {
                 v *= scale;
             }
         } else if (f == a.k && a.model == SVDPP) {
@@ -431,8 +442,44 @@ __global__ void ext_rank_queries(ExtEvalArgs<T> a, const int32_t *qu, const int3
         }
         dst[f] = (T)v;
     }
-    if (threadIdx.x == 0) row_const[blockIdx.x] = a.model == SVDPP ? (T)(a.io.gm + (double)a.userBias[u]) : (T)0;
+    if (threadIdx.x == 0) {
+        row_const[blockIdx.x] = a.model == SVDPP ? (T)(a.io.gm + (double)a.userBias[u]) : (T)0;
+        if (row_scale) row_scale[blockIdx.x] = late ? (T)scale : (T)1;
+    }
 }
+
+// SVD++ and a candidate whose Q row holds an infinity or a NaN.  The contraction gives it (P_u + ysum_u / w)[f] * Q_j[f]: an infinity by the
+// sign of the SUM.  The reference adds <P_u, Q_j> and then <Y_k, Q_j> / w item by item (SVDPlusPlus.java:138-146): P_u[f] * Inf and every
+// Y_k[f] * Inf are terms of their own, and the score is a NaN as soon as two of them differ in sign or one of the factors is 0.  Such a
+// score is never a number, so all there is to find is which of +Inf, -Inf and NaN it is: the reference's chain, for the listed candidates
+// (`listed`: [0] their number, then their positions; none in a model that has not diverged: every thread reads the count and returns).
+// tests/test_gpu_rank_nonfinite.py holds this.
+template <typename T>
+__global__ __launch_bounds__(256) void ext_rank_mend_svdpp(ExtEvalArgs<T> a, const int32_t *__restrict__ qu, const int32_t *__restrict__ cand,
+                                                           const int32_t *__restrict__ listed, T *__restrict__ S, int nq, int nc) {
+    const int64_t n = listed[0], total = n * (int64_t)nq;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int q = (int)(i / n), c = listed[1 + i % n];
+        const int u = qu[q], j = cand[c];
+        const T *qj = a.Q + (size_t)j * a.k;
+        double pred = ((a.io.gm + (double)a.userBias[u]) + (double)a.itemBias[j]) + seq_dot_f64(a.P + (size_t)u * a.k, qj, a.k);
+        const int32_t ib = a.ui_ptr[u], ie = a.ui_ptr[u + 1];
+        const double w = sqrt((double)(ie - ib));
+        for (int32_t r = ib; r < ie; ++r) pred += seq_dot_f64(a.Y + (size_t)a.ui_items[r] * a.k, qj, a.k) / w;
+        S[(size_t)q * nc + c] = (T)pred;
+    }
+}
+
+template <typename T>
+hipError_t launch_ext_rank_mend(const ExtEvalArgs<T> &a, const int32_t *qu, int nq, const int32_t *cand, int nc, const int32_t *listed, T *S,
+                                hipStream_t s) {
+    if (nq <= 0 || nc <= 0 || a.model != SVDPP) return hipSuccess;
+    hipLaunchKernelGGL(ext_rank_mend_svdpp<T>, dim3((unsigned)std::min<int64_t>(1024, ((int64_t)nq + 3) / 4)), dim3(256), 0, s, a, qu, cand, listed, S,
+                       nq, nc);
+    return hipGetLastError();
+}
+template hipError_t launch_ext_rank_mend<float>(const ExtEvalArgs<float> &, const int32_t *, int, const int32_t *, int, const int32_t *, float *, hipStream_t);
+template hipError_t launch_ext_rank_mend<double>(const ExtEvalArgs<double> &, const int32_t *, int, const int32_t *, int, const int32_t *, double *, hipStream_t);
 
 template <typename T>
 hipError_t launch_ext_rank_items(const ExtEvalArgs<T> &a, const int32_t *cand, int nc, T *B, int kp, hipStream_t s) {
@@ -441,16 +488,16 @@ hipError_t launch_ext_rank_items(const ExtEvalArgs<T> &a, const int32_t *cand, i
     return hipGetLastError();
 }
 template <typename T>
-hipError_t launch_ext_rank_queries(const ExtEvalArgs<T> &a, const int32_t *qu, const int32_t *qc, int nq, T *A, T *row_const, int kp,
-                                   hipStream_t s) {
+hipError_t launch_ext_rank_queries(const ExtEvalArgs<T> &a, const int32_t *qu, const int32_t *qc, int nq, T *A, T *row_const, T *row_scale,
+                                   int kp, hipStream_t s) {
     if (nq <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ext_rank_queries<T>, dim3(nq), dim3(128), 0, s, a, qu, qc, A, row_const, kp);
+    hipLaunchKernelGGL(ext_rank_queries<T>, dim3(nq), dim3(128), 0, s, a, qu, qc, A, row_const, row_scale, kp);
     return hipGetLastError();
 }
 template hipError_t launch_ext_rank_items<float>(const ExtEvalArgs<float> &, const int32_t *, int, float *, int, hipStream_t);
 template hipError_t launch_ext_rank_items<double>(const ExtEvalArgs<double> &, const int32_t *, int, double *, int, hipStream_t);
-template hipError_t launch_ext_rank_queries<float>(const ExtEvalArgs<float> &, const int32_t *, const int32_t *, int, float *, float *, int, hipStream_t);
-template hipError_t launch_ext_rank_queries<double>(const ExtEvalArgs<double> &, const int32_t *, const int32_t *, int, double *, double *, int, hipStream_t);
+template hipError_t launch_ext_rank_queries<float>(const ExtEvalArgs<float> &, const int32_t *, const int32_t *, int, float *, float *, float *, int, hipStream_t);
+template hipError_t launch_ext_rank_queries<double>(const ExtEvalArgs<double> &, const int32_t *, const int32_t *, int, double *, double *, double *, int, hipStream_t);
 
 // ---------------------------------------------------------------------------------------------
 // launchers

@@ -168,9 +168,14 @@ hipError_t launch_ext_eval(const ExtEvalArgs<T> &a, int64_t n, hipStream_t s);
 // operands of the ranking evaluation for these models (see ext_kernels.hip)
 template <typename T>
 hipError_t launch_ext_rank_items(const ExtEvalArgs<T> &a, const int32_t *cand, int nc, T *B, int kp, hipStream_t s);
+// row_scale (null for SVD++): [nq], the context's scale where it is an infinity or a NaN -- the row of A is then P_u unscaled -- else 1
 template <typename T>
-hipError_t launch_ext_rank_queries(const ExtEvalArgs<T> &a, const int32_t *qu, const int32_t *qc, int nq, T *A, T *row_const, int kp,
-                                   hipStream_t s);
+hipError_t launch_ext_rank_queries(const ExtEvalArgs<T> &a, const int32_t *qu, const int32_t *qc, int nq, T *A, T *row_const, T *row_scale,
+                                   int kp, hipStream_t s);
+// SVD++: the scores S[q * nc + c] of the listed candidates (a Q row with an infinity or a NaN) by the reference's chain; else nothing
+template <typename T>
+hipError_t launch_ext_rank_mend(const ExtEvalArgs<T> &a, const int32_t *qu, int nq, const int32_t *cand, int nc, const int32_t *listed, T *S,
+                                hipStream_t s);
 
 // dtype conversion for cmi_set_state / cmi_get_state staging
 hipError_t launch_convert(const void *src, int src_f64, void *dst, int dst_f64, int64_t n, hipStream_t s);

@@ -817,7 +817,11 @@ hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan
     f.units = nq, f.batch = bq;
     f.buffers = {{W::DB, up128(nc) * kp * sizeof(T)}, {W::DA, up128(bq) * kp * sizeof(T)}, {W::DS, (size_t)bq * (size_t)nc * sizeof(T)}, {W::DRC, (size_t)bq * sizeof(T)}};
     const bool has_hot = ops.hot1 > ops.hot0;
-    if (has_hot) f.buffers.push_back({W::DHOT, ((size_t)nc + 1) * sizeof(int32_t)});
+    const bool mends = ops.mend && ops.mend_cols > 0;
+    if (has_hot && mends) return hipErrorInvalidValue; // (one list per evaluation: no model has both)
+    if (has_hot || mends) f.buffers.push_back({W::DHOT, ((size_t)nc + 1) * sizeof(int32_t)});
+    const bool scaled = (bool)ops.build_scaled_queries;
+    if (scaled) f.buffers.push_back({W::DSCALE, (size_t)bq * sizeof(T)});
     f.plan_arrays = {plan_array(W::DCAND, plan.cand), plan_array(W::DQU, plan.qu), plan_array(W::DQC, plan.qc), plan_array(W::DEXPTR, plan.excl_ptr),
                      plan_array(W::DEXCL, plan.excl_idx)};
     // This form uploads the plan's arrays on every evaluation, as it always did.  With the uploads skipped, one evaluation of every process
@@ -828,16 +832,21 @@ hipError_t rank_run_device(hipStream_t stream, RankWorkspace &ws, const RankPlan
     f.prepare = [&] {
         hipError_t e = ops.build_items(ws.d<T>(W::DB), ws.d<int32_t>(W::DCAND), nc, kp, stream);
         if (e == hipSuccess && has_hot) e = rank_launch_list_nonfinite<T>(ws.d<T>(W::DB), nc, kp, RankHot{ops.hot0, ops.hot1, nullptr}, ws.d<int32_t>(W::DHOT), stream);
+        if (e == hipSuccess && mends) e = rank_launch_list_nonfinite<T>(ws.d<T>(W::DB), nc, kp, RankHot{0, ops.mend_cols, nullptr}, ws.d<int32_t>(W::DHOT), stream);
         return e;
     };
     f.enqueue = [&](size_t, int64_t q0, int64_t q1, RankBatch &r) {
         const int n = (int)(q1 - q0);
         r.q0 = q0, r.q1 = q1;
-        hipError_t e = ops.build_queries(ws.d<T>(W::DA), ws.d<T>(W::DRC), ws.d<int32_t>(W::DQU) + q0, ws.d<int32_t>(W::DQC) + q0, n, kp, stream);
+        const int32_t *dqu = ws.d<int32_t>(W::DQU) + q0, *dqc = ws.d<int32_t>(W::DQC) + q0;
+        hipError_t e = scaled ? ops.build_scaled_queries(ws.d<T>(W::DA), ws.d<T>(W::DRC), ws.d<T>(W::DSCALE), dqu, dqc, n, kp, stream)
+                              : ops.build_queries(ws.d<T>(W::DA), ws.d<T>(W::DRC), dqu, dqc, n, kp, stream);
+        std::function<hipError_t(T *)> mend;
+        if (mends) mend = [&, dqu, n](T *dS) { return ops.mend(dS, dqu, n, ws.d<int32_t>(W::DCAND), nc, ws.d<int32_t>(W::DHOT), stream); };
         if (e == hipSuccess)
             e = rank_launch_score<T>(ws.d<T>(W::DA), ws.d<T>(W::DB), ws.d<T>(W::DRC), ws.d<T>(W::DS), n, nc, kp, ws.d<int64_t>(W::DEXPTR), ws.d<int32_t>(W::DEXCL),
                                      (int)q0, thold, topn, ws.d<int32_t>(W::DTOP), ws.d<double>(W::DSCORE), ws.d<int32_t>(W::DCOUNT), stream,
-                                     has_hot ? RankHot{ops.hot0, ops.hot1, ws.d<int32_t>(W::DHOT)} : RankHot());
+                                     has_hot ? RankHot{ops.hot0, ops.hot1, ws.d<int32_t>(W::DHOT)} : RankHot(), scaled ? ws.d<T>(W::DSCALE) : nullptr, mend);
         return e;
     };
     return rank_run_batches(stream, ws, plan, topn, f, on_batch, ms);
@@ -1071,9 +1080,22 @@ static RankOperands<T> ext_operands(cmi_instance *h, int k_logical) {
     ops.build_items = [h](T *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
         return launch_ext_rank_items<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dcand, nc, dB, kp, s);
     };
-    ops.build_queries = [h](T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
-        return launch_ext_rank_queries<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dqu, dqc, n, dA, drc, kp, s);
+    auto queries = [h](T *dA, T *drc, T *dscale, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
+        return launch_ext_rank_queries<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dqu, dqc, n, dA, drc, dscale, kp, s);
     };
+    // the similarity models scale the finished dot product: a scale that is no number is applied behind the contraction (ext_kernels.hip)
+    // SVD++ adds a rated item's <Y_k, Q_j> term by term: the scores of a candidate whose Q row is no number are formed again its way
+    if (h->model == CMI_MODEL_SVDPP) {
+        ops.build_queries = [queries](T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t s) {
+            return queries(dA, drc, nullptr, dqu, dqc, n, kp, s);
+        };
+        ops.mend_cols = h->k;
+        ops.mend = [h](T *dS, const int32_t *dqu, int n, const int32_t *dcand, int nc, const int32_t *listed, hipStream_t s) {
+            return launch_ext_rank_mend<T>(cmi_ext_eval_args<T>(h, cmi_eval_io(h)), dqu, n, dcand, nc, listed, dS, s);
+        };
+    } else {
+        ops.build_scaled_queries = queries;
+    }
     return ops;
 }
 

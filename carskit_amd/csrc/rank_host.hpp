@@ -44,6 +44,14 @@ struct RankOperands {
     int hot0 = 0, hot1 = 0; // its one-hot columns [hot0, hot1), the last of the k_logical (RankHot, rank_kernels.hpp); hot1 <= hot0: none
     std::function<hipError_t(T *dB, const int32_t *dcand, int nc, int kp, hipStream_t)> build_items;
     std::function<hipError_t(T *dA, T *drc, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t)> build_queries;
+    // optional, in place of build_queries: also writes dscale[q], the factor the row's finished scores are multiplied by when it is an
+    // infinity or a NaN (rank_launch_score: row_scale); 1 for every other row
+    std::function<hipError_t(T *dA, T *drc, T *dscale, const int32_t *dqu, const int32_t *dqc, int n, int kp, hipStream_t)> build_scaled_queries;
+    // optional: the candidates whose operand row holds an infinity or a NaN in the columns [0, mend_cols) are listed once per evaluation
+    // (`listed`: [0] their number, then their positions), and mend computes the scores of a batch's n queries for them again, behind the
+    // contraction and in front of the mask: for a model whose reference forms such a score from other terms than the contraction does
+    int mend_cols = 0;
+    std::function<hipError_t(T *dS, const int32_t *dqu, int n, const int32_t *dcand, int nc, const int32_t *listed, hipStream_t)> mend;
 };
 
 // A growable store of HIP events, made on first use and kept for the next evaluation.
@@ -80,6 +88,7 @@ struct RankWorkspace {
         DSB, DAB,                              // split form: the second slab / operand buffer (batch b + 1 is contracted while batch b is selected)
         DM1, DM1B, DM2,                        // split form: per-row maxima of S1 (per slab) / S2 over tiles of 64 candidates (the selection's tile pruning)
         DHOT,                                  // the candidates whose one-hot columns hold an infinity or a NaN (RankHot::count_list)
+        DSCALE,                                // per query of a batch: the scale applied to its finished scores (RankOperands::build_scaled_queries)
         N_DEV
     };
     enum Pin { H_TOP, H_SCORE, H_COUNT, N_PIN }; // pinned host: the lists as they come back

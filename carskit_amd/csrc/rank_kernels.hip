@@ -435,12 +435,26 @@ __global__ __launch_bounds__(256) void rank_fix_tile_max(const T *__restrict__ S
     }
 }
 
+// ---- a row scale that is no number ------------------------------------------------------------------------------------------------
+// CAMF_ICS / LCS / MCS multiply the FINISHED dot product by the context's similarities (CAMF_ICS.java:53-57, CAMF_LCS.java:43-61,
+// CAMF_MCS.java:53-67): dot * (+-Inf) is an infinity by the sign of the dot product and a NaN only where the dot product is exactly 0.
+// Folded into the query operand (a_q = s * P_u) an infinite scale makes Inf - Inf = NaN of every dot product whose terms have both
+// signs and 0 * Inf = NaN wherever P_u has a zero.  The operand builder (ext_rank_queries) therefore leaves P_u unscaled and records
+// the scale in row_scale[q] when it is an infinity or a NaN (1 otherwise), and rank_mask -- a block per row, behind the contraction --
+// multiplies such a row before it masks it.  No launch is added: a model that has not diverged has no such row and every block reads one
+// value more.  The row constant of these models is 0, so S holds the dot product itself.  tests/test_gpu_rank_nonfinite.py holds this.
+
 // ---- exclusions: items the user already rated in this context (never candidates) -----------------------------------
 
 template <typename T>
-__global__ void rank_mask(T *S, int nc, const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, int nq) {
+__global__ void rank_mask(T *S, int nc, const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, int nq, const T *row_scale) {
     const int q = blockIdx.x;
     if (q >= nq) return;
+    if (row_scale && rank_no_number(row_scale[q])) { // (uniform over the block)
+        const T s = row_scale[q];
+        for (int c = threadIdx.x; c < nc; c += blockDim.x) S[(size_t)q * nc + c] *= s;
+        __syncthreads(); // a masked entry must not be scaled afterwards: -Inf * -Inf
+    }
     for (int64_t p = excl_ptr[q_base + q] + threadIdx.x; p < excl_ptr[q_base + q + 1]; p += blockDim.x)
         S[(size_t)q * nc + excl_idx[p]] = -INFINITY;
 }
@@ -872,11 +886,14 @@ hipError_t rank_launch_fix_onehot(const T *A, const T *B, const T *row_const, T 
 template <typename T>
 hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp,
                              const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
-                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot) {
+                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot, const T *row_scale,
+                             const std::function<hipError_t(T *S)> &mend) {
     if (nq <= 0 || nc <= 0) return hipSuccess;
     if (hipError_t e = rank_launch_gemm<T>(A, B, row_const, S, nq, nc, kp, s, nullptr, nullptr)) return e;
     if (hipError_t e = rank_launch_fix_onehot<T>(A, B, row_const, S, nq, nc, kp, hot, s, nullptr)) return e;
-    hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq);
+    if (mend)
+        if (hipError_t e = mend(S)) return e;
+    hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq, row_scale);
     if (topn <= 64)
         hipLaunchKernelGGL(rank_topn_stream<T>, dim3((nq + 3) / 4), dim3(256), 0, s, (const T *)S, nq, nc, thold, topn, out_idx,
                            out_score, out_count, q_base);
@@ -890,7 +907,7 @@ template <typename T>
 hipError_t rank_launch_select(T *S, int nq, int nc, const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
                               int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s) {
     if (nq <= 0 || nc <= 0) return hipSuccess;
-    hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq);
+    hipLaunchKernelGGL(rank_mask<T>, dim3(nq), dim3(64), 0, s, S, nc, excl_ptr, excl_idx, q_base, nq, (const T *)nullptr);
     if (topn <= 64)
         hipLaunchKernelGGL(rank_topn_stream<T>, dim3((nq + 3) / 4), dim3(256), 0, s, (const T *)S, nq, nc, thold, topn, out_idx,
                            out_score, out_count, q_base);
@@ -943,7 +960,8 @@ hipError_t rank_launch_split_select(const float *S1, const float *S2, const Rank
     template hipError_t rank_launch_list_nonfinite<T>(const T *, int, int, const RankHot &, int32_t *, hipStream_t);    \
     template hipError_t rank_launch_fix_onehot<T>(const T *, const T *, const T *, T *, int, int, int, const RankHot &, hipStream_t, T *); \
     template hipError_t rank_launch_score<T>(const T *, const T *, const T *, T *, int, int, int, const int64_t *,     \
-                                             const int32_t *, int, double, int, int32_t *, double *, int32_t *, hipStream_t, const RankHot &);
+                                             const int32_t *, int, double, int, int32_t *, double *, int32_t *, hipStream_t, const RankHot &, const T *, \
+                                             const std::function<hipError_t(T *)> &);
 CMI_INST(float)
 CMI_INST(double)
 #undef CMI_INST

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <functional>
+
 namespace cmi {
 
 // bytes the score slabs (S1, S2) are allocated beyond their last row: the pruned selection loads whole tiles of 64 candidates, and the
@@ -59,10 +61,13 @@ template <typename T>
 hipError_t rank_launch_fix_onehot(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp, const RankHot &hot, hipStream_t s,
                                   T *tile_max = nullptr);
 // S = A.B^T + row_const (one-hot terms as above); mask the (q_base+q)-th exclusion list; top-N per row into out_*[(q_base+q)*topn + n]
+// row_scale (may be null): [nq]; a row whose entry is an infinity or a NaN has its finished scores multiplied by it, by rank_mask in
+// front of its masking; every other entry is ignored.  mend (may be empty): the model's own launches on the finished slab, in front of the mask
 template <typename T>
 hipError_t rank_launch_score(const T *A, const T *B, const T *row_const, T *S, int nq, int nc, int kp,
                              const int64_t *excl_ptr, const int32_t *excl_idx, int q_base, double thold, int topn,
-                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot = RankHot());
+                             int32_t *out_idx, double *out_score, int32_t *out_count, hipStream_t s, const RankHot &hot = RankHot(),
+                             const T *row_scale = nullptr, const std::function<hipError_t(T *S)> &mend = nullptr);
 
 // the exclusions masked and the top-N selected on a FINISHED slab S[nq][nc] (scores that are no contraction: SLIM): what
 // rank_launch_score does behind its contraction

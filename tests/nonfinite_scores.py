@@ -179,30 +179,228 @@ def score_slab(model, dtype=np.float64, form="chain"):
 @functools.lru_cache(maxsize=None)
 def scores(model):
     """the reference's scores, fp64: S[c, u, p]"""
-    s = score_slab(model)
+    s = ext_score_slab(model) if model in EXT_MODELS else score_slab(model)
     s.setflags(write=False)
     return s
 
 
+# ---- SVD++ and the similarity models CAMF_ICS / CAMF_LCS / CAMF_MCS (the operand builders of ext_kernels.hip) ---------------------------
+# The similarity models multiply the FINISHED dot product by the context's similarities, one per dimension (CAMF_ICS.java:53-57,
+# CAMF_LCS.java:43-61), or once by 1 - sqrt(dist) (CAMF_MCS.java:53-67).  Contexts are the reference's: one condition per dimension,
+# the i-th against dimension i's ':na' condition SIM_EMPTY[i].  Two dimensions of four conditions; per condition the similarity to its
+# partner (CAMF_ICS: the ccMatrix entry; CAMF_LCS: the dot product of two cfMatrix rows, one entry of a row at an infinity; CAMF_MCS: the
+# difference of two positions, where an infinite or NaN position makes the scale -Inf or NaN -- a scale of +Inf does not exist there):
+#   dimension 0: condition 0 +Inf, 1 NaN, 2 zero, 3 (':na', with itself) 2        dimension 1: 4 -Inf, 5 -1/2, 6 zero, 7 (':na') 1/2
+# and the contexts' scales, in the order of SIM_CTX (ICS and LCS | MCS):
+#   0 all empty: 2 * 1/2 = 1 | 1      1: +Inf | -Inf      2: -Inf | -Inf      3: NaN | NaN      4: 0 | 0      5: 2 * -1/2 = -1 | -1
+#   6: the pair (+Inf, 0), a NaN by the reference's sequential product | -Inf      7: +Inf * -Inf = -Inf | -Inf
+# P and Q are those of factors(): against every scale stand users whose dot products are positive, negative, exactly 0, +Inf, -Inf and
+# NaN over the candidates, and every user's P row has zeros.
+SIM_MODELS = ("CAMF_ICS", "CAMF_LCS", "CAMF_MCS")
+EXT_MODELS = ("SVD++",) + SIM_MODELS
+SIM_DIMS, SIM_CONDS, SIM_NUM_F = 2, 8, 2
+SIM_EMPTY = np.array([3, 7], np.int32)
+SIM_CTX = [(3, 7), (0, 7), (3, 4), (1, 7), (2, 7), (3, 5), (0, 6), (0, 4)]
+SIM_NCTX = len(SIM_CTX)
+SIM_CTX_PTR = np.arange(0, 2 * SIM_NCTX + 1, 2, dtype=np.int32)
+SIM_CTX_CONDS = np.array(SIM_CTX, np.int32).reshape(-1)
+SIM_FINITE_CTX = (0, 4, 5)
+SIM_SCALES = {"CAMF_ICS": (1.0, np.inf, -np.inf, np.nan, 0.0, -1.0, np.nan, -np.inf),
+              "CAMF_MCS": (1.0, -np.inf, -np.inf, np.nan, 0.0, -1.0, -np.inf, -np.inf)}
+SIM_SCALES["CAMF_LCS"] = SIM_SCALES["CAMF_ICS"]
+# SVD++: the user without a training tuple (|N(u)| = 0); users whose rated items' Y rows hold +Inf and -Inf in ONE factor, in two
+# different factors, and -Inf alone (the items are candidate positions the user rated in every construction of svdpp_tuples)
+U_DEG0, U_Y_SAME, U_Y_TWO, U_Y_ONE = U_00, 14, 15, 16
+Y_PLANTS = {28: (6, np.inf), 55: (6, -np.inf), 29: (6, np.inf), 56: (7, -np.inf), 30: (6, -np.inf)}     # position: (factor, value)
+
+
+def plus_zero(a):
+    """`a` with every zero +0 (-0 + 0 = +0; every other value, infinities and NaN included, unchanged).  The similarity models' chain
+    dot * s gives -0 where one of the two is negative and the other an exact zero; the device's sum of products starts from +0 and
+    gives +0.  No comparison of the ranking tells the two apart (-0 == +0 for the threshold and for the sort)."""
+    return np.asarray(a, np.float64) + 0.0
+
+
+def tuples_of(model):
+    return svdpp_tuples() if model == "SVD++" else tuples(SIM_NCTX) if model in SIM_MODELS else tuples()
+
+
+def ctx_table(model):
+    return (SIM_CTX_PTR, SIM_CTX_CONDS) if model in SIM_MODELS else (CTX_PTR, CTX_CONDS)
+
+
 @functools.lru_cache(maxsize=None)
-def tuples():
-    """(train, test) as (u, j, ctx, r) arrays, sorted by (user, item, context).  Every candidate is rated once by a user of 13..39;
-    users 0..12 have a query in every context, with three excluded items each; user 1 (pair (+, -)) has rated position 63 (+Inf for it)
-    in context 0 only and has position 0 (+Inf) as a correct item there; user 4 (pair (-, -)) has rated position 100 in context 1"""
+def svdpp_tuples():
+    """tuples() for SVD++: unique (user, item) pairs (userItemsCache has no duplicates), no training tuple of U_DEG0, and every other
+    user's degree filled up to 16 (users 0..12) or 64 (the others) with further candidates, so sqrt|N(u)| is a power of two and every
+    sum stays exact; the items of Y_PLANTS are rated by their own user alone"""
+    rng = np.random.default_rng(20261024)
+    cand, _ = items()
+    tr, te = _tuple_sets(4)
+    planted = {cand[p] for p in Y_PLANTS}
+    pairs, out = set(), set()
+    for t in sorted(tr):
+        if t[0] != U_DEG0 and t[:2] not in pairs and (t[1] not in planted or t[0] >= 13):
+            pairs.add(t[:2])
+            out.add(t)
+    for u in range(NU):
+        have = {j for (x, j) in pairs if x == u}
+        want = 0 if u == U_DEG0 else 16 if u < 13 else 64
+        assert len(have) <= want, (u, len(have))
+        free = [j for j in cand if j not in have and j not in planted]
+        for j in rng.choice(free, want - len(have), replace=False).tolist():
+            out.add((u, j, u % 4))
+    assert all([u for (u, j, _) in out if j == cand[p]] == [13 + p % 27] for p in Y_PLANTS)
+    return _tuple_arrays(out, te)
+
+
+@functools.lru_cache(maxsize=None)
+def rated_items(model="SVD++"):
+    """N(u) of every user: the items of its training tuples, ascending"""
+    (u, j, _, _), _ = tuples_of(model)
+    out = [[] for _ in range(NU)]
+    for x, y in sorted(set(zip(u.tolist(), j.tolist()))):
+        out[x].append(y)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def ext_state(model):
+    """the state tables of an EXT model, fp64: P and Q of factors(), and the planted similarity tables / SVD++ biases and Y"""
+    P, Q = factors()
+    st = {"P": P, "Q": Q}
+    rng = np.random.default_rng(20261025)
+    cand, _ = items()
+    inf, nan = np.inf, np.nan
+    if model == "SVD++":
+        at = lambda ps: [cand[p] for p in ps]  # noqa: E731
+        st["userBias"] = rng.choice([-0.5, -0.25, 0.0, 0.25, 0.5], NU)
+        st["userBias"][U_RC] = -inf
+        st["userBias"][U_LOW] = -0.5
+        st["itemBias"] = np.zeros(N_ITEMS)
+        st["itemBias"][cand] = rng.choice([-0.25, 0.0, 0.0, 0.25], NC)
+        st["itemBias"][at(IB_PINF)] = inf
+        st["itemBias"][at(IB_NINF)] = -inf
+        st["Y"] = np.zeros((N_ITEMS, K))
+        st["Y"][cand] = rng.choice([-0.5, -0.125, 0.0, 0.0, 0.125, 0.25], (NC, K))
+        for p, (f, v) in Y_PLANTS.items():
+            st["Y"][cand[p], f] = v
+    elif model == "CAMF_ICS":
+        cc = np.full((SIM_CONDS, SIM_CONDS), 0.25)                   # (an entry read at a wrong index gives a finite scale)
+        for c, e, v in ((0, 3, inf), (1, 3, nan), (2, 3, 0.0), (3, 3, 2.0), (4, 7, -inf), (5, 7, -0.5), (6, 7, 0.0), (7, 7, 0.5)):
+            cc[c, e] = cc[e, c] = v
+        st["ccMatrix"] = cc
+    elif model == "CAMF_LCS":
+        st["cfMatrix"] = np.array([[inf, 1.0], [nan, 0.0], [1.0, -1.0], [1.0, 1.0], [-inf, 1.0], [-1.0, 0.0], [1.0, -1.0], [0.5, 0.5]])
+    else:
+        st["cVector"] = np.array([inf, nan, 1.25, 0.25, -inf, 2.5, 1.5, 0.5])
+    return st
+
+
+def sim_chain(model, st):
+    """per context the factors the reference multiplies the dot product by, in its order, fp64 from the state `st`"""
+    out = []
+    with np.errstate(invalid="ignore"):
+        for ctx in SIM_CTX:
+            sims, dist = [], np.float64(0.0)
+            for c, e in zip(ctx, SIM_EMPTY.tolist()):
+                if model == "CAMF_ICS":
+                    sims.append(np.float64(st["ccMatrix"][c, e]))
+                elif model == "CAMF_LCS":
+                    s = np.float64(0.0)
+                    for f in range(SIM_NUM_F):
+                        s = s + np.float64(st["cfMatrix"][c, f]) * np.float64(st["cfMatrix"][e, f])
+                    sims.append(s)
+                else:
+                    d = np.float64(st["cVector"][c]) - np.float64(st["cVector"][e])
+                    dist = dist + d * d
+            out.append(sims if model != "CAMF_MCS" else [np.float64(1.0) - np.sqrt(dist)])
+    return out
+
+
+def ext_score_slab(model, dtype=np.float64, form="chain"):
+    """S[c, u, p] of an EXT model from its state rounded to `dtype`, every operation of the score in `dtype`.
+    form "chain": the reference's predict() in its order -- the dot product ascending, then one multiplication per similarity; SVD++:
+    gm + bu + bj + dot, then + dot(Y_k, Q_j) / sqrt|N(u)| per rated item, ascending (SVDPlusPlus.java:138-146).
+    form "operand": the contraction over the device's operands -- a_q = fl(s * P_u) with s the product of the similarities formed in fp64,
+    which is NOT what the reference computes when s is an infinity (Inf - Inf, 0 * Inf); SVD++: a_q = [fl(P_u + ysum / w) | 1],
+    b_j = [Q_j | itemBias_j], + (gm + bu)"""
+    cand, _ = items()
+    st = {n: a.astype(dtype) for n, a in ext_state(model).items()}
+    P, Qc = st["P"], st["Q"][cand]
+    n_ctx = 4 if model == "SVD++" else SIM_NCTX
+    out = np.zeros((n_ctx, NU, NC), dtype)
+
+    def contract(A):
+        s = np.zeros((NU, NC), dtype)
+        for f in range(K):
+            s = s + A[:, f][:, None] * Qc[:, f][None, :]
+        return s
+    with np.errstate(invalid="ignore", over="ignore"):
+        if model == "SVD++":
+            gm, ub, ib, Y, N = dtype(GM), st["userBias"][:, None], st["itemBias"][cand][None, :], st["Y"], rated_items()
+            if form == "chain":
+                s = ((gm + ub) + ib) + contract(P)
+                for u in range(NU):
+                    w = dtype(math.sqrt(len(N[u])))
+                    for k in N[u]:
+                        yq = np.zeros(NC, dtype)
+                        for f in range(K):
+                            yq = yq + Y[k, f] * Qc[:, f]
+                        s[u] = s[u] + yq / w
+            else:
+                A = np.zeros((NU, K), np.float64)
+                for u in range(NU):
+                    ys = np.zeros(K, np.float64)
+                    for k in N[u]:
+                        ys = ys + Y[k].astype(np.float64)
+                    A[u] = P[u].astype(np.float64) + (ys / math.sqrt(len(N[u])) if N[u] else 0.0)
+                s = (contract(A.astype(dtype)) + dtype(1.0) * ib) + (gm + ub).astype(dtype)
+            out[:] = s[None]
+            return out
+        chain = sim_chain(model, st)
+        dot = contract(P)
+        for c in range(n_ctx):
+            if form == "chain":
+                s = dot
+                for sim in chain[c]:
+                    s = s * dtype(sim)
+            else:
+                scale = np.float64(1.0)
+                for sim in chain[c]:
+                    scale = scale * sim
+                s = contract((P.astype(np.float64) * scale).astype(dtype))
+            out[c] = s
+    return out
+
+
+def _tuple_sets(n_ctx):
     rng = np.random.default_rng(20261023)
     cand, _ = items()
-    tr = {(13 + p % 27, cand[p], p % 4) for p in range(NC)}
+    tr = {(13 + p % 27, cand[p], p % n_ctx) for p in range(NC)}
     tr |= {(U_PM, cand[63], 0), (U_MM, cand[100], 1)}
     te = {(U_PM, cand[0], 0), (U_PP, cand[64], 1), (U_MM, cand[300], 0)}
     for u in range(NU):
-        for c in (range(4) if u < 13 else ((u % 4), (u + 1) % 4)):
+        for c in (range(n_ctx) if u < 13 else ((u % n_ctx), (u + 1) % n_ctx)):
             if u < 13:
                 tr |= {(u, cand[int(p)], c) for p in rng.choice(NC, 3, replace=False)}
             te |= {(u, cand[int(p)], c) for p in rng.choice(NC, 2, replace=False)}
-    te -= tr
+    return tr, te
+
+
+def _tuple_arrays(tr, te):
     arr = lambda ts, r: (np.array([t[0] for t in ts], np.int32), np.array([t[1] for t in ts], np.int32),  # noqa: E731
                          np.array([t[2] for t in ts], np.int32), np.full(len(ts), r))
-    return arr(sorted(tr), 3.0), arr(sorted(te), 5.0)
+    return arr(sorted(tr), 3.0), arr(sorted(te - tr), 5.0)
+
+
+@functools.lru_cache(maxsize=None)
+def tuples(n_ctx=4):
+    """(train, test) as (u, j, ctx, r) arrays, sorted by (user, item, context).  Every candidate is rated once by a user of 13..39;
+    users 0..12 have a query in every context, with three excluded items each; user 1 (pair (+, -)) has rated position 63 (+Inf for it)
+    in context 0 only and has position 0 (+Inf) as a correct item there; user 4 (pair (-, -)) has rated position 100 in context 1.
+    n_ctx: the number of contexts (4: the MF family and the slab form; SIM_NCTX: the similarity models)"""
+    return _tuple_arrays(*_tuple_sets(n_ctx))
 
 
 def as_lists(d):
@@ -214,7 +412,7 @@ def oracle(model, bin_thold, num_recs):
     """(measures, lists) of oracle/rank_oracle.eval_rankings over the reference's scores"""
     _, pos = items()
     s = scores(model)
-    train, test = tuples()
+    train, test = tuples_of(model)
     return rank_oracle.eval_rankings(lambda u, j, c: float(s[c, u, pos[j]]), as_lists(train), as_lists(test), bin_thold=bin_thold,
                                      num_recs=num_recs)
 
@@ -276,10 +474,11 @@ def select(row, excl, thold, num_recs, rule="reference", tile_bound=None):
     return [(p, s) for p, s, _ in entries[:num_recs]]
 
 
-def lists_by(model, queries, thold, num_recs, rule="reference", bounds=None):
-    """{(u, c): [(item, score)]} of every query of `queries` (capi.rank_plan's) that has a list under `rule`"""
+def lists_by(model, queries, thold, num_recs, rule="reference", bounds=None, s=None):
+    """{(u, c): [(item, score)]} of every query of `queries` (capi.rank_plan's) that has a list under `rule`; s: scores to select from in
+    place of the reference's"""
     cand, _ = items()
-    s = scores(model)
+    s = scores(model) if s is None else s
     out = {}
     for q, (u, c, correct, excl) in enumerate(queries):
         got = select(s[c, u], excl, thold, num_recs, rule, None if bounds is None else bounds[q])

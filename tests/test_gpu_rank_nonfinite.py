@@ -16,6 +16,12 @@ Which kernels a case reaches (rank_kernels.hip unless noted):
       rank_mask<float>, then rank_topn_stream<float> (num_recs <= 64) or rank_topn<float> (70)
   rank_gemm<double> is followed by rank_fix_onehot too.  Contexts 2 and 3 of the CAMF models do not hold the condition whose icBias
   entries are planted: a contraction that multiplies them by the one-hot row's zeros makes NaN of scores the reference leaves alone.
+  SVD++, CAMF_ICS / LCS / MCS (fp32 and fp64 state; always the per-query contraction): ext_rank_items and ext_rank_queries
+      (ext_kernels.hip) build the operands, rank_gemm_mfma_f32 or rank_gemm<double> contracts them, then
+      SVD++: rank_list_nonfinite_rows lists the candidates whose Q row is no number, ext_rank_mend_svdpp forms their scores again
+      then rank_mask -- which, for CAMF_ICS / LCS / MCS, first multiplies the rows whose context's scale is an infinity or a NaN
+          (ext_rank_queries left P_u unscaled there and recorded the scale); contexts 0, 4 and 5 have finite scales (1, 0, -1) and take
+          the folded operand as before -- and rank_topn_stream (num_recs 10) or rank_topn (70), as above
   rank_tile_max, the VALU fallback of the contraction's tile maxima, is not reached: no supported configuration takes it (every
   operand length is rounded up to the matrix kernel's k step of 16).
 """
@@ -41,17 +47,19 @@ def thold_of(model, t):
 
 
 def check(h, model, thold, num_recs, oracle=nf.oracle, **env):
-    """one evaluation against the oracle's lists and measures of the same setting; returns the lists"""
-    train, test = nf.tuples()
+    """one evaluation against the oracle's lists and measures of the same setting; returns the lists.  (The similarity models: a zero
+    score of either sign counts as +0, see nf.plus_zero; every other model's scores bit for bit, as ever.)"""
+    train, test = nf.tuples_of(model)
     res, lists = with_env(lambda: h.eval_rankings(train, test, bin_thold=thold, num_recs=num_recs, with_lists=True), **env)
     ref, want = oracle(model, thold, num_recs)
     label = (model, thold, num_recs, env)
+    canon = nf.plus_zero if model in nf.SIM_MODELS else (lambda x: x)
     assert set(lists) == set(want) and len(want) > 20, (label, sorted(set(lists) ^ set(want))[:5])
     for key, ref_l in want.items():
         got = lists[key]
         assert len(got) == len(ref_l), (label, key, len(got), len(ref_l))
         assert [i for i, _ in got] == [i for i, _ in ref_l], (label, key, got[:12], ref_l[:12])
-        assert same_bits_exact([s for _, s in got], [s for _, s in ref_l]), (label, key)
+        assert same_bits_exact(canon([s for _, s in got]), canon([s for _, s in ref_l])), (label, key)
     for m, b in ref.items():
         a = res[m]
         assert (math.isnan(a) and math.isnan(b)) or abs(a - b) <= 1e-12, (label, m, a, b)
@@ -177,3 +185,36 @@ def test_pruned_and_plain_split_forms_agree_entry_for_entry(model):
             assert pruned[1] == plain[1] and len(plain[1]) > 20
             for m, v in plain[0].items():
                 assert np.float64(v).tobytes() == np.float64(pruned[0][m]).tobytes() or (math.isnan(v) and math.isnan(pruned[0][m])), m
+
+
+# ---- SVD++ and the similarity models: operand builders of their own, always the per-query contraction ----------------------------------
+@functools.lru_cache(maxsize=None)
+def ext_handle(model, flags):
+    """the injected model (never trained): set_ratings gives SVD++ its users' item lists and the others their context table"""
+    train, _ = nf.tuples_of(model)
+    h = capi.Instance(model, nf.K, nf.NU, nf.N_ITEMS, nf.SIM_CONDS if model in nf.SIM_MODELS else nf.N_CONDS, flags=flags | capi.FLAG_SCHED_SERIAL)
+    h.set_hparams(REG, REG, REG, REGC, nf.GM)
+    if model == "SVD++":
+        h.set_ratings(train[0], train[1], None, train[3])
+    else:
+        h.set_sim_params(nf.SIM_NUM_F, nf.SIM_DIMS, nf.SIM_EMPTY)
+        h.set_ratings(*train, nf.SIM_CTX_PTR, nf.SIM_CTX_CONDS)
+    st = nf.ext_state(model)
+    h.set_states(st)
+    back = h.get_states()
+    for name, a in st.items():
+        assert np.array_equal(back[name], a, equal_nan=True), name           # every entry is an fp32 number, an infinity or a NaN
+    return h
+
+
+@pytest.mark.parametrize("num_recs", [10, 70])
+@pytest.mark.parametrize("state", ["f32", "f64"])
+@pytest.mark.parametrize("model", nf.EXT_MODELS)
+def test_ext_operand_forms(model, state, num_recs):
+    """scales of +Inf, -Inf, NaN, 0, -1 and 1 (CAMF_MCS: no +Inf) against dot products that are positive, negative, exactly 0, +Inf, -Inf
+    and NaN; SVD++ with planted Y rows, biases, a row constant of -Inf, the user without a rated item, and Q rows that are no numbers"""
+    h = ext_handle(model, capi.FLAG_STATE_F64 if state == "f64" else 0)
+    for t in THOLDS:
+        lists = check(h, model, thold_of(model, t), num_recs)
+        assert check(h, model, thold_of(model, t), num_recs, CMI_RANK_BATCH=23) == lists
+        assert check(h, model, thold_of(model, t), num_recs, CMI_RANK_NO_SPLIT=1) == lists      # (no split form: the variable changes nothing)

@@ -224,3 +224,128 @@ def test_the_real_tile_bound_is_nan_only_over_tiles_that_hold_no_passing_score(m
             else:
                 assert ub[t] >= top, (u, c, t)
     assert n_nan >= 1 or model == "PQ", model
+
+
+# ---- SVD++ and the similarity models CAMF_ICS / CAMF_LCS / CAMF_MCS -------------------------------------------------------------------
+def ext_plan(model, thold):
+    train, test = nf.tuples_of(model)
+    return capi.rank_plan(nf.NU, nf.N_ITEMS, train, test, thold, 0)
+
+
+@pytest.mark.parametrize("model", nf.EXT_MODELS)
+def test_ext_candidates_and_queries_are_the_constructions(model):
+    cand, queries = ext_plan(model, -1.0)
+    assert cand == nf.items()[0]
+    n_ctx = nf.SIM_NCTX if model in nf.SIM_MODELS else 4
+    assert {(u, c) for u, c, _, _ in queries} >= {(u, c) for u in range(13) for c in range(n_ctx)}
+    if model == "SVD++":
+        (tu, tj, _, _), _ = nf.tuples_of(model)
+        assert len(set(zip(tu.tolist(), tj.tolist()))) == len(tu)                      # unique pairs: |N(u)| is unambiguous
+        deg = [len(n) for n in nf.rated_items()]
+        assert deg[nf.U_DEG0] == 0 and set(deg) == {0, 16, 64}
+        assert not [q for q in queries if q[0] == nf.U_DEG0 and q[3]]                   # no training tuple: nothing excluded
+        N, cand_at = nf.rated_items(), nf.items()[0]
+        assert {cand_at[28], cand_at[55]} <= set(N[nf.U_Y_SAME]) and {cand_at[29], cand_at[56]} <= set(N[nf.U_Y_TWO]) and cand_at[30] in N[nf.U_Y_ONE]
+    else:
+        # the reference's contexts: one condition per dimension, the i-th from dimension i; one context of the ':na' conditions alone
+        assert all(len(c) == nf.SIM_DIMS and all(4 * i <= x < 4 * i + 4 for i, x in enumerate(c)) for c in nf.SIM_CTX)
+        assert tuple(nf.SIM_EMPTY) == nf.SIM_CTX[0] and nf.ext_state(model)["P"].shape[1] == nf.K
+        assert all(np.any(nf.ext_state(model)["P"][u] == 0.0) for u in range(nf.NU))     # every P row has zeros
+
+
+@pytest.mark.parametrize("model", nf.EXT_MODELS)
+def test_ext_finite_entries_are_dyadic_and_the_chain_is_exact_in_fp32_and_fp64(model):
+    for name, a in nf.ext_state(model).items():
+        fin = a[np.isfinite(a)]
+        assert np.all(fin * 8 == np.rint(fin * 8)) and np.all(np.abs(fin) <= 2.5), name
+        assert np.array_equal(a.astype(np.float32).astype(np.float64), a, equal_nan=True), name
+    ref = nf.scores(model)
+    assert same_bits(nf.ext_score_slab(model, np.float32, "chain").astype(np.float64), ref)
+    assert (np.isfinite(ref).sum(), np.sum(ref == np.inf), np.sum(ref == -np.inf), np.isnan(ref).sum()) > (ref.size // 8, 1000, 1000, 1000)
+
+
+@pytest.mark.parametrize("model", nf.SIM_MODELS)
+def test_sim_contexts_carry_the_planted_scales_against_every_class_of_dot_product(model):
+    chain = nf.sim_chain(model, nf.ext_state(model))
+    with np.errstate(invalid="ignore"):
+        scales = [float(np.prod(np.array(c))) if len(c) == 1 else float(c[0] * c[1]) for c in chain]
+    assert same_bits(scales, nf.SIM_SCALES[model])
+    if model != "CAMF_MCS":
+        assert chain[6][0] == np.inf and chain[6][1] == 0.0 and chain[7][0] == np.inf and chain[7][1] == -np.inf
+        assert chain[0] == [2.0, 0.5]                                  # the ':na' pairs are not 1 each: a skipped dimension shows
+    dot = nf.scores("PQ")[0]                                           # <P_u, Q_j>, the same factors
+    ref = nf.scores(model)
+    _, queries = ext_plan(model, -1.0)
+    for c, s in enumerate(nf.SIM_SCALES[model]):
+        users = sorted({u for u, qc, _, _ in queries if qc == c})
+        d = dot[users]
+        fin = np.isfinite(d)
+        assert np.any(d[fin] > 0) and np.any(d[fin] < 0) and np.any(d == 0.0) and np.any(d == np.inf) and np.any(d == -np.inf) and np.isnan(d).any()
+        if abs(s) == np.inf:      # the reference: an infinity by the sign of the dot product, a NaN only on an exact zero (or a NaN)
+            r = ref[c][users]
+            assert np.array_equal(r[fin & (d != 0)], np.sign(d[fin & (d != 0)]) * s) and np.isnan(r[d == 0.0]).all()
+            assert np.array_equal(r[np.isinf(d)], np.sign(d[np.isinf(d)]) * s)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("model", nf.SIM_MODELS)
+def test_a_scale_folded_into_the_query_operand_would_be_told_apart(model, dtype):
+    """a_q = s * P_u first, then the contraction: NaN where the reference's chain has an infinity (Inf - Inf over terms of both signs,
+    0 * Inf on the zeros of P_u); bit for bit the chain on the finite contexts; and a selector fed those scores loses lists.
+    (Bit for bit but for the sign of a zero: the chain's dot * s is -0 where one of the two is negative and the other an exact zero, a
+    sum of products that starts from +0 is +0.  Nothing orders or thresholds the two apart, so the comparisons here and on the device
+    take a zero of either sign for +0: nf.plus_zero.)"""
+    ref, raw = nf.scores(model), nf.ext_score_slab(model, dtype, "operand").astype(np.float64)
+    for c, s in enumerate(nf.SIM_SCALES[model]):
+        if c in nf.SIM_FINITE_CTX:
+            assert np.isfinite(s) and same_bits(nf.plus_zero(raw[c]), nf.plus_zero(ref[c]))
+            odd = raw[c].view(np.int64) != ref[c].view(np.int64)
+            assert np.all(raw[c][odd & ~np.isnan(ref[c])] == 0.0) and np.all(ref[c][odd & ~np.isnan(ref[c])] == 0.0)
+        elif abs(s) == np.inf:
+            spoiled = np.isnan(raw[c]) & np.isinf(ref[c])
+            assert spoiled.sum() > 1000 and spoiled[nf.U_LOW].any() and spoiled[nf.U_PP].any(), (c, spoiled.sum())
+            assert np.isnan(raw[c][np.isnan(ref[c])]).all()
+        else:
+            assert math.isnan(s) and np.isnan(ref[c]).all() and np.isnan(raw[c]).all()
+    differ = 0
+    for thold in (-1.0, nf.mode_threshold(model), -1e300):
+        _, queries = ext_plan(model, thold)
+        for num_recs in (10, 70):
+            _, want = nf.oracle(model, thold, num_recs)
+            assert nf.same_lists(nf.lists_by(model, queries, thold, num_recs), want)
+            got = nf.lists_by(model, queries, thold, num_recs, s=raw)
+            differ += not nf.same_lists(got, want)
+            fin = lambda d: {k: [(j, v + 0.0) for j, v in l] for k, l in d.items() if k[1] in nf.SIM_FINITE_CTX}  # noqa: E731
+            assert fin(got) == fin(want)
+    assert differ == 6
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_svdpp_operand_form_is_the_chain_but_on_the_candidates_whose_q_row_is_no_number(dtype):
+    """[P_u + ysum / w | 1] against [Q_j | itemBias_j]: the same NaN and infinite terms as the reference's chain wherever Q_j is finite --
+    planted Y rows, biases, P rows included.  Against a Q_j[f] that is an infinity the operand has ONE term, (P_u + ysum / w)[f] * Inf,
+    an infinity by the sign of the sum; the chain has P_u[f] * Inf and every Y_k[f] * Inf / w as terms of their own, a NaN as soon as two
+    differ in sign or one factor is 0: there the contraction alone is not the reference, and a selector fed its scores is told apart"""
+    ref, raw = nf.scores("SVD++"), nf.ext_score_slab("SVD++", dtype, "operand").astype(np.float64)
+    q_bad = np.zeros(nf.NC, bool)
+    q_bad[list(set(nf.A) | set(nf.B))] = True
+    assert same_bits(raw[:, :, ~q_bad], ref[:, :, ~q_bad])
+    assert not np.isfinite(ref[:, :, q_bad]).any() and not np.isfinite(raw[:, :, q_bad]).any()
+    spoiled = np.isinf(raw) & np.isnan(ref)
+    assert spoiled.sum() > 1000 and not (np.isnan(raw) & ~np.isnan(ref)).any()
+    differ = 0
+    for thold in (-1.0, -1e300):
+        _, queries = ext_plan("SVD++", thold)
+        for num_recs in (10, 70):
+            differ += not nf.same_lists(nf.lists_by("SVD++", queries, thold, num_recs, s=raw), nf.oracle("SVD++", thold, num_recs)[1])
+    assert differ == 4
+    s = ref[0]
+    assert np.isnan(s[nf.U_Y_SAME]).all()                                            # +Inf and -Inf in one factor: Inf - Inf whatever Q_j
+    assert np.any(s[nf.U_Y_TWO] == np.inf) and np.any(s[nf.U_Y_TWO] == -np.inf) and np.isnan(s[nf.U_Y_TWO]).any()
+    assert np.any(s[nf.U_Y_ONE] == np.inf) and np.any(s[nf.U_Y_ONE] == -np.inf) and np.isnan(s[nf.U_Y_ONE]).any()
+    assert not np.any(s[nf.U_RC] > -np.inf) and np.isfinite(s[nf.U_DEG0]).any()
+    assert np.all(s[nf.U_Y_ONE][list(nf.IB_PINF)] != -np.inf) and s[17, nf.IB_PINF[0]] == np.inf and s[17, nf.IB_NINF[0]] == -np.inf
+    for thold in (-1.0, nf.mode_threshold("SVD++"), -1e300):
+        _, queries = ext_plan("SVD++", thold)
+        for num_recs in (10, 70):
+            assert nf.same_lists(nf.lists_by("SVD++", queries, thold, num_recs), nf.oracle("SVD++", thold, num_recs)[1])
