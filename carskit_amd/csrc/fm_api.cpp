@@ -52,6 +52,8 @@ struct cmi_fm_instance {
     bool v_valid = true, vt_valid = false; // which of V (p x k) / Vt (k x p) holds the current factors
     double *d_r = nullptr, *d_part = nullptr, *d_scratch = nullptr, *d_E = nullptr;
     double2 *d_tab = nullptr;
+    int32_t *d_bad = nullptr; // the census of w and V that predict and the rankings read (fm_kernels.hip fm_census_kernel)
+    bool bad_valid = false;   // ... is that of the model as it stands: whatever writes w or V clears it
     int32_t *d_u = nullptr, *d_j = nullptr, *d_ctx = nullptr, *d_src[3] = {nullptr, nullptr, nullptr};
     FmOrderDev ord[3];   // [2] only: the context field (records sorted by feature, a wave per feature)
     FmCellsDev cell[2];  // users, items
@@ -96,7 +98,7 @@ extern "C" int cmi_fm_destroy(cmi_fm_handle h) {
     if (h->comm) (void)ncclCommDestroy(h->comm);
     h->comm = nullptr;
     h->rank_ws.release();
-    abi_free(h->d_w0, h->d_d0, h->d_w, h->d_V, h->d_Vt, h->d_part, h->d_scratch, h->d_tab);
+    abi_free(h->d_w0, h->d_d0, h->d_w, h->d_V, h->d_Vt, h->d_part, h->d_scratch, h->d_tab, h->d_bad);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return CMI_OK;
@@ -138,6 +140,7 @@ extern "C" int cmi_fm_create(int k, int n_users, int n_items, int n_conds, int n
         if (e == hipSuccess) e = hipMalloc((void **)&h->d_scratch, 256 * sizeof(double));
         if (e == hipSuccess) e = hipMalloc((void **)&h->d_tab, (size_t)(h->p + 1) * sizeof(double2)); // + 1: fm_rec_eval's dummy gather
         if (e == hipSuccess) e = hipMemsetAsync(h->d_tab, 0, (size_t)(h->p + 1) * sizeof(double2), h->stream);
+        if (e == hipSuccess) e = hipMalloc((void **)&h->d_bad, fm_census_ints() * sizeof(int32_t));
         if (e != hipSuccess) {
             g_fm_create_err = std::string("cmi_fm_create: ") + hipGetErrorString(e);
             cmi_fm_destroy(h);
@@ -165,6 +168,7 @@ extern "C" int cmi_fm_set_model(cmi_fm_handle h, double w0, const double *w, con
     CMI_HIP(h, hipStreamSynchronize(h->stream));
     h->have_model = true;
     h->initialised = false;
+    h->bad_valid = false;
     h->col[0] = h->col[1] = h->col[2] = -1;
     h->v_valid = true;
     h->vt_valid = false;
@@ -176,6 +180,14 @@ static int fm_sync_V(cmi_fm_instance *h) {
     if (h->v_valid) return CMI_OK;
     CMI_HIP(h, fm_launch_transpose(h->d_Vt, h->d_V, h->k, h->p, h->stream));
     h->v_valid = true;
+    return CMI_OK;
+}
+// V as the API has it, and the census of the model as it stands: what cmi_fm_predict_batch and cmi_fm_eval_rankings read
+static int fm_sync_eval(cmi_fm_instance *h) {
+    if (int rc = fm_sync_V(h)) return rc;
+    if (h->bad_valid) return CMI_OK;
+    CMI_HIP(h, fm_launch_census(h->d_w, h->d_V, h->n_users, h->n_items, h->p, h->k, h->d_bad, h->stream));
+    h->bad_valid = true;
     return CMI_OK;
 }
 static int fm_sync_Vt(cmi_fm_instance *h) {
@@ -753,6 +765,7 @@ extern "C" int cmi_fm_init(cmi_fm_handle h) {
     if (int rc = fm_ready(h, false)) return rc;
     if (int rc = fm_sync_V(h)) return rc;
     h->col[0] = h->col[1] = h->col[2] = -1;
+    h->bad_valid = false;
     CMI_HIP(h, fm_launch_init(fm_args(h), h->stream));
     CMI_HIP(h, hipStreamSynchronize(h->stream));
     h->initialised = true;
@@ -836,6 +849,7 @@ extern "C" int cmi_fm_phase_apply(cmi_fm_handle h, int phase) {
     if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     if (h->last_phase != phase) CMI_FAIL(h, CMI_E_INVALID, "fm: phase_apply(%d) without the matching phase_reduce", phase);
     FmArgs a = fm_args(h);
+    h->bad_valid = false;
     if (phase == 0) CMI_HIP(h, fm_launch_w0_apply(a, h->stream));
     else {
         a.xcol = fm_xcol(h, field, f);
@@ -855,6 +869,7 @@ extern "C" int cmi_fm_phase_run(cmi_fm_handle h, int phase) {
     if (!phase_decode(h, phase, &field, &f)) CMI_FAIL(h, CMI_E_INVALID, "fm: bad phase %d", phase);
     if (int rc = fm_before_phase(h, field, f)) return rc;
     FmArgs a = fm_args(h);
+    h->bad_valid = false;
     if (phase == 0) {
         CMI_HIP(h, fm_launch_w0_reduce(a, h->d_scratch, h->stream));
         CMI_HIP(h, fm_launch_w0_apply(a, h->stream));
@@ -1017,8 +1032,8 @@ extern "C" int cmi_fm_predict_batch(cmi_fm_handle h, int64_t n, const int32_t *u
                 CMI_FAIL(h, CMI_E_INVALID, "fm_predict: id out of range at tuple %lld", (long long)t);
         if (n == 0) return CMI_OK;
         return abi_predict(h, "fm_predict", n, u, j, ctx, nullptr, 0, out, [&](const AbiTuples &t, double *d_out) {
-            if (int rc = fm_sync_V(h)) return rc;
-            return abi_hip(h->err, "fm_predict", fm_launch_predict(fm_args(h), n, t.a, t.b, t.c, bound, lo, hi, d_out, h->stream));
+            if (int rc = fm_sync_eval(h)) return rc;
+            return abi_hip(h->err, "fm_predict", fm_launch_predict(fm_args(h), h->d_bad, n, t.a, t.b, t.c, bound, lo, hi, d_out, h->stream));
         });
     });
 }
@@ -1035,12 +1050,12 @@ extern "C" int cmi_fm_eval_rankings(cmi_fm_handle h, int64_t n_train, const int3
         auto ready = [h]() -> int {
             if (!h->have_model) CMI_FAIL(h, CMI_E_INVALID, "fm: call cmi_fm_set_model first");
             CMI_HIP(h, hipSetDevice(h->device));
-            return fm_sync_V(h);
+            return fm_sync_eval(h);
         };
         auto score = [&](const RankPlan &plan, const RankBatchFn &on_batch) {
             RankOperands<double> ops;
             ops.k_logical = h->k + 1;
-            const RankFmArgs base{h->d_w0, h->d_w, h->d_V, h->k, 0, h->n_users, h->n_items, h->n_conds, 1.0 / (double)h->n_ctx_dims};
+            const RankFmArgs base{h->d_w0, h->d_w, h->d_V, h->k, 0, h->n_users, h->n_items, h->n_conds, 1.0 / (double)h->n_ctx_dims, h->d_bad};
             ops.build_items = [base](double *dB, const int32_t *dcand, int nc, int kp, hipStream_t s) {
                 RankFmArgs a = base;
                 a.kp = kp;

@@ -592,8 +592,47 @@ __global__ __launch_bounds__(256) void fm_init_spread(FmArgs a) {
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.d0 = 0.0;
 }
 
+// FM.predict multiplies EVERY entry of w and of each column of V by the feature vector, the zeros included (FM.java:97-98, 103-105):
+// an entry that is no finite number at a coordinate the tuple does NOT hold adds 0 * Inf = NaN to the sum.  At a coordinate it holds
+// the entry takes part as written: in w that can leave an infinity, in V it is NaN again (sum1^2 - sum2 = Inf - Inf).  So a
+// prediction is NaN when V holds any such entry, or w holds one outside the tuple's own (at most three) coordinates.  The kernels
+// that evaluate FM.predict touch the tuple's coordinates only; they read this census of the model:
+//   bad[0] = 1 when V has an entry that is not finite; bad[1] = how many of w's user and condition entries are not finite;
+//   bad[2] = how many of w's item entries are.
+constexpr int FM_CENSUS_BLOCKS = 256;
+__global__ __launch_bounds__(256) void fm_census_kernel(const double *w, const double *V, int64_t n_users, int64_t n_items, int64_t p,
+                                                        int64_t pk, int32_t *partial) {
+    __shared__ int32_t red[3][256];
+    int32_t in_v = 0, in_w = 0, in_w_items = 0;
+    const int64_t stride = (int64_t)gridDim.x * 256, t0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t i = t0; i < p; i += stride)
+        if (!isfinite(w[i])) {
+            if (i >= n_users && i < n_users + n_items) ++in_w_items;
+            else ++in_w;
+        }
+    for (int64_t i = t0; i < pk; i += stride)
+        if (!isfinite(V[i])) in_v = 1;
+    red[0][threadIdx.x] = in_v;
+    red[1][threadIdx.x] = in_w;
+    red[2][threadIdx.x] = in_w_items;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m)
+            for (int c = 0; c < 3; ++c) red[c][threadIdx.x] += red[c][threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x < 3) partial[3 * blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
+}
+__global__ void fm_census_sum(const int32_t *partial, int nblk, int32_t *bad) {
+    if (threadIdx.x < 3) {
+        int32_t s = 0;
+        for (int b = 0; b < nblk; ++b) s += partial[3 * b + threadIdx.x];
+        bad[threadIdx.x] = threadIdx.x == 0 ? (s != 0) : s;
+    }
+}
+
 // FM.predict (FM.java:93-113) for arbitrary tuples; one wave per tuple
-__global__ __launch_bounds__(256) void fm_predict_kernel(FmArgs a, int64_t n, const int32_t *tu, const int32_t *tj,
+__global__ __launch_bounds__(256) void fm_predict_kernel(FmArgs a, const int32_t *bad, int64_t n, const int32_t *tu, const int32_t *tj,
                                                          const int32_t *tc, int bound, double lo, double hi,
                                                          double *out) {
     const int lane = threadIdx.x & 63;
@@ -612,10 +651,13 @@ __global__ __launch_bounds__(256) void fm_predict_kernel(FmArgs a, int64_t n, co
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) pair += __shfl_xor(pair, m, 64);
         if (lane == 0) {
-            double pred = *a.w0 + a.w[u];
-            pred += a.w[a.n_users + j];
-            if (has_c) pred += a.w[a.n_users + a.n_items + c] * a.xc;
+            const double wu = a.w[u], wj = a.w[a.n_users + j], wc = has_c ? a.w[a.n_users + a.n_items + c] : 0.0;
+            double pred = *a.w0 + wu;
+            pred += wj;
+            if (has_c) pred += wc * a.xc;
             pred += 0.5 * pair;
+            // an entry that is no number at a coordinate this tuple does not hold (fm_census_kernel)
+            if (bad[0] || bad[1] > (int)!isfinite(wu) + (int)!isfinite(wc) || bad[2] > (int)!isfinite(wj)) pred = __builtin_nan("");
             out[i] = bound_to_scale(pred, bound, lo, hi);
         }
     }
@@ -719,12 +761,24 @@ hipError_t fm_launch_init(const FmArgs &a, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t fm_launch_predict(const FmArgs &a, int64_t n, const int32_t *tu, const int32_t *tj, const int32_t *tc,
+hipError_t fm_launch_predict(const FmArgs &a, const int32_t *bad, int64_t n, const int32_t *tu, const int32_t *tj, const int32_t *tc,
                              int bound, double lo, double hi, double *out, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     int64_t blocks = (n + 3) / 4;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(fm_predict_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, n, tu, tj, tc, bound, lo, hi, out);
+    hipLaunchKernelGGL(fm_predict_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, bad, n, tu, tj, tc, bound, lo, hi, out);
+    return hipGetLastError();
+}
+
+size_t fm_census_ints() { return 3 + 3 * (size_t)FM_CENSUS_BLOCKS; }
+
+hipError_t fm_launch_census(const double *w, const double *V, int n_users, int n_items, int64_t p, int k, int32_t *bad, hipStream_t s) {
+    const int64_t pk = p * k;
+    int64_t blocks = (p + pk + 256 * 16 - 1) / (256 * 16);
+    if (blocks < 1) blocks = 1;
+    if (blocks > FM_CENSUS_BLOCKS) blocks = FM_CENSUS_BLOCKS;
+    hipLaunchKernelGGL(fm_census_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w, V, (int64_t)n_users, (int64_t)n_items, p, pk, bad + 3);
+    hipLaunchKernelGGL(fm_census_sum, dim3(1), dim3(64), 0, s, bad + 3, (int)blocks, bad);
     return hipGetLastError();
 }
 

@@ -105,7 +105,10 @@ hipError_t fm_launch_transpose(const double *src, double *dst, int64_t rows, int
 hipError_t fm_launch_w0_reduce(const FmArgs &a, double *scratch, hipStream_t s);            // part[0] = sum(err_i - w0)
 hipError_t fm_launch_w0_apply(const FmArgs &a, hipStream_t s);
 hipError_t fm_launch_init(const FmArgs &a, hipStream_t s);
-hipError_t fm_launch_predict(const FmArgs &a, int64_t n, const int32_t *tu, const int32_t *tj, const int32_t *tc,
+// the census of w and V (fm_kernels.hip fm_census_kernel): bad[0..2] are the answer, the rest of the fm_census_ints() ints is scratch
+size_t fm_census_ints();
+hipError_t fm_launch_census(const double *w, const double *V, int n_users, int n_items, int64_t p, int k, int32_t *bad, hipStream_t s);
+hipError_t fm_launch_predict(const FmArgs &a, const int32_t *bad, int64_t n, const int32_t *tu, const int32_t *tj, const int32_t *tc,
                              int bound, double lo, double hi, double *out, hipStream_t s);
 
 } // namespace cmi

@@ -73,7 +73,10 @@ __global__ void rank_build_queries(RankQueryArgs<T> a) { // one block per query
 __global__ void rank_fm_items(RankFmArgs a, const int32_t *cand, double *B) { // one block per candidate
     const int64_t l = (int64_t)a.n_users + cand[blockIdx.x];
     double *dst = B + (size_t)blockIdx.x * a.kp;
-    for (int f = threadIdx.x; f < a.kp; f += blockDim.x) dst[f] = f < a.k ? a.V[(size_t)l * a.k + f] : (f == a.k ? a.w[l] : 0.0);
+    // FM.predict multiplies every entry of w by the feature vector (FM.java:97-98): an item's weight that is no number makes NaN of
+    // every OTHER item's score
+    const double wl = a.w[l], wj = a.bad[2] > (int)!isfinite(wl) ? __builtin_nan("") : wl;
+    for (int f = threadIdx.x; f < a.kp; f += blockDim.x) dst[f] = f < a.k ? a.V[(size_t)l * a.k + f] : (f == a.k ? wj : 0.0);
 }
 
 __global__ void rank_fm_queries(RankFmArgs a, const int32_t *qu, const int32_t *qc, double *A, double *row_const) {
@@ -102,8 +105,12 @@ __global__ void rank_fm_queries(RankFmArgs a, const int32_t *qu, const int32_t *
     if (threadIdx.x == 0) {
         double s = 0.0;
         for (int t = 0; t < (int)blockDim.x; ++t) s += part[t];
-        double rc = *a.w0 + a.w[u];
-        if (has_c) rc += a.xc * a.w[(int64_t)a.n_users + a.n_items + c] + a.xc * s;
+        const double wu = a.w[u], wc = has_c ? a.w[(int64_t)a.n_users + a.n_items + c] : 0.0;
+        double rc = *a.w0 + wu;
+        if (has_c) rc += a.xc * wc + a.xc * s;
+        // the same for V (FM.java:103-108: wherever the entry sits, sum1^2 - sum2 is NaN) and for the weights of the users and conditions
+        // this query does not hold: the whole row is NaN
+        if (a.bad[0] || a.bad[1] > (int)!isfinite(wu) + (int)!isfinite(wc)) rc = __builtin_nan("");
         row_const[blockIdx.x] = rc;
     }
 }

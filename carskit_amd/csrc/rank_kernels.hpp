@@ -37,6 +37,7 @@ struct RankFmArgs {
     const double *w0, *w, *V; // V: p x k row-major, p = n_users + n_items + n_conds
     int k, kp, n_users, n_items, n_conds;
     double xc;
+    const int32_t *bad; // the census of w and V (fm_kernels.hip fm_census_kernel)
 };
 hipError_t rank_launch_fm_items(const RankFmArgs &a, const int32_t *cand, int nc, double *B, hipStream_t s);
 hipError_t rank_launch_fm_queries(const RankFmArgs &a, const int32_t *qu, const int32_t *qc, int nq, double *A, double *row_const,

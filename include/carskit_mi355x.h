@@ -447,7 +447,10 @@ int cmi_fm_init(cmi_fm_handle h);
 int cmi_fm_sweep(cmi_fm_handle h);
 /* whole buildModel(): cmi_fm_init + num_iters sweeps (the reference has no early stop for FM) */
 int cmi_fm_train(cmi_fm_handle h, int num_iters);
-/* FM.predict (FM.java:93-113) (+ bounding, Recommender.java:306-317) */
+/* FM.predict (FM.java:93-113) (+ bounding, Recommender.java:306-317).  The reference multiplies EVERY entry of w and V by the
+ * feature vector, its zeros included (FM.java:97-98, 103-105): while w or V holds an entry that is an infinity or a NaN, every
+ * prediction whose tuple does not hold that entry's coordinate is NaN (an entry of V: every prediction) -- here and in
+ * cmi_fm_eval_rankings.  (How such entries spread through cmi_fm_init and the sweeps is not modelled.) */
 int cmi_fm_predict_batch(cmi_fm_handle h, int64_t n, const int32_t *u, const int32_t *j, const int32_t *ctx,
                          int bound, double lo, double hi, double *out);
 int cmi_fm_synchronize(cmi_fm_handle h);

@@ -37,8 +37,37 @@ static double feature_of(const orc_fm *m, int64_t i, int32_t l) { /* fvalues.get
     return 0.0;
 }
 
-/* FM.predict (FM.java:93-113) for an arbitrary (u, j, c); zero features add exact zeros and are skipped */
-double orc_fm_predict(const orc_fm *m, int32_t u, int32_t j, int32_t c) {
+/* FM.predict (FM.java:93-113) as written, the dense walk over all p entries: what a model with an entry that is no finite number
+ * needs, because the zero features then add 0 * Inf = NaN (FM.java:98, 104-106) */
+static double predict_dense(const orc_fm *m, int32_t u, int32_t j, int32_t c) {
+    const int32_t iu = u, ij = m->n_users + j, ic = m->n_users + m->n_items + c;
+    const double xc = 1.0 / (double)m->n_ctx_dims;
+    double pred = m->w0;
+    for (int32_t l = 0; l < m->p; ++l) pred += m->w[l] * (l == iu || l == ij ? 1.0 : l == ic ? xc : 0.0);
+    double sum = 0.0;
+    for (int f = 0; f < m->k; ++f) {
+        double sum1 = 0.0, sum2 = 0.0;
+        for (int32_t l = 0; l < m->p; ++l) {
+            double dot = m->V[(size_t)l * m->k + f] * (l == iu || l == ij ? 1.0 : l == ic ? xc : 0.0);
+            sum1 += dot;
+            sum2 += dot * dot;
+        }
+        sum += sum1 * sum1 - sum2;
+    }
+    return pred + 0.5 * sum;
+}
+
+static int all_finite(const orc_fm *m) {
+    for (int32_t l = 0; l < m->p; ++l)
+        if (!isfinite(m->w[l])) return 0;
+    for (size_t i = 0, n = (size_t)m->p * m->k; i < n; ++i)
+        if (!isfinite(m->V[i])) return 0;
+    return 1;
+}
+
+/* the same over the (at most three) features that are not zero: zero features add exact zeros and are skipped -- which holds while
+ * every entry of w and V is finite */
+static double predict_active(const orc_fm *m, int32_t u, int32_t j, int32_t c) {
     int32_t idx[3];
     double val[3];
     int n = 0;
@@ -61,10 +90,16 @@ double orc_fm_predict(const orc_fm *m, int32_t u, int32_t j, int32_t c) {
     return pred + 0.5 * sum;
 }
 
+/* FM.predict (FM.java:93-113) for an arbitrary (u, j, c) */
+double orc_fm_predict(const orc_fm *m, int32_t u, int32_t j, int32_t c) {
+    return all_finite(m) ? predict_active(m, u, j, c) : predict_dense(m, u, j, c);
+}
+
 /* the pre-pass of buildModel (FM.java:117-146): errors[] and Q[][] */
 void orc_fm_init(orc_fm *m) {
+    const int finite = all_finite(m); /* (nothing below writes w or V) */
     for (int64_t i = 0; i < m->size; ++i) {
-        m->errors[i] = m->r[i] - orc_fm_predict(m, m->u[i], m->j[i], m->ctx[i]);
+        m->errors[i] = m->r[i] - (finite ? predict_active(m, m->u[i], m->j[i], m->ctx[i]) : predict_dense(m, m->u[i], m->j[i], m->ctx[i]));
         int32_t idx[3];
         double val[3];
         int n = features(m, i, idx, val);

@@ -33,7 +33,8 @@ def make_fm(data, k, seed, flags=None):
 @pytest.mark.parametrize("k", [1, 4, 64, 70])
 def test_fm_sweeps_match_oracle(k, flags):
     data = util.small_data(n_users=40, n_items=15, n_dims=2, conds_per_dim=3, n=500, seed=51)
-    assert data.n_ctx > data.n_conds or data.n_ctx > 0
+    # both kinds of context ids (FM.java:81-86): with a feature, and (id >= numConditions) without
+    assert (data.ctx < data.n_conds).sum() > 50 and (data.ctx >= data.n_conds).sum() > 50
     orc, g = make_fm(data, k, 3, flags)
     orc.init()
     g.init()
