@@ -58,7 +58,8 @@ def applicable(model, m):
     return any("UIBC"[i] in USES[model] for i in m[1:])
 
 
-# the bars of the GPU module, none of them new: (state atol, loss rtol); None = bit-identical
+# the bars of the GPU module, none of them new: (state atol, loss rtol); None = bit-identical.  (The fp32 pair is the aggregate bar against
+# the fp64 oracle; tests/test_gpu_sgd_f32_bitexact.py holds the same fp32 kernels bit for bit to tests/sgd_f32_ref.py, their fp32 restatement.)
 BARS = {"f32": (3e-4, 3e-5),              # test_owner_f32_vs_oracle_north_star_bar, test_chain_small_k_lane_layouts_bitwise_equal_plain
         "f64": (1e-11, 1e-10),            # test_owner_f64_vs_oracle
         "strict": (None, 1e-12),          # test_level_strict_f64_state_bit_exact, test_owner_strict_f64_state_bit_identical_to_oracle
