@@ -278,6 +278,23 @@ SYMBOLS = [
     ("cmi_ranksgd_assign_host", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp, _vp, C.POINTER(_i64)]),
     ("cmi_ranksgd_sample_host", C.c_int, [C.c_int, C.c_int, _i64, _vp, _vp, _vp, C.c_uint, C.POINTER(_i64), _vp, _vp, _vp, _vp,
                                           C.POINTER(_i64), C.POINTER(_i64)]),
+    ("cmi_cptf_create", C.c_int, [C.c_int, C.c_int, _vp, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_cptf_destroy", C.c_int, [_vp]),
+    ("cmi_cptf_last_error", C.c_char_p, [_vp]),
+    ("cmi_cptf_set_entries", C.c_int, [_vp, _i64, _vp, _vp]),
+    ("cmi_cptf_set_context_keys", C.c_int, [_vp, _i32, _vp]),
+    ("cmi_cptf_set_rating_range", C.c_int, [_vp, _dbl, _dbl]),
+    ("cmi_cptf_set_model", C.c_int, [_vp, _vp]),
+    ("cmi_cptf_get_model", C.c_int, [_vp, _vp]),
+    ("cmi_cptf_iterate", C.c_int, [_vp, _dbl, _dbl, C.POINTER(_dbl)]),
+    ("cmi_cptf_predict_batch", C.c_int, [_vp, _i64, _vp, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_cptf_eval_rankings", C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _dbl, C.c_int, C.c_int,
+                                         C.c_int, _vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp]),
+    ("cmi_cptf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_cptf_ctx_in_lds", C.c_int, [_vp]),
+    ("cmi_cptf_tensor_build", C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, C.c_uint,
+                                        C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _vp, C.POINTER(_i64), _vp, _vp,
+                                        _vp]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -1621,3 +1638,125 @@ class LRMFInstance(_FactorModel):
         out = (_i64 * 5)()
         self._chk(self.L.cmi_lrmf_last_schedule(self.h, out))
         return dict(zip(("levels", "alone", "runs", "widest", "global_units"), (int(x) for x in out)))
+
+
+CPTF_FLAG_STRICT, CPTF_FLAG_GLOBAL_CTX, CPTF_FLAG_KEYS_INDEXOF = 0x1, 0x2, 0x4
+
+
+def cptf_tensor_build(cells, pair_user, pair_item, ctx_conds, cond_dim, test_pairs=(), flags=0):
+    """Host-only: DataDAO.toSparseTensor, TensorRecommender's fold split and getKeys.  cells: (pair, context, rate) in rateMatrix
+    order; ctx_conds[c]: the context's conditions in list order; cond_dim[cond]: its dimension; test_pairs: the pair of every cell
+    of testMatrix in its order.  flags: 0 the reference's keys, CPTF_FLAG_KEYS_INDEXOF the condition's own index.
+    Returns a dict: dims, dim_lists, keys, vals, train_keys, train_vals, test_keys, test_vals, ctx_keys"""
+    pair = np.ascontiguousarray([c[0] for c in cells], dtype=np.int32)
+    ctx = np.ascontiguousarray([c[1] for c in cells], dtype=np.int32)
+    rate = np.ascontiguousarray([c[2] for c in cells], dtype=np.float64)
+    pu, pi = _c32(pair_user), _c32(pair_item)
+    ptr = np.zeros(len(ctx_conds) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(c) for c in ctx_conds])
+    conds = np.ascontiguousarray([x for c in ctx_conds for x in c], dtype=np.int32)
+    cd, tp = _c32(cond_dim), _c32(list(test_pairs))
+    n, D = len(cells), (int(cd.max()) + 1 if len(cd) else 0)
+    nd = C.c_int32()
+    dims, lptr, lst = np.zeros(16, np.int32), np.zeros(D + 2, np.int32), np.zeros(max(len(cd), 1), np.int32)
+    room = max(n, 1) * max(2 + D, 2)
+    keys, trk, tek = (np.zeros(room, np.int32) for _ in range(3))
+    vals, trv, tev = (np.zeros(max(n, 1)) for _ in range(3))
+    ntr, nte = _i64(), _i64()
+    ck = np.zeros(max(len(ctx_conds) * D, 1), np.int32)
+    rc = lib().cmi_cptf_tensor_build(n, _p(pair), _p(ctx), _p(rate), len(pu), _p(pu), _p(pi), len(ctx_conds), _p(ptr), _p(conds), len(cd),
+                                     _p(cd), len(tp), _p(tp), int(flags), C.byref(nd), _p(dims), _p(lptr), _p(lst), _p(keys), _p(vals),
+                                     C.byref(ntr), _p(trk), _p(trv), C.byref(nte), _p(tek), _p(tev), _p(ck))
+    if rc != OK:
+        raise CmiError(rc, lib().cmi_cptf_last_error(None).decode())
+    w = nd.value
+    return {"dims": dims[:w].tolist(), "dim_lists": [lst[lptr[d]:lptr[d + 1]].tolist() for d in range(w - 2)],
+            "keys": keys[:n * w].reshape(n, w).copy(), "vals": vals[:n].copy(),
+            "train_keys": trk[:ntr.value * w].reshape(-1, w).copy(), "train_vals": trv[:ntr.value].copy(),
+            "test_keys": tek[:nte.value * w].reshape(-1, w).copy(), "test_vals": tev[:nte.value].copy(),
+            "ctx_keys": ck[:len(ctx_conds) * (w - 2)].reshape(len(ctx_conds), w - 2).copy()}
+
+
+class CPTFInstance(_Handle):
+    """The reference's CPTF on one GPU (a `cmi_cptf_handle`): one factor matrix (dims[d], k) per tensor dimension -- user, item, then
+    one per context dimension.  1 <= k <= 128, 2 <= len(dims) <= 10."""
+
+    _api = ("cmi_cptf_create", "cmi_cptf_destroy", "cmi_cptf_last_error")
+
+    def __init__(self, k, dims, device=0, flags=0):
+        self.k, self.dims = k, [int(d) for d in dims]
+        self.n_users, self.n_items = (self.dims + [0, 0])[:2]
+        d = np.ascontiguousarray(self.dims, dtype=np.int32)
+        super().__init__(k, len(self.dims), _p(d), device, flags)
+
+    def _keys(self, keys, width):
+        keys = np.ascontiguousarray(keys, dtype=np.int32).reshape(-1, width) if width else np.zeros((len(keys), 0), np.int32)
+        return np.ascontiguousarray(keys)
+
+    def set_entries(self, keys, r):
+        """trainTensor in iterator order: keys (n, len(dims)) and the rates"""
+        keys, r = self._keys(keys, len(self.dims)), np.ascontiguousarray(r, dtype=np.float64)
+        if len(keys) != len(r):
+            raise CmiError(E_INVALID, "%d key tuples for %d rates" % (len(keys), len(r)))
+        self._chk(self.L.cmi_cptf_set_entries(self.h, len(r), _p(keys), _p(r)))
+
+    def set_context_keys(self, ctx_keys):
+        """TensorRecommender.getKeys' keys of every context id: (n_ctx, len(dims) - 2)"""
+        ctx_keys = self._keys(ctx_keys, len(self.dims) - 2)
+        self._chk(self.L.cmi_cptf_set_context_keys(self.h, len(ctx_keys), _p(ctx_keys)))
+
+    def set_rating_range(self, min_rate, max_rate):
+        self._chk(self.L.cmi_cptf_set_rating_range(self.h, float(min_rate), float(max_rate)))
+
+    def set_model(self, M):
+        """M: one (dims[d], k) matrix per dimension"""
+        if len(M) != len(self.dims):
+            raise CmiError(E_INVALID, "%d matrices for %d dimensions" % (len(M), len(self.dims)))
+        parts = []
+        for d, a in enumerate(M):
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (self.dims[d], self.k):
+                raise CmiError(E_INVALID, "M[%d] has shape %s, not %s" % (d, a.shape, (self.dims[d], self.k)))
+            parts.append(a.ravel())
+        flat = np.ascontiguousarray(np.concatenate(parts))
+        self._chk(self.L.cmi_cptf_set_model(self.h, _p(flat)))
+
+    def model(self):
+        """[M[0], ..., M[len(dims) - 1]]"""
+        flat = np.empty(sum(self.dims) * self.k)
+        self._chk(self.L.cmi_cptf_get_model(self.h, _p(flat)))
+        out, at = [], 0
+        for n in self.dims:
+            out.append(flat[at:at + n * self.k].reshape(n, self.k).copy())
+            at += n * self.k
+        return out
+
+    def iterate(self, lrate, reg):
+        """one iteration of CPTF.buildModel's loop; returns the loss (a CmiError of code E_NUMERIC carries a non-finite one as .loss)"""
+        loss = _dbl()
+        rc = self.L.cmi_cptf_iterate(self.h, float(lrate), float(reg), C.byref(loss))
+        if rc != OK:
+            err = CmiError(rc, self.L.cmi_cptf_last_error(self.h).decode())
+            err.loss = loss.value
+            raise err
+        return loss.value
+
+    def predict(self, keys, bound=False, lo=0.0, hi=0.0):
+        """CPTF.predict(keys) of (n, len(dims)) key tuples; bound: clamped to [lo, hi]"""
+        keys = self._keys(keys, len(self.dims))
+        out = np.empty(len(keys))
+        self._chk(self.L.cmi_cptf_predict_batch(self.h, len(keys), _p(keys), 1 if bound else 0, float(lo), float(hi), _p(out)))
+        return out
+
+    def eval_rankings(self, train, test, bin_thold=-1.0, num_recs=10, num_ignore=0, strategy="ucu", with_lists=False):
+        return _eval_rankings(self.L.cmi_cptf_eval_rankings, self._chk, self.h, train, test, bin_thold, num_recs, num_ignore, strategy,
+                              with_lists)
+
+    def last_iter_ms(self):
+        """(epoch, loss sum) device milliseconds of the last iterate() and the scoring loop of the last eval_rankings()"""
+        ms = (C.c_float * 3)()
+        self._chk(self.L.cmi_cptf_last_iter_ms(self.h, ms))
+        return tuple(ms)
+
+    def ctx_in_lds(self):
+        return bool(self.L.cmi_cptf_ctx_in_lds(self.h))

@@ -39,6 +39,7 @@ struct Dao {
         d.r.resize(n);
         cmi_dao_matrix(h, ui.data(), d.ctx.data(), d.r.data());
         cmi_dao_ui_maps(h, uiu.data(), uii.data());
+        d.pair = ui;
         d.u.resize(n);
         d.j.resize(n);
         for (size_t t = 0; t < n; ++t) {
@@ -53,6 +54,7 @@ struct Dao {
             int32_t n_empty = 0;
             cmi_dao_cond_info(h, cond_dim.data(), empty.data(), &n_empty);
             d.empty_conds.assign(empty.begin(), empty.begin() + n_empty);
+            d.cond_dim.assign(cond_dim.begin(), cond_dim.begin() + counts[4]);
         }
         int32_t ns = 0;
         cmi_dao_rating_scale(h, nullptr, 0, &ns);
@@ -161,6 +163,9 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
         // LRMF: a top-N model on one GPU
         if (a == "lrmf" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": LRMF runs on one GPU");
+        // CPTF: one dependency chain, one GPU
+        if (a == "cptf" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": CPTF runs on one GPU");
         // RankSGD: a top-N model on one GPU; its constructor calls checkBinary() (RankSGD.java:58, Recommender.java:1154-1160)
         if (a == "ranksgd" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": RankSGD runs on one GPU");
@@ -261,6 +266,7 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
     } else if (mode == "test-set") {
         Dao testDao(work + "test.csv", rateDao.h);
         RatingData test = testDao.ratingData();
+        test.pair.clear(); // its rows are another matrix's: CPTF, which builds its tensor from rateMatrix alone, refuses
         RatingData train = data; // id spaces of the union (the shared maps were extended by the test DAO)
         train.n_users = test.n_users;
         train.n_items = test.n_items;

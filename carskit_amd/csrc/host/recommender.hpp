@@ -72,14 +72,17 @@ struct RatingData {
     int32_t n_users = 0, n_items = 0, n_conds = 0, n_dims = 0;
     std::vector<int32_t> u, j, ctx;
     std::vector<double> r;
+    std::vector<int32_t> pair;        // the tuple's row of rateMatrix (its user-item pair id); empty where the source has none
+    std::vector<int32_t> cond_dim;    // condition -> context dimension (DataDAO.condDimensionMap)
     std::vector<int32_t> ctx_ptr, ctx_conds;
     std::vector<int32_t> empty_conds; // EmptyContextConditions (DataDAO.java:213-214): the ":na" conditions in header order
     double min_rate = 1, max_rate = 5;
     int64_t n() const { return (int64_t)r.size(); }
     RatingData subset(const std::vector<int64_t> &idx) const {
         RatingData d = *this;
-        d.u.clear(), d.j.clear(), d.ctx.clear(), d.r.clear();
+        d.u.clear(), d.j.clear(), d.ctx.clear(), d.r.clear(), d.pair.clear();
         for (int64_t t : idx) {
+            if (!pair.empty()) d.pair.push_back(pair[(size_t)t]);
             d.u.push_back(u[(size_t)t]);
             d.j.push_back(j[(size_t)t]);
             d.ctx.push_back(ctx[(size_t)t]);
@@ -144,6 +147,10 @@ struct Conf {
     // RankSGD=-numrates size|reference: what RankSGD.java:71 divides by.  `reference` (and the absent key) is the reference as it stands:
     // numRates is never assigned (Recommender.java:141), so the divisor is 0; `size` is the number of ratings of the 2-D train matrix
     bool ranksgdNumRatesSize = false;
+    // CPTF=-keys reference|indexof: the keys of the training tensor.  `reference` (and the absent key) is DataDAO.java:461 as it stands
+    // (a condition already listed gets its list's last index); `indexof` gives the condition's own index, what getKeys uses
+    bool cptfKeysIndexOf = false;
+    double reg = java_float("0.01"); // reg.lambda's main parameter (Recommender.java: reg), what CPTF.java:104-106 uses
     std::shared_ptr<int64_t> bprStream; // BPR: the 48-bit state of happy.coding's Randoms stream, shared by the folds of a run (null: from randSeed)
     Conf() {}
     explicit Conf(const FileConfiger &cf) {
@@ -156,7 +163,7 @@ struct Conf {
         }
         if (cf.contains("reg.lambda")) {
             LineConfiger ro = cf.getParamOptions("reg.lambda");
-            const double reg = java_float(ro.getMainParam());
+            reg = java_float(ro.getMainParam());
             regU = ro.getFloat("-u", reg);
             regI = ro.getFloat("-i", reg);
             regB = ro.getFloat("-b", reg);
@@ -209,6 +216,11 @@ struct Conf {
             const std::string v = lower(cf.getParamOptions("RankSGD").getString("-numrates", "reference"));
             if (v != "size" && v != "reference") throw std::runtime_error("RankSGD=-numrates " + v + ": size or reference");
             ranksgdNumRatesSize = v == "size";
+        }
+        if (cf.contains("CPTF")) {
+            const std::string v = lower(cf.getParamOptions("CPTF").getString("-keys", "reference"));
+            if (v != "indexof" && v != "reference") throw std::runtime_error("CPTF=-keys " + v + ": indexof or reference");
+            cptfKeysIndexOf = v == "indexof";
         }
         if (cf.contains("FM")) {
             LineConfiger fm = cf.getParamOptions("FM");
@@ -1079,6 +1091,128 @@ class RankSGD : public PairRecommender<cmi_ranksgd_handle, cmi_ranksgd_destroy, 
     void predictBounded(double *) override { throw std::runtime_error("RankSGD is a top-N recommender: it has no rating evaluation"); }
 };
 
+// src/carskit/alg/cars/adaptation/independent/CPTF.java on src/carskit/generic/TensorRecommender.java: one factor matrix per
+// dimension of the rating tensor (user, item, one per context dimension).  Parameters: num.factors, num.max.iter, learn.rate,
+// reg.lambda (its main parameter); CPTF=-keys reference|indexof (see Conf).  The tensor, the fold's train and test tensors and
+// getKeys' table are the library's (cmi_cptf_tensor_build: DataDAO.java:423-481, TensorRecommender.java:62-84, :189-205) over
+// rateMatrix = the fold's train and test tuples together, in rateMatrix order (pair, then context).
+class CPTF : public IterativeRecommender {
+  public:
+    CPTF(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : IterativeRecommender(-1, "CPTF", true, tr, te, fold, c, log) {}
+    ~CPTF() override {
+        if (t_) cmi_cptf_destroy(t_);
+    }
+    // TensorRecommender.java:53-84 (the tensors), then CPTF.java:46-55: M[d].init(1, 0.1) per dimension in d order, row by row
+    void initModel() override {
+        buildTensors();
+        JavaRandom rnd(conf_.randSeed);
+        size_t total = 0;
+        for (int32_t d : dims) total += (size_t)d * (size_t)conf_.numFactors;
+        M.resize(total);
+        for (double &x : M) x = 1.0 + 0.1 * rnd.nextGaussian();
+    }
+    void buildModel() override { // CPTF.java:75-115
+        // pred and the loss as the reference's chains up to 2^18 loss terms; else the fixed tree and the loss by parts
+        const int64_t terms = (int64_t)train_vals.size() * (1 + (int64_t)conf_.numFactors * (int64_t)dims.size());
+        check(cmi_cptf_create(conf_.numFactors, (int)dims.size(), dims.data(), conf_.device, terms <= ((int64_t)1 << 18) ? CMI_CPTF_FLAG_STRICT : 0u,
+                              &t_), "cmi_cptf_create");
+        check(cmi_cptf_set_entries(t_, (int64_t)train_vals.size(), train_keys.data(), train_vals.data()), "cmi_cptf_set_entries");
+        check(cmi_cptf_set_model(t_, M.data()), "cmi_cptf_set_model");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_cptf_iterate(t_, lRate, conf_.reg, &loss);
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_cptf_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        check(cmi_cptf_get_model(t_, M.data()), "cmi_cptf_get_model");
+    }
+    // TensorRecommender.java:86-164 (view "all"): the bounded predict(keys) of every entry of the TEST TENSOR in iterator order
+    Measures evalRatings() override {
+        const double lo = trainMatrix.min_rate, hi = trainMatrix.max_rate;
+        std::vector<double> pred(test_vals.size());
+        check(cmi_cptf_predict_batch(t_, (int64_t)pred.size(), test_keys.data(), 1, lo, hi, pred.data()), "cmi_cptf_predict_batch");
+        double sa = 0, ss = 0, sra = 0, srs = 0;
+        int64_t n = 0, pe = 0;
+        for (size_t t = 0; t < pred.size(); ++t) {
+            if (std::isnan(pred[t])) continue;
+            const double rp = std::floor(pred[t] / lo + 0.5) * lo; // Math.round
+            const double e = std::fabs(test_vals[t] - pred[t]), re = std::fabs(test_vals[t] - rp);
+            sa += e, ss += e * e, sra += re, srs += re * re;
+            ++n;
+            if (re > 1e-5) ++pe;
+        }
+        const double mae = sa / (double)n;
+        return Measures{{"MAE", mae}, {"RMSE", std::sqrt(ss / (double)n)}, {"NMAE", mae / (hi - lo)}, {"rMAE", sra / (double)n},
+                        {"rRMSE", std::sqrt(srs / (double)n)}, {"MPE", ((double)pe + 0.0) / (double)n}};
+    }
+    // Recommender.java:668-964 with ranking(u, j, c) = CPTF.predict(u, j, c): getKeys' keys, clamped (CPTF.java:119-139)
+    Measures evalRankings() override {
+        static const char *names[CMI_RANK_MEASURES] = {"Pre5", "Pre10", "PreN", "Rec5", "Rec10", "RecN", "AUC5", "AUC10", "AUCN",
+                                                       "MAP5", "MAP10", "MAPN", "NDCG5", "NDCG10", "NDCGN", "MRR5", "MRR10",
+                                                       "MRRN", "D5", "D10", "DN"};
+        check(cmi_cptf_set_context_keys(t_, (int32_t)(trainMatrix.ctx_ptr.size() - 1), ctx_keys.data()), "cmi_cptf_set_context_keys");
+        check(cmi_cptf_set_rating_range(t_, trainMatrix.min_rate, trainMatrix.max_rate), "cmi_cptf_set_rating_range");
+        double out[CMI_RANK_MEASURES];
+        int64_t nq = 0;
+        check(cmi_cptf_eval_rankings(t_, trainMatrix.n(), trainMatrix.u.data(), trainMatrix.j.data(), trainMatrix.ctx.data(),
+                                     trainMatrix.r.data(), testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), testMatrix.ctx.data(),
+                                     testMatrix.r.data(), conf_.binThold, conf_.numRecs, conf_.numIgnore,
+                                     conf_.evalStrategy == "uc" ? CMI_RANK_UC : CMI_RANK_UCU, out, &nq, nullptr, nullptr, nullptr, nullptr,
+                                     nullptr), "cmi_cptf_eval_rankings");
+        Measures m;
+        for (int i = 0; i < CMI_RANK_MEASURES; ++i) m[names[i]] = out[i];
+        return m;
+    }
+    void saveModel() override {
+        if (log_) log_("--save-model: not available for " + algoName);
+    }
+    std::vector<int32_t> dims, train_keys, test_keys, ctx_keys; // the tensors' sizes, entries in iterator order, getKeys per context
+    std::vector<double> train_vals, test_vals, M;               // M[0] .. M[n_dims - 1] concatenated, each dims[d] x numFactors
+
+  private:
+    void check(int rc, const char *what) { // (a failed create, and the tensor build, leave t_ null: the thread's message)
+        if (rc != CMI_OK) throw std::runtime_error(std::string(what) + ": " + cmi_cptf_last_error(t_));
+    }
+    void buildTensors() {
+        if (trainMatrix.pair.size() != trainMatrix.r.size() || testMatrix.pair.size() != testMatrix.r.size())
+            throw std::runtime_error("CPTF: the rating tensor is built from one rating matrix; a separate test set has no rows in it");
+        // rateMatrix: the train and test tuples together in its iteration order (row = pair, then column = context)
+        struct Cell { int32_t pair, ctx; double r; };
+        std::vector<Cell> cells;
+        int32_t n_pairs = 0;
+        for (const RatingData *d : {&trainMatrix, &testMatrix})
+            for (size_t t = 0; t < d->r.size(); ++t) {
+                cells.push_back({d->pair[t], d->ctx[t], d->r[t]});
+                n_pairs = std::max(n_pairs, d->pair[t] + 1);
+            }
+        std::sort(cells.begin(), cells.end(), [](const Cell &a, const Cell &b) { return a.pair != b.pair ? a.pair < b.pair : a.ctx < b.ctx; });
+        std::vector<int32_t> pair(cells.size()), ctx(cells.size()), pu((size_t)n_pairs, 0), pi((size_t)n_pairs, 0);
+        std::vector<double> rate(cells.size());
+        for (size_t t = 0; t < cells.size(); ++t) pair[t] = cells[t].pair, ctx[t] = cells[t].ctx, rate[t] = cells[t].r;
+        for (const RatingData *d : {&trainMatrix, &testMatrix})
+            for (size_t t = 0; t < d->r.size(); ++t) pu[(size_t)d->pair[t]] = d->u[t], pi[(size_t)d->pair[t]] = d->j[t];
+        const size_t n = cells.size(), n_ctx = trainMatrix.ctx_ptr.size() - 1, w = 2 + (size_t)std::max(1, trainMatrix.n_dims);
+        int32_t nd = 0;
+        int64_t n_train = 0, n_test = 0;
+        std::vector<int32_t> d10(16), lptr(16), lst(trainMatrix.cond_dim.size() + 1), keys(n * w + 1);
+        std::vector<double> vals(n + 1);
+        train_keys.assign(n * w + 1, 0), test_keys.assign(n * w + 1, 0), train_vals.assign(n + 1, 0.0), test_vals.assign(n + 1, 0.0);
+        ctx_keys.assign(n_ctx * w + 1, 0);
+        check(cmi_cptf_tensor_build((int64_t)n, pair.data(), ctx.data(), rate.data(), n_pairs, pu.data(), pi.data(), (int32_t)n_ctx,
+                                    trainMatrix.ctx_ptr.data(), trainMatrix.ctx_conds.data(), (int32_t)trainMatrix.cond_dim.size(),
+                                    trainMatrix.cond_dim.data(), testMatrix.n(), testMatrix.pair.data(),
+                                    conf_.cptfKeysIndexOf ? CMI_CPTF_FLAG_KEYS_INDEXOF : 0u, &nd, d10.data(), lptr.data(), lst.data(), keys.data(),
+                                    vals.data(), &n_train, train_keys.data(), train_vals.data(), &n_test, test_keys.data(), test_vals.data(),
+                                    ctx_keys.data()), "cmi_cptf_tensor_build");
+        dims.assign(d10.begin(), d10.begin() + nd);
+        train_keys.resize((size_t)n_train * (size_t)nd), train_vals.resize((size_t)n_train);
+        test_keys.resize((size_t)n_test * (size_t)nd), test_vals.resize((size_t)n_test);
+        ctx_keys.resize(n_ctx * (size_t)(nd - 2));
+    }
+    cmi_cptf_handle t_ = nullptr;
+};
+
 // the factory switch of CARSKit.getRecommender (src/carskit/main/CARSKit.java:461-469,700-712,742), lower-cased names
 inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &name, const RatingData &tr, const RatingData &te,
                                                             int fold, const Conf &c, Logger log) {
@@ -1102,8 +1236,9 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
     if (n == "bpr") return std::unique_ptr<IterativeRecommender>(new BPR(tr, te, fold, c, log));
     if (n == "lrmf") return std::unique_ptr<IterativeRecommender>(new LRMF(tr, te, fold, c, log));
+    if (n == "cptf") return std::unique_ptr<IterativeRecommender>(new CPTF(tr, te, fold, c, log));         // CARSKit.java:693-697
     if (n == "ranksgd") return std::unique_ptr<IterativeRecommender>(new RankSGD(tr, te, fold, c, log));   // CARSKit.java:479-480
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, slim, rankals, bpr, lrmf, ranksgd, itemknn, userknn, slopeone, nmf)");
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, cptf, slim, rankals, bpr, lrmf, ranksgd, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

@@ -979,6 +979,76 @@ int cmi_ranksgd_assign_host(int n_users, int n_items, int64_t n, const int32_t *
 int cmi_ranksgd_sample_host(int n_users, int n_items, int64_t n, const int32_t *u, const int32_t *i, const double *r, unsigned flags,
                             int64_t *state, int32_t *ou, int32_t *oi, int32_t *oj, double *orr, int64_t *n_cells, int64_t *tries_used);
 
+/* ---- CPTF (src/carskit/alg/cars/adaptation/independent/CPTF.java on src/carskit/generic/TensorRecommender.java; cptf_api.cpp,
+ * cptf_kernels.hip) ---------------------------------------------------------------------------------------------------------------
+ * CP tensor factorisation, fp64: one factor matrix M[d] (dims[d] x k) per dimension of the rating tensor -- dimension 0 the user,
+ * 1 the item, one more per context dimension -- and pred(keys) = sum_f prod_d M[d][keys[d]][f].  An iteration sweeps the train
+ * entries in the tensor's iterator order; nearly every entry touches the same few context rows, so the sweep is one dependency chain
+ * and runs as one wave that owns the factors (cptf_kernels.hip).  The caller supplies the entries' keys as the reference's tensor holds
+ * them and, for ranking, the keys TensorRecommender.getKeys gives every context id: the two differ in the reference
+ * (DataDAO.java:456-462 gives a condition that is already listed the LAST index of its dimension's list, getKeys uses indexOf).
+ * 1 <= k <= 128, 2 <= n_dims <= 10.  No CPU fallback: without a device cmi_cptf_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_cptf_instance *cmi_cptf_handle;
+#define CMI_CPTF_FLAG_STRICT 0x1u     /* pred as the reference's chain over f, the loss as its chain over (entry, f, d): bit for bit; a slot
+                                       * per loss term, at most CMI_CPTF_STRICT_MAX_TERMS of them (small data) */
+#define CMI_CPTF_STRICT_MAX_TERMS (1LL << 27) /* 1 GiB of slots, summed by one thread */
+#define CMI_CPTF_FLAG_GLOBAL_CTX 0x2u /* context rows travel through memory even where they would fit the LDS budget */
+/* CPTF.java:46-55, TensorRecommender.java:62-84.  dims: n_dims sizes.  k > 128, n_dims < 2 or > 10 -> CMI_E_UNSUPPORTED */
+int cmi_cptf_create(int k, int n_dims, const int32_t *dims, int device, unsigned flags, cmi_cptf_handle *out);
+int cmi_cptf_destroy(cmi_cptf_handle h);
+const char *cmi_cptf_last_error(cmi_cptf_handle h);
+/* trainTensor as CPTF.java:81 iterates it: keys (n x n_dims, row-major) and the rates.  An entry with rate <= 0 takes no part
+ * (:85-86).  A key outside its dimension -> CMI_E_INVALID; with CMI_CPTF_FLAG_STRICT more than CMI_CPTF_STRICT_MAX_TERMS loss terms
+ * (entries x (1 + k x n_dims)) -> CMI_E_UNSUPPORTED */
+int cmi_cptf_set_entries(cmi_cptf_handle h, int64_t n, const int32_t *keys, const double *r);
+/* TensorRecommender.java:189-205: the keys of the dimensions 2 .. n_dims - 1 for every context id (n_ctx x (n_dims - 2)), what
+ * CPTF.predict(u, j, c) and so evalRankings use.  A key outside its dimension -> CMI_E_INVALID */
+int cmi_cptf_set_context_keys(cmi_cptf_handle h, int32_t n_ctx, const int32_t *ctx_keys);
+/* minRate and maxRate, which CPTF.java:133-136 clamps the ranking score to (Recommender.java's rating scale) */
+int cmi_cptf_set_rating_range(cmi_cptf_handle h, double min_rate, double max_rate);
+/* CPTF.java:46-55: M[0] .. M[n_dims - 1] concatenated, each dims[d] x k row-major; the caller draws them */
+int cmi_cptf_set_model(cmi_cptf_handle h, const double *M);
+int cmi_cptf_get_model(cmi_cptf_handle h, double *M);
+/* CPTF.java:80-111: one iteration; *loss as after :111.  NaN/Inf loss (:103 divides by an element without a guard) -> CMI_E_NUMERIC
+ * with *loss set */
+int cmi_cptf_iterate(cmi_cptf_handle h, double lrate, double reg, double *loss);
+/* CPTF.java:141-155 of n key tuples (n x n_dims), the sum in the reference's order; bound: clamped to [lo, hi] as
+ * TensorRecommender.java:86-164 bounds what it evaluates */
+int cmi_cptf_predict_batch(cmi_cptf_handle h, int64_t n, const int32_t *keys, int bound, double lo, double hi, double *out);
+/* Recommender.java:630-860 with ranking(u, j, c) = CPTF.predict(u, j, c) (CPTF.java:119-139: getKeys' keys, clamped); arguments,
+ * outputs and semantics exactly as cmi_eval_rankings.  A context id with no keys set -> CMI_E_INVALID */
+int cmi_cptf_eval_rankings(cmi_cptf_handle h, int64_t n_train, const int32_t *tu, const int32_t *tj, const int32_t *tctx, const double *tr,
+                           int64_t n_test, const int32_t *su, const int32_t *sj, const int32_t *sctx, const double *sr, double bin_thold,
+                           int num_recs, int num_ignore, int strategy, double out[21], int64_t *n_queries, int32_t *q_user, int32_t *q_ctx,
+                           int32_t *q_count, int32_t *top_items, double *top_scores);
+/* by events: ms[0] the epoch and ms[1] the loss sum of the last cmi_cptf_iterate (0 before one), ms[2] the last
+ * cmi_cptf_eval_rankings.  Before both -> CMI_E_INVALID */
+int cmi_cptf_last_iter_ms(cmi_cptf_handle h, float ms[3]);
+/* 1: the last iteration kept the context rows in LDS; 0: in memory */
+int cmi_cptf_ctx_in_lds(cmi_cptf_handle h);
+/* without a device or a handle: DataDAO.toSparseTensor (DataDAO.java:423-481), the fold split of TensorRecommender's constructor
+ * (TensorRecommender.java:62-84) and getKeys (:189-205).
+ * In: rateMatrix as n_cells cells (pair, ctx, rate) in its iteration order (rows = user-item pairs, then columns = contexts); the
+ * pairs' users and items; context c's conditions ctx_conds[ctx_ptr[c] .. ctx_ptr[c + 1]) in list order, one per dimension; cond_dim:
+ * condition -> context dimension (0 .. D - 1); testMatrix as the pair of each of its n_test cells, in its order.
+ * flags: 0 builds the keys as the reference does (DataDAO.java:461: a condition already listed gets its list's LAST index);
+ * CMI_CPTF_FLAG_KEYS_INDEXOF gives the condition's own index.
+ * Out: *n_dims = 2 + D and dims; dimension d's condition list dim_list[dim_list_ptr[d] .. dim_list_ptr[d + 1]) (D + 1 and n_conds
+ * entries of room); the rate tensor's keys (n_cells x n_dims) and vals; the train and the test tensor of the fold in iterator order
+ * (n_cells entries of room each; every context of a test pair moves to the test tensor, and contexts of a pair that share keys are
+ * one test entry with the value set last); ctx_keys (n_ctx x D): getKeys' keys of every context.
+ * dims[0] and dims[1] count the DISTINCT users and items, as the reference does, while the keys are the ids: an id not below that count
+ * builds here as there and is refused by cmi_cptf_set_entries (the reference indexes its factor matrix out of range).
+ * A context whose getKeys gives -1 (named with its dimension and condition) -> CMI_E_INVALID; no context dimension (librec's SparseTensor refuses fewer than 3
+ * dimensions), more than 10 dimensions, a HashSet of positions with a tree bin -> CMI_E_UNSUPPORTED.  The message: cmi_cptf_last_error(NULL) */
+#define CMI_CPTF_FLAG_KEYS_INDEXOF 0x4u
+int cmi_cptf_tensor_build(int64_t n_cells, const int32_t *pair, const int32_t *ctx, const double *rate, int32_t n_pairs,
+                          const int32_t *pair_user, const int32_t *pair_item, int32_t n_ctx, const int32_t *ctx_ptr, const int32_t *ctx_conds,
+                          int32_t n_conds, const int32_t *cond_dim, int64_t n_test, const int32_t *test_pair, unsigned flags,
+                          int32_t *n_dims, int32_t *dims, int32_t *dim_list_ptr, int32_t *dim_list, int32_t *keys, double *vals,
+                          int64_t *n_train, int32_t *train_keys, double *train_vals, int64_t *n_test_out, int32_t *test_keys,
+                          double *test_vals, int32_t *ctx_keys);
+
 #ifdef __cplusplus
 }
 #endif
