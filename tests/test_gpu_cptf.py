@@ -70,10 +70,10 @@ def test_tree_form_rating_measures_within_the_parity_bound_of_the_reference_pinn
         assert abs(mae - want["MAE"]) <= 1e-5 and abs(rmse - want["RMSE"]) <= 1e-5, run["name"]
 
 
-def draw_model(rng, dims, k, total=None):
+def draw_model(rng, dims, k, total=None, spread=0.1):
     """CPTF.initModel's draw, elements around 1; total: scaled so that a prediction lies around `total`"""
     scale = 1.0 if total is None else (total / k) ** (1.0 / len(dims))
-    return [scale * (1.0 + 0.1 * rng.standard_normal((n, k))) for n in dims]
+    return [scale * (1.0 + spread * rng.standard_normal((n, k))) for n in dims]
 
 
 def draw_entries(rng, dims, n):
@@ -93,9 +93,10 @@ def dims_for(n_dims):
     return [3, 4] + [2, 3, 2, 3, 2, 3, 2, 3][:n_dims - 2]
 
 
-def run_forms(dims, k, keys, r, seed, sum_forms=SUM_FORMS, ctx_forms=CTX_FORMS, iters=ITERS):
+def run_forms(dims, k, keys, r, seed, sum_forms=SUM_FORMS, ctx_forms=CTX_FORMS, iters=ITERS, M0=None):
     rng = np.random.default_rng(seed)
-    M0 = draw_model(rng, dims, k, total=3.0)                         # inside the ratings' range: the run stays finite at every k
+    if M0 is None:
+        M0 = draw_model(rng, dims, k, total=3.0)                     # inside the ratings' range: the run stays finite at every k
     for sname, sflag, ref_epoch in sum_forms:
         want_M, want_loss = [m.copy() for m in M0], []
         for _ in range(iters):
@@ -198,9 +199,10 @@ def test_predict_matches_the_restatement(k, n_dims):
 
 
 # ---- top-N ---------------------------------------------------------------------------------------------------------------------------
-def rank_case(n_cand, seed, n_users=6, n_ctx=4):
+def rank_case(n_cand, seed, n_users=6, n_ctx=4, ids=None):
     """train tuples that make the items 0 .. n_cand - 1 the candidates, and test tuples of some users in some contexts: a 2-D matrix
-    in which every item has a cell, spread over contexts and split by the helper the other top-N tests use"""
+    in which every item has a cell, spread over contexts and split by the helper the other top-N tests use; ids: the item id that
+    stands for item j in the tuples (a catalogue larger than the candidate set)"""
     rng = np.random.default_rng(seed)
     cells = {(int(rng.integers(0, n_users)), j): float(rng.integers(1, 6)) for j in range(n_cand)}
     for u in range(n_users):
@@ -211,6 +213,8 @@ def rank_case(n_cand, seed, n_users=6, n_ctx=4):
     tr, te = tup(tr), tup(te)
     have = {j for _, j, _, _ in tr}
     tr += [(0, j, 0, 3.0) for j in range(n_cand) if j not in have]                   # (an item whose every tuple went to the test side)
+    if ids is not None:
+        tr, te = ([(u, int(ids[j]), c, v) for u, j, c, v in d] for d in (tr, te))
     return sorted(tr), [t for t in te if (t[0], t[1], t[2]) not in {(a, b, c) for a, b, c, _ in tr}]
 
 
@@ -219,16 +223,22 @@ def cols(tuples):
             np.array([t[3] for t in tuples]))
 
 
-def check_rankings(M, dims, k, ctx_keys, lo, hi, tr, te, **kw):
+def check_rankings(M, dims, k, ctx_keys, lo, hi, tr, te, h=None, got=None, **kw):
     """the lists entry for entry and score for score, the measures within the tolerance the other fp64 top-N tests use, against the
-    ranking restatement fed with cptf_ref's scores"""
-    h = capi.CPTFInstance(k, dims)
-    h.set_model(M)
-    h.set_context_keys(ctx_keys)
-    h.set_rating_range(lo, hi)
+    ranking restatement fed with cptf_ref's scores; h: a handle that holds M, ctx_keys and the range already, and stays open; got: a
+    list that takes the device's (measures, lists)"""
+    own = h is None
+    if own:
+        h = capi.CPTFInstance(k, dims)
+        h.set_model(M)
+        h.set_context_keys(ctx_keys)
+        h.set_rating_range(lo, hi)
     res, lists = h.eval_rankings(cols(tr), cols(te), with_lists=True, **kw)
     assert h.last_iter_ms()[2] > 0.0
-    h.close()
+    if own:
+        h.close()
+    if got is not None:
+        got.append((res, lists))
     score = functools.lru_cache(maxsize=None)(lambda u, c: cref.score_items(M, u, ctx_keys[c], lo, hi))
     ref, ref_lists = rank_oracle.eval_rankings(lambda u, j, c: score(u, c)[j], tr, te, **kw)
     assert len(ref_lists) > 0 and set(lists) == set(ref_lists)
