@@ -6,6 +6,7 @@ Pinned to the reference's own source by tests/golden/reference_nmf.json.gz (test
     W, Ht = float64 arrays (n_users, k), (n_items, k)   # H item-major: Ht[j][f] = H[f][j]
     loss = iterate(W, Ht, rows, cols)         # one pass of buildModel()'s loop, in place: W phase, H phase, loss
     predict(W, Ht, u, j)                      # DenseMatrix.product(W, u, H, j)
+    loss_tree(loss_cells(W, Ht, rows))        # the loss in the DEVICE's fixed summation order (not the reference's chain), bit for bit
 
 Every sum is a left-to-right chain from 0.0: product() over f, DenseVector.inner(SparseVector) over the vector's entries in ascending
 index order (its term is sv.get(j) * dv.get(j); the product commutes).  numpy does the arithmetic across the INDEPENDENT axis only (all
@@ -79,6 +80,42 @@ def loss_terms(W, Ht, rows):
     r = np.concatenate([val for _, val in rows] + [np.zeros(0)])
     e = products(W, Ht, u, j) - r
     return (e * e)[r > 0]
+
+
+def loss_cells(W, Ht, rows):
+    """the loss term of every stored non-zero cell in CRS order, in place: (predict(u, j) - r)^2, and 0.0 where r > 0 does not hold (the
+    device gives such a cell a lane of its own that adds +0.0; loss_terms leaves it out, which moves every later cell's place)"""
+    u = np.concatenate([np.full(len(idx), a, np.int64) for a, (idx, _) in enumerate(rows)] + [np.zeros(0, np.int64)])
+    j = np.concatenate([idx for idx, _ in rows] + [np.zeros(0, np.int64)])
+    r = np.concatenate([val for _, val in rows] + [np.zeros(0)])
+    e = products(W, Ht, u, j) - r
+    return np.where(r > 0, e * e, 0.0)
+
+
+LOSS_BLOCK = 256  # NMF_BLOCK: cells of a loss block, four waves of 64
+
+
+def loss_partials(cells):
+    """the device's partial of every loss block: the cells in order, LOSS_BLOCK a block, the last block padded with 0.0.
+    A wave of 64 folds its terms in halves, t[l] + t[l + 32] for l < 32, then + 16, + 8, + 4, + 2, + 1; the block is ((w0 + w1) + w2) +
+    w3.  All blocks, waves and the lanes of one fold side by side: none of them feeds another."""
+    cells = np.asarray(cells, np.float64)
+    blocks = -(-len(cells) // LOSS_BLOCK)
+    t = np.zeros(blocks * LOSS_BLOCK)
+    t[:len(cells)] = cells
+    t = t.reshape(blocks, LOSS_BLOCK // 64, 64)
+    for half in (32, 16, 8, 4, 2, 1):
+        t = t[:, :, :half] + t[:, :, half:2 * half]
+    w = t[:, :, 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+def loss_tree(cells):
+    """the loss in the device's order: the block partials of loss_cells() added in block order in one chain from 0.0, then halved"""
+    s = 0.0
+    for p in loss_partials(cells).tolist():
+        s += p
+    return s * 0.5
 
 
 def loss_of(W, Ht, rows):

@@ -201,7 +201,7 @@ def inversion_batch(n, count=200):
     return A
 
 
-@pytest.mark.parametrize("n", [2, 3, 10, 33, 64])
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 8, 9, 10, 16, 17, 32, 33, 64])
 def test_inversion_batch_matches_the_restatement(n):
     A = inversion_batch(n)
     stopped, want = [], np.empty_like(A)

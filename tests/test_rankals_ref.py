@@ -1,11 +1,13 @@
 """tests/rankals_ref.py (the CPU restatement the GPU tests compare against) equals the run of the reference's own RankALS source
 (tests/golden/reference_rankals.json.gz, minted by tests/tools/mint_reference_rankals.py) bit for bit: P and Q after every iteration,
 the predictions, DenseMatrix.inv() on the table's matrices, initModel()'s draws; and its hoisted form (what the device runs) equals its
-literal form bit for bit."""
+literal form bit for bit.  The fixtures of tests/test_gpu_rankals_anchor.py (tests/rankals_fixtures.py) are held to their conditions
+here, without a GPU."""
 import numpy as np
+import pytest
 
 from oracle import oracle_np
-from tests import nmf_ref, rankals_ref as rref
+from tests import nmf_ref, rankals_fixtures as fx, rankals_ref as rref
 from tests.util import same_bits_exact
 
 RUNS = rref.golden_runs()
@@ -107,3 +109,29 @@ def test_array_form_for_large_matrices_equals_the_list_form():
     assert all(same_bits_exact(x, y) for x, y in zip(mom_a, mom_b))
     for j in range(ni):
         assert same_bits_exact(a.solve_item(Pa, m, sum_sq, mom_a, j), b.solve_item(Pb, ms, sum_sq, mom_b, j)), j
+
+
+# ---- the fixtures of tests/test_gpu_rankals_anchor.py -----------------------------------------------------------------------------------
+def test_per_is_derived_from_the_kernels_constants():
+    c = fx.kernel_constants()
+    assert c["RANKALS_MAX_K"] == 64 and c["RANKALS_CHUNK"] == 64 and c["RANKALS_STAGE_MIN"] == 1024 and c["RANKALS_TILE"] == 16
+    assert [fx.per_of(k) for k in (1, 8, 16, 17, 32, 33, 63, 64)] == [64, 64, 64, 60, 32, 33, 63, 64]
+    assert all(fx.per_of(k) != c["RANKALS_CHUNK"] for k in fx.BORDER_KS[1:])       # the staging borders no other test puts an entry on
+
+
+@pytest.mark.parametrize("k", fx.BORDER_KS)
+def test_per_border_matrix_has_the_borders(k):
+    per, tile = fx.per_of(k), fx.kernel_constants()["RANKALS_TILE"]
+    nu, ni, cells = fx.per_border_matrix(k)
+    for sw in (True, False):
+        m = rref.RankALS(nu, ni, cells, sw)
+        ul, il = [len(x) for x in m.rows], [len(x) for x in m.cols]
+        assert ul[1:4] == [per, per + 1, 2 * per] and il[1:4] == [per, per + 1, 2 * per]
+        assert ni % tile == 0 and len(m.users) % tile == 0 and m.users == list(range(nu))       # every last pass is a full tile
+        assert max(ul[:1] + ul[4:]) < per and max(il[:1] + il[4:]) < per and min(ul) >= 3 and min(il) >= 1
+    stored = [(j, v) for u, j, v in cells if u == 3]
+    assert len(stored) == 2 * per + 1 and sum(1 for _, v in stored if v == 0.0) == 1 and sum(1 for _, v in stored if v < 0) == 1
+    assert [j for j, v in m.rows[3]].index(next(j for j, v in stored if v < 0)) == per          # it opens the second staged chunk
+    assert all(v > 0 for u, _, v in cells if u != 3)
+    P0, Q0, out = fx.per_border_run(k, True)
+    assert all(np.isfinite(P).all() and np.isfinite(Q).all() for P, Q in out)
