@@ -89,6 +89,7 @@ SYMBOLS = [
     ("cmi_rank_list_measures", C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp]),
     ("cmi_narrow_runs", C.c_int, [_i64, _vp, _i64, _i64, _vp, C.POINTER(_i64)]),
     ("cmi_conflict_free_blocks", C.c_int, [_i64, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, C.POINTER(_i64)]),
+    ("cmi_svdpp_team_rows", C.c_int, [C.c_int, C.c_int, C.POINTER(_i64)]),
     ("cmi_java_int_hashset_order", C.c_int, [_i64, _vp, _vp, C.POINTER(_i64)]),
     ("cmi_state_device_ptr", C.c_int, [_vp, C.c_int, C.POINTER(_vp), C.POINTER(_i64), C.POINTER(C.c_int)]),
     ("cmi_stream", C.c_int, [_vp, C.POINTER(_vp)]),
@@ -346,6 +347,18 @@ def conflict_free_blocks(u, j, n_users, n_items, max_block=64):
     if rc:
         raise CmiError(rc, "cmi_conflict_free_blocks")
     return off
+
+
+def svdpp_team_rows(k, f64):
+    """Host-only: the most rated items of a user whose Y rows the SVD++ team kernel keeps in LDS at k factors (0: k out of range)"""
+    return int(lib().cmi_svdpp_team_rows(int(k), 1 if f64 else 0, None))
+
+
+def svdpp_team_lds(k, f64):
+    """Host-only: the dynamic LDS bytes of the SVD++ team kernel's launch at k factors"""
+    n = _i64()
+    lib().cmi_svdpp_team_rows(int(k), 1 if f64 else 0, C.byref(n))
+    return n.value
 
 
 def rank_list_measures(ranked, truth, num_dropped, num_recs):

@@ -1964,3 +1964,10 @@ extern "C" int cmi_conflict_free_blocks(int64_t n, const int32_t *u, const int32
         return CMI_OK;
     });
 }
+
+extern "C" int cmi_svdpp_team_rows(int k, int f64, int64_t *lds_bytes) {
+    const size_t es = f64 ? sizeof(double) : sizeof(float);
+    const bool ok = k >= 1 && k <= 1024;
+    if (lds_bytes) *lds_bytes = ok ? (int64_t)svdpp_team_lds(k, es) : 0;
+    return ok ? svdpp_team_rows(k, es) : 0;
+}

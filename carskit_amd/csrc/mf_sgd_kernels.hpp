@@ -153,6 +153,10 @@ template <typename T>
 hipError_t launch_ext_serial(const ExtArgs<T> &a, int model, bool strict, int64_t n, double *loss_out, hipStream_t s);
 // SVD++ with a workgroup per chain link, the user's rows resident in LDS (svdpp_team.hip)
 bool svdpp_team_supported(int k);
+// the most rated items of a user whose Y rows svdpp_team keeps in LDS at k factors (1 <= k <= 1024) of esize bytes, and the dynamic LDS
+// of that launch; a user with more is walked by one wave through memory
+int svdpp_team_rows(int k, size_t esize);
+size_t svdpp_team_lds(int k, size_t esize);
 template <typename T>
 hipError_t launch_svdpp_team(const ExtArgs<T> &a, int64_t n, double *loss_out, hipStream_t s);
 

@@ -289,15 +289,24 @@ __global__ __launch_bounds__(NT) void svdpp_team(ExtArgs<T> a, int64_t n, int ma
 
 } // namespace
 
+// The row budget: the kernel's seven arrays (the layout above svdpp_team) out of 144 KB of the CU's 160 KB.  s_p, s_q and s_part are
+// `fixed`; a row costs its k factors in s_Y and one entry each in s_rr, s_items and s_j.  At most 4096 rows (small k).
+static size_t svdpp_team_fixed(int k, size_t esize) { return ((size_t)2 * k + 66) * esize; }
+static size_t svdpp_team_per_row(int k, size_t esize) { return (size_t)k * esize + esize + 2 * sizeof(int32_t); }
+int svdpp_team_rows(int k, size_t esize) {
+    const size_t budget = 144 * 1024;
+    const size_t rows = (budget - svdpp_team_fixed(k, esize)) / svdpp_team_per_row(k, esize);
+    return rows > 4096 ? 4096 : (int)rows;
+}
+size_t svdpp_team_lds(int k, size_t esize) {
+    return svdpp_team_fixed(k, esize) + (size_t)svdpp_team_rows(k, esize) * svdpp_team_per_row(k, esize) + 16;
+}
+
 // unused s_part lanes must read as zero: the kernel sums all 64 slots
 template <typename T>
 hipError_t launch_svdpp_team(const ExtArgs<T> &a, int64_t n, double *loss_out, hipStream_t s) {
-    const size_t budget = 144 * 1024; // of the CU's 160 KB
-    const size_t fixed = ((size_t)2 * a.k + 66) * sizeof(T);
-    const size_t per_row = (size_t)a.k * sizeof(T) + sizeof(T) + 2 * sizeof(int32_t);
-    size_t rows = (budget - fixed) / per_row;
-    if (rows > 4096) rows = 4096;
-    const size_t lds = fixed + rows * per_row + 16;
+    const int rows = svdpp_team_rows(a.k, sizeof(T));
+    const size_t lds = svdpp_team_lds(a.k, sizeof(T));
     // team size: 1024 threads measured fastest (measured on a stream of one-rating runs: 2.9 / 3.8 / 5.1 us per rating at k = 10 / 64 / 128 against 3.2 / 5.7 / 9.1 with
     // 256 threads) although a link is only ~375 instructions per wave: the wide parts (|N(u)| k element updates, one group per row) win more
     // from 16 waves than the uniform part loses

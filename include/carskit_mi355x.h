@@ -568,6 +568,10 @@ int cmi_narrow_runs(int64_t n_levels, const int64_t *level_off, int64_t max_tupl
                     int64_t *n_launches);
 int cmi_conflict_free_blocks(int64_t n, const int32_t *u, const int32_t *j, int32_t n_users, int32_t n_items, int32_t max_block,
                              int32_t *off, int64_t off_cap, int64_t *n_blocks);
+/* host-only: the most rated items of a user whose Y rows the default SVD++ epoch (svdpp_team.hip) keeps in LDS at k factors, fp64
+ * state or fp32, from the kernel's LDS use (0: k outside 1 .. 1024) -- a user with more is walked by one wave through memory;
+ * *lds_bytes (may be NULL): the dynamic LDS of that launch */
+int cmi_svdpp_team_rows(int k, int f64, int64_t *lds_bytes);
 
 /* The owner form behind CMI_FLAG_SCHED_OWNER (level_schedule.cpp, build_owner_schedule): like the level schedules it replaces the
  * reference's implicit "one tuple after another" order (librec MatrixIterator in `for (MatrixEntry me : trainMatrix)`,

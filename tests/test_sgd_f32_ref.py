@@ -34,6 +34,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle_c
+from tests import border_data as bd
 from tests import hparam_anchor as ha
 from tests import sgd_f32_ref as ref
 from tests import util
@@ -205,6 +206,31 @@ def test_camf_c_within_the_derived_bound_of_the_oracle(k):
         loss = ref.epoch_camfc(st, pb, hp, layout, ref.camfc_blocks(pb))
         ratio = worst_ratio(st, states[1], bound)
         print("worst |difference| / bound: %-12s k=%-3d %-22r %.4f" % ("CAMF_C", k, layout, ratio))
+        assert ratio <= 1.0, (layout, ratio)
+        assert abs(loss - want) <= 2e-6 * abs(want), (layout, loss, want)
+
+
+@pytest.mark.parametrize("n_dims,cpd,ragged,k", [c for c in bd.CAMFC_CASES if c[2] or c[0] >= 8])
+def test_camf_c_border_data_within_the_derived_bound_of_the_oracle(n_dims, cpd, ragged, k):
+    """epoch_camfc where tests/test_gpu_camfc_blocks_borders.py relies on it: ragged contexts (a context with no condition among them),
+    8 and 16 dimensions, blocks of exactly 64 tuples one after another, 64 to 344 conditions"""
+    d = bd.camfc_data(n_dims, cpd, ragged)
+    pb = ref.problem("CAMF_C", d)
+    blk = ref.camfc_blocks(pb)
+    lens = np.diff(blk)
+    assert pb.dmax == n_dims and np.any((lens[:-1] == 64) & (lens[1:] == 64)) and (np.any(pb.conds < 0) == ragged)
+    gm = oracle_c.global_mean(d.r)
+    hp = ref.hparams("CAMF_C", util.LR, REGS, gm)
+    start = ref.start_state("CAMF_C", d, k)
+    orc = util.c_oracle("CAMF_C", d, k, ref.widen(start), gm, *REGS)
+    want = orc.epoch(util.LR)
+    after = {n: np.array(orc.state[n], np.float64).reshape(start[n].shape) for n in start}
+    bound = forward_bound("CAMF_C", pb, k, [ref.widen(start), after], gm, 1)
+    for name, layout in sorted(ref.camfc_layouts(k).items()):
+        st = {n: a.copy() for n, a in start.items()}
+        loss = ref.epoch_camfc(st, pb, hp, layout, blk)
+        ratio = worst_ratio(st, after, bound)
+        print("worst |difference| / bound: %-12s k=%-3d dims=%-2d %-22r %.4f" % ("CAMF_C", k, n_dims, layout, ratio))
         assert ratio <= 1.0, (layout, ratio)
         assert abs(loss - want) <= 2e-6 * abs(want), (layout, loss, want)
 
