@@ -296,6 +296,27 @@ SYMBOLS = [
     ("cmi_cptf_tensor_build", C.c_int, [_i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64, _vp, C.c_uint,
                                         C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _vp, C.POINTER(_i64), _vp, _vp,
                                         _vp]),
+    ("cmi_bpmf_create", C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint, C.POINTER(_vp)]),
+    ("cmi_bpmf_destroy", C.c_int, [_vp]),
+    ("cmi_bpmf_last_error", C.c_char_p, [_vp]),
+    ("cmi_bpmf_set_ratings", C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    ("cmi_bpmf_set_global_mean", C.c_int, [_vp, _dbl]),
+    ("cmi_bpmf_get_global_mean", C.c_int, [_vp, C.POINTER(_dbl)]),
+    ("cmi_bpmf_set_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_bpmf_get_model", C.c_int, [_vp, _vp, _vp]),
+    ("cmi_bpmf_set_stream", C.c_int, [_vp, _i64, C.c_int, _dbl]),
+    ("cmi_bpmf_get_stream", C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(_dbl)]),
+    ("cmi_bpmf_init_hyper", C.c_int, [_vp]),
+    ("cmi_bpmf_get_hyper", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("cmi_bpmf_set_hyper", C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    ("cmi_bpmf_iterate", C.c_int, [_vp, C.POINTER(_dbl)]),
+    ("cmi_bpmf_last_iter_ms", C.c_int, [_vp, C.POINTER(C.c_float)]),
+    ("cmi_bpmf_predict_batch", C.c_int, [_vp, _i64, _vp, _vp, C.c_int, _dbl, _dbl, _vp]),
+    ("cmi_bpmf_sample_side", C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.POINTER(_i64)]),
+    ("cmi_java_next_gaussians", C.c_int, [C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(_dbl), _i64, _vp]),
+    ("cmi_bpmf_gauss_attempts", _i64, [_i64]),
+    ("cmi_bpmf_moments", C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, C.c_int]),
+    ("cmi_bpmf_hyper_host", C.c_int, [C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(C.c_int), C.POINTER(_dbl)]),
     ("cmi_fm_synchronize", C.c_int, [_vp]),
     ("cmi_fm_stream", C.c_int, [_vp, C.POINTER(_vp)]),
     ("cmi_fm_num_phases", C.c_int, [_vp]),
@@ -1773,3 +1794,132 @@ class CPTFInstance(_Handle):
 
     def ctx_in_lds(self):
         return bool(self.L.cmi_cptf_ctx_in_lds(self.h))
+
+
+BPMF_FLAG_STRICT = 0x1
+BPMF_MAX_K, BPMF_TILE, BPMF_CHUNK, BPMF_GAUSS_BLOCK = 64, 32, 64, 256   # bpmf_kernels.hpp
+
+
+def _bpmf_chk(rc, fn):
+    if rc != OK:
+        raise CmiError(rc, (lib().cmi_bpmf_last_error(None) or fn.encode()).decode())
+
+
+def java_next_gaussians(state, n, have_cached=False, cached=0.0):
+    """n values of java.util.Random.nextGaussian() on the device from the 48-bit `state` and the cached second value of the last pair;
+    (values, (state, have_cached, cached) after)"""
+    st, hv, cv = _i64(int(state)), C.c_int(1 if have_cached else 0), _dbl(float(cached))
+    out = np.empty(max(int(n), 1))
+    _bpmf_chk(lib().cmi_java_next_gaussians(C.byref(st), C.byref(hv), C.byref(cv), int(n), _p(out)), "cmi_java_next_gaussians")
+    return out[:int(n)], (st.value, bool(hv.value), cv.value)
+
+
+def bpmf_gauss_attempts(n_pairs):
+    """the attempts of the polar method the device makes at first for n_pairs accepted ones"""
+    return int(lib().cmi_bpmf_gauss_attempts(int(n_pairs)))
+
+
+def bpmf_moments(X, on_device=True):
+    """(DenseMatrix.columnMean of every column, DenseMatrix.cov()) of X (rows, k); host-only unless on_device"""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    rows, k = X.shape
+    mean, cov = np.empty(k), np.empty((k, k))
+    _bpmf_chk(lib().cmi_bpmf_moments(_p(X), rows, k, _p(mean), _p(cov), 1 if on_device else 0), "cmi_bpmf_moments")
+    return mean, cov
+
+
+def bpmf_hyper_host(rows, mean, cov, alpha, mu, stream):
+    """Host-only: BPMF's hyper-parameter step of one side with `rows` rows; stream = (state, have_cached, cached).
+    (alpha, mu, stream after)"""
+    mean = np.ascontiguousarray(mean, dtype=np.float64)
+    cov = np.ascontiguousarray(cov, dtype=np.float64)
+    alpha = np.array(alpha, dtype=np.float64, order="C")
+    mu = np.array(mu, dtype=np.float64, order="C")
+    st, hv, cv = _i64(int(stream[0])), C.c_int(1 if stream[1] else 0), _dbl(float(stream[2]))
+    _bpmf_chk(lib().cmi_bpmf_hyper_host(len(mean), int(rows), _p(mean), _p(cov), _p(alpha), _p(mu), C.byref(st), C.byref(hv), C.byref(cv)),
+              "cmi_bpmf_hyper_host")
+    return alpha, mu, (st.value, bool(hv.value), cv.value)
+
+
+class BPMFInstance(_FactorModel):
+    """The reference's BPMF on one GPU (a `cmi_bpmf_handle`): P is (n_users, k), Q is (n_items, k), 1 <= k <= 64.  P and Q come from the
+    caller; the Gibbs and hyper-parameter draws come from the handle's stream (set_stream)."""
+
+    _api = ("cmi_bpmf_create", "cmi_bpmf_destroy", "cmi_bpmf_last_error")
+    _prefix = "cmi_bpmf"
+
+    def set_global_mean(self, gm):
+        self._chk(self.L.cmi_bpmf_set_global_mean(self.h, float(gm)))
+
+    def global_mean(self):
+        gm = _dbl()
+        self._chk(self.L.cmi_bpmf_get_global_mean(self.h, C.byref(gm)))
+        return gm.value
+
+    def set_model(self, P=None, Q=None):
+        P = self._shaped(P, (self.n_users, self.k), "P")
+        Q = self._shaped(Q, (self.n_items, self.k), "Q")
+        self._chk(self.L.cmi_bpmf_set_model(self.h, None if P is None else _p(P), None if Q is None else _p(Q)))
+
+    def model(self):
+        """(P, Q)"""
+        P, Q = np.empty((self.n_users, self.k)), np.empty((self.n_items, self.k))
+        self._chk(self.L.cmi_bpmf_get_model(self.h, _p(P), _p(Q)))
+        return P, Q
+
+    def set_stream(self, state, have_cached=False, cached=0.0):
+        self._chk(self.L.cmi_bpmf_set_stream(self.h, int(state), 1 if have_cached else 0, float(cached)))
+
+    def stream(self):
+        """(state, have_cached, cached)"""
+        st, hv, cv = _i64(), C.c_int(), _dbl()
+        self._chk(self.L.cmi_bpmf_get_stream(self.h, C.byref(st), C.byref(hv), C.byref(cv)))
+        return st.value, bool(hv.value), cv.value
+
+    def init_hyper(self):
+        self._chk(self.L.cmi_bpmf_init_hyper(self.h))
+
+    def hyper(self):
+        """(alpha_u, mu_u, alpha_m, mu_m)"""
+        k = self.k
+        au, mu, am, mm = np.empty((k, k)), np.empty(k), np.empty((k, k)), np.empty(k)
+        self._chk(self.L.cmi_bpmf_get_hyper(self.h, _p(au), _p(mu), _p(am), _p(mm)))
+        return au, mu, am, mm
+
+    def set_hyper(self, alpha_u, mu_u, alpha_m, mu_m):
+        k = self.k
+        a = [self._shaped(alpha_u, (k, k), "alpha_u"), self._shaped(mu_u, (k,), "mu_u"), self._shaped(alpha_m, (k, k), "alpha_m"),
+             self._shaped(mu_m, (k,), "mu_m")]
+        self._chk(self.L.cmi_bpmf_set_hyper(self.h, *[_p(x) for x in a]))
+
+    def iterate(self):
+        """one iteration of BPMF.buildModel's loop; returns the loss (a CmiError of code E_NUMERIC carries a non-finite one as .loss)"""
+        loss = _dbl()
+        rc = self.L.cmi_bpmf_iterate(self.h, C.byref(loss))
+        if rc != OK:
+            err = CmiError(rc, self.L.cmi_bpmf_last_error(self.h).decode())
+            err.loss = loss.value
+            raise err
+        return loss.value
+
+    def sample_side(self, side, alpha, mu):
+        """one Gibbs pass of the users (side 0) or the items (side 1) with the caller's hyper-parameters: (null flags per row, draws)"""
+        alpha = self._shaped(alpha, (self.k, self.k), "alpha")
+        mu = self._shaped(mu, (self.k,), "mu")
+        flags = np.zeros(self.n_users if side == 0 else self.n_items, np.int32)
+        draws = _i64()
+        self._chk(self.L.cmi_bpmf_sample_side(self.h, int(side), _p(alpha), _p(mu), _p(flags), C.byref(draws)))
+        return flags, draws.value
+
+    def predict(self, u, j, bound=False, lo=1.0, hi=5.0):
+        u = np.ascontiguousarray(u, dtype=np.int32)
+        j = np.ascontiguousarray(j, dtype=np.int32)
+        out = np.empty(len(u))
+        self._chk(self.L.cmi_bpmf_predict_batch(self.h, len(u), _p(u), _p(j), 1 if bound else 0, float(lo), float(hi), _p(out)))
+        return out
+
+    def last_iter_ms(self):
+        """(moments, hyper steps on the host, user passes, item passes, loss) milliseconds of the last iterate()"""
+        ms = (C.c_float * 5)()
+        self._chk(self.L.cmi_bpmf_last_iter_ms(self.h, ms))
+        return tuple(ms)

@@ -147,6 +147,11 @@ static int run(const std::string &config, unsigned flags, int iters_override, bo
             throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of NMF is not accelerated yet");
         if (a == "nmf" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": NMF runs on one GPU");
+        // BPMF: the same two refusals
+        if (a == "bpmf" && conf.isRankingPred)
+            throw std::runtime_error("item.ranking=on with " + a + ": top-N recommendation of BPMF is not accelerated yet");
+        if (a == "bpmf" && shards > 1)
+            throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": BPMF runs on one GPU");
         // SLIM is a top-N model (item.ranking -diverse is refused with every model, by Conf), on one GPU
         if (a == "slim" && shards > 1)
             throw std::runtime_error("--shards " + std::to_string(shards) + " with " + a + ": SLIM runs on one GPU");

@@ -830,6 +830,55 @@ class NMF : public PairRecommender<cmi_nmf_handle, cmi_nmf_destroy, cmi_nmf_last
     }
 };
 
+// src/carskit/alg/baseline/cf/BPMF.java: P and Q by Gibbs sampling over the 2-D train matrix.  Parameters: num.factors, num.max.iter.
+// lRate = -1 (BPMF.java:47).  Two random streams: P.init(0, 1) and Q.init(0, 1) draw from librec.util.Randoms, the gaussian and gamma
+// draws of buildModel from happy.coding.math.Randoms; both are seeded with --rand-seed, and the second is the handle's stream.
+class BPMF : public PairRecommender<cmi_bpmf_handle, cmi_bpmf_destroy, cmi_bpmf_last_error, cmi_bpmf_set_ratings> {
+  public:
+    BPMF(const RatingData &tr, const RatingData &te, int fold, const Conf &c, Logger log = nullptr)
+        : PairRecommender("BPMF", tr, te, fold, c, log) {
+        lRate = -1;
+    }
+    // BPMF.java:71-75: P.init(0, 1), Q.init(0, 1), row by row (super.initModel()'s own draw of P and Q, IterativeRecommender.java:235-241,
+    // comes first on the same stream and is overwritten)
+    void initModel() override {
+        JavaRandom rnd(conf_.randSeed);
+        const size_t nu = (size_t)trainMatrix.n_users, ni = (size_t)trainMatrix.n_items, k = (size_t)conf_.numFactors;
+        for (size_t t = 0; t < (nu + ni) * k; ++t) (void)rnd.nextGaussian();
+        P.resize(nu * k);
+        Q.resize(ni * k);
+        for (double &x : P) x = 0.0 + 1.0 * rnd.nextGaussian();
+        for (double &x : Q) x = 0.0 + 1.0 * rnd.nextGaussian();
+    }
+    void buildModel() override { // BPMF.java:52-247
+        // the loss as the reference's one chain up to 2^18 terms, as BPR; else the fixed tree
+        const bool small = (int64_t)trainMatrix.n() <= ((int64_t)1 << 18);
+        check(cmi_bpmf_create(conf_.numFactors, trainMatrix.n_users, trainMatrix.n_items, conf_.device, small ? CMI_BPMF_FLAG_STRICT : 0u, &h_),
+              "cmi_bpmf_create");
+        setRatings("cmi_bpmf_set_ratings");
+        check(cmi_bpmf_set_global_mean(h_, globalMean), "cmi_bpmf_set_global_mean");
+        check(cmi_bpmf_set_model(h_, P.data(), Q.data()), "cmi_bpmf_set_model");
+        check(cmi_bpmf_set_stream(h_, (int64_t)cmi::java_lcg_scramble(conf_.randSeed), 0, 0.0), "cmi_bpmf_set_stream");
+        check(cmi_bpmf_init_hyper(h_), "cmi_bpmf_init_hyper");
+        for (int iter = 1; iter <= conf_.numIters; ++iter) {
+            const int rc = cmi_bpmf_iterate(h_, &loss); // both hyper steps, two Gibbs passes of each side, the loss
+            if (rc != CMI_E_NUMERIC) check(rc, "cmi_bpmf_iterate"); // a NaN / Inf loss: isConverged reports it, as in the reference
+            losses.push_back(loss);
+            itersDone = iter;
+            if (isConverged(iter)) break;
+        }
+        check(cmi_bpmf_get_model(h_, P.data(), Q.data()), "cmi_bpmf_get_model");
+    }
+    void saveModel() override { saveFactors(P, Q); }
+    std::vector<double> P, Q; // numUsers x numFactors; numItems x numFactors
+
+  private:
+    void predictBounded(double *pred) override {
+        check(cmi_bpmf_predict_batch(h_, testMatrix.n(), testMatrix.u.data(), testMatrix.j.data(), 1, trainMatrix.min_rate,
+                                     trainMatrix.max_rate, pred), "cmi_bpmf_predict_batch");
+    }
+};
+
 // src/carskit/alg/baseline/ranking/SLIM.java: the item x item weights W by coordinate descent over each item's neighbour list, for
 // top-N.  Parameters: SLIM=-l1 -l2 -k, similarity, num.shrinkage, num.max.iter.  The constructor sets the static isRankingPred = true
 // (SLIM.java:68), so execute() evaluates with evalRankings() whatever item.ranking says.
@@ -1233,12 +1282,13 @@ inline std::unique_ptr<IterativeRecommender> getRecommender(const std::string &n
     if (n == "userknn") return std::unique_ptr<IterativeRecommender>(new UserKNN(tr, te, fold, c, log));
     if (n == "slopeone") return std::unique_ptr<IterativeRecommender>(new SlopeOne(tr, te, fold, c, log));
     if (n == "nmf") return std::unique_ptr<IterativeRecommender>(new NMF(tr, te, fold, c, log));             // CARSKit.java:467
+    if (n == "bpmf") return std::unique_ptr<IterativeRecommender>(new BPMF(tr, te, fold, c, log));           // CARSKit.java:465-466
     if (n == "rankals") return std::unique_ptr<IterativeRecommender>(new RankALS(tr, te, fold, c, log));   // CARSKit.java:477-478
     if (n == "bpr") return std::unique_ptr<IterativeRecommender>(new BPR(tr, te, fold, c, log));
     if (n == "lrmf") return std::unique_ptr<IterativeRecommender>(new LRMF(tr, te, fold, c, log));
     if (n == "cptf") return std::unique_ptr<IterativeRecommender>(new CPTF(tr, te, fold, c, log));         // CARSKit.java:693-697
     if (n == "ranksgd") return std::unique_ptr<IterativeRecommender>(new RankSGD(tr, te, fold, c, log));   // CARSKit.java:479-480
-    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, cptf, slim, rankals, bpr, lrmf, ranksgd, itemknn, userknn, slopeone, nmf)");
+    throw std::runtime_error("recommender '" + name + "' is not on the accelerated path (biasedmf, pmf, svd++, camf_c, camf_ci, camf_cu, camf_cuci, camf_ics, camf_lcs, camf_mcs, fm, cptf, bpmf, slim, rankals, bpr, lrmf, ranksgd, itemknn, userknn, slopeone, nmf)");
 }
 
 } // namespace carskit

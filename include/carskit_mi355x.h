@@ -1053,6 +1053,65 @@ int cmi_cptf_tensor_build(int64_t n_cells, const int32_t *pair, const int32_t *c
                           int64_t *n_train, int32_t *train_keys, double *train_vals, int64_t *n_test_out, int32_t *test_keys,
                           double *test_vals, int32_t *ctx_keys);
 
+/* ---- BPMF (src/carskit/alg/baseline/cf/BPMF.java; bpmf_api.cpp, bpmf_kernels.hip, bpmf_host.hpp) -----------------------------------
+ * Bayesian PMF by Gibbs sampling over the 2-D train matrix, fp64, bit for bit: per iteration the hyper-parameter step of both sides
+ * (on the host: two k x k Wishart draws), then two Gibbs passes, each over every user and then every item -- a row's posterior is
+ * a k x k solve (Gram matrix, DenseMatrix.inv(), DenseMatrix.cholesky(), k normal draws), a workgroup per row.
+ * Two random streams: P and Q are drawn by the caller (DenseMatrix.init draws from librec.util.Randoms); the gaussian and gamma draws
+ * of buildModel come from happy.coding.math.Randoms, whose state -- the 48-bit LCG state and the cached second value of
+ * nextGaussian()'s last pair -- is the handle's stream.  1 <= k <= 64 (two k x k matrices of doubles in LDS).  No CPU fallback:
+ * without a device cmi_bpmf_create returns CMI_E_NO_DEVICE. */
+typedef struct cmi_bpmf_instance *cmi_bpmf_handle;
+#define CMI_BPMF_FLAG_STRICT 0x1u /* the loss as one chain in cell order: the reference's sum bit for bit (small data); else a fixed tree */
+/* BPMF.java:44-75 (numFactors, the shapes of P and Q).  k > 64 -> CMI_E_UNSUPPORTED */
+int cmi_bpmf_create(int k, int n_users, int n_items, int device, unsigned flags, cmi_bpmf_handle *out);
+int cmi_bpmf_destroy(cmi_bpmf_handle h);
+const char *cmi_bpmf_last_error(cmi_bpmf_handle h);
+/* `train` as n cells.  A stored 0.0 is no entry of train.row(u) / train.column(j) (BPMF.java:157-158, :196-197: a user whose only cell
+ * is a stored zero has count == 0 and is skipped) but is a term of the loss (:233: the matrix iterator gives it).  Sets globalMean to
+ * the mean of the non-zero cells, one chain in cell order */
+int cmi_bpmf_set_ratings(cmi_bpmf_handle h, int64_t n, const int32_t *u, const int32_t *i, const double *r);
+/* globalMean (Recommender.java:265: the mean of the CONTEXTUAL train matrix, which the caller holds), read by :168, :206 and predict */
+int cmi_bpmf_set_global_mean(cmi_bpmf_handle h, double global_mean);
+int cmi_bpmf_get_global_mean(cmi_bpmf_handle h, double *global_mean);
+/* BPMF.java:71-75: P and Q, drawn by the caller with init(0, 1); and any later injection */
+int cmi_bpmf_set_model(cmi_bpmf_handle h, const double *P, const double *Q);
+int cmi_bpmf_get_model(cmi_bpmf_handle h, double *P, double *Q);
+/* the stream of happy.coding.math.Randoms: state (0 .. 2^48 - 1; after Randoms.seed(s): (s ^ 0x5DEECE66D) & (2^48 - 1)), have_cached
+ * and cached (java.util.Random's haveNextNextGaussian and nextNextGaussian) */
+int cmi_bpmf_set_stream(cmi_bpmf_handle h, int64_t state, int have_cached, double cached);
+int cmi_bpmf_get_stream(cmi_bpmf_handle h, int64_t *state, int *have_cached, double *cached);
+/* BPMF.java:77-83: mu_u / mu_m = the column means, alpha_u / alpha_m = cov().inv(), of the model as it stands */
+int cmi_bpmf_init_hyper(cmi_bpmf_handle h);
+/* alpha_u (k x k), mu_u (k), alpha_m, mu_m as they stand; any may be null */
+int cmi_bpmf_get_hyper(cmi_bpmf_handle h, double *alpha_u, double *mu_u, double *alpha_m, double *mu_m);
+int cmi_bpmf_set_hyper(cmi_bpmf_handle h, const double *alpha_u, const double *mu_u, const double *alpha_m, const double *mu_m);
+/* BPMF.java:97-242: one iteration -- both hyper steps, two Gibbs passes over the users and the items, the loss (*loss as after :242).
+ * Before set_ratings, set_model or init_hyper -> CMI_E_INVALID.  NaN / Inf loss -> CMI_E_NUMERIC with *loss set */
+int cmi_bpmf_iterate(cmi_bpmf_handle h, double *loss);
+/* of the last cmi_bpmf_iterate: ms[0] the moments of P and Q (:99-100, :126-127; device, by events), ms[1] the hyper steps (:102-122,
+ * :129-149; host, wall clock), ms[2] the two user passes and ms[3] the two item passes (gaussians, rows and the read-back of the null
+ * flags; by events), ms[4] the loss */
+int cmi_bpmf_last_iter_ms(cmi_bpmf_handle h, float ms[5]);
+/* BPMF.java:325-327: globalMean + DenseMatrix.rowMult(P, u, Q, j) of n tuples; bound: clamped to [lo, hi] (Recommender.predict(u, j, c,
+ * true)), which the rating evaluation takes */
+int cmi_bpmf_predict_batch(cmi_bpmf_handle h, int64_t n, const int32_t *u, const int32_t *j, int bound, double lo, double hi, double *out);
+/* one Gibbs pass of one side alone with the caller's hyper-parameters (side 0: BPMF.java:155-191, the users, writes P; side 1:
+ * :194-229, the items, writes Q).  null_flags (n_users or n_items ints; may be null): 1 where the row has entries and
+ * covar.cholesky() is null -- the row keeps its value and takes no draw.  *draws: the gaussians taken.  The handle's stream moves on */
+int cmi_bpmf_sample_side(cmi_bpmf_handle h, int side, const double *alpha, const double *mu, int32_t *null_flags, int64_t *draws);
+/* the parts alone.  The message of a failure: cmi_bpmf_last_error(NULL).
+ * java.util.Random.nextGaussian() n times on the device from (*state, *have_cached, *cached), which are left as after the last one */
+int cmi_java_next_gaussians(int64_t *state, int *have_cached, double *cached, int64_t n, double *out);
+/* the attempts of the polar method the device makes at first for n_pairs accepted ones; where fewer are accepted it goes on */
+int64_t cmi_bpmf_gauss_attempts(int64_t n_pairs);
+/* DenseMatrix.columnMean(f) of every f and DenseMatrix.cov() of X (rows x k), on the device (on_device) or by the host loop */
+int cmi_bpmf_moments(const double *X, int rows, int k, double *mean, double *cov, int on_device);
+/* BPMF.java:102-122 (or :129-149) of one side with `rows` rows, on the host: x_bar = mean, S_bar = cov; alpha (k x k) and mu (k) in
+ * place; the stream in place */
+int cmi_bpmf_hyper_host(int k, int rows, const double *mean, const double *cov, double *alpha, double *mu, int64_t *state, int *have_cached,
+                        double *cached);
+
 #ifdef __cplusplus
 }
 #endif
