@@ -1797,7 +1797,7 @@ class CPTFInstance(_Handle):
 
 
 BPMF_FLAG_STRICT = 0x1
-BPMF_MAX_K, BPMF_TILE, BPMF_CHUNK, BPMF_GAUSS_BLOCK = 64, 32, 64, 256   # bpmf_kernels.hpp
+BPMF_MAX_K, BPMF_BLOCK, BPMF_TILE, BPMF_CHUNK, BPMF_GAUSS_BLOCK, BPMF_STAGE_MIN = 64, 256, 32, 64, 256, 1024   # bpmf_kernels.hpp
 
 
 def _bpmf_chk(rc, fn):

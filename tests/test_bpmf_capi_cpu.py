@@ -36,8 +36,10 @@ def test_bpmf_symbols_in_header_binding_and_library():
               "sample_side", "predict", "last_iter_ms", "close"):
         assert callable(getattr(capi.BPMFInstance, m))
     assert (capi.BPMF_MAX_K, capi.BPMF_TILE, capi.BPMF_CHUNK, capi.BPMF_GAUSS_BLOCK) == (64, 32, 64, 256)
+    assert (capi.BPMF_BLOCK, capi.BPMF_STAGE_MIN) == (256, 1024)
     src = open(os.path.join(ROOT, "carskit_amd", "csrc", "bpmf_kernels.hpp")).read()
-    for name, v in (("BPMF_MAX_K", 64), ("BPMF_TILE", 32), ("BPMF_CHUNK", 64), ("BPMF_GAUSS_BLOCK", 256)):
+    for name, v in (("BPMF_MAX_K", 64), ("BPMF_TILE", 32), ("BPMF_CHUNK", 64), ("BPMF_GAUSS_BLOCK", 256), ("BPMF_BLOCK", 256),
+                    ("BPMF_STAGE_MIN", 1024)):
         assert re.search(r"constexpr int %s = %d;" % (name, v), src), name
 
 

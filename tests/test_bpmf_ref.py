@@ -70,6 +70,32 @@ def test_wishart_p7_leaves_out_a_term_of_sparse_inner():
     assert ref.sparse_inner([1.0] * 5, [1.0] * 5) == 4.0
 
 
+def test_the_k17_run_reaches_sparse_inner_where_contains_misses_other_indices(monkeypatch):
+    """a hyper step at k = 17 calls SparseVector.inner over every length 1 .. 16: besides 5, 9 and 10 (what k = 10 and the p = 7 case
+    reach) contains() misses indices at 11 (8, 9, 10) and 13 (12), and the run's P, Q and loss hold those sums to the reference"""
+    run = next(r for r in G["runs"] if r["k"] == 17)
+    missed = {n: [k for k in range(n) if not ref.contains(list(range(n)), k)] for n in range(1, 17)}
+    assert {n: v for n, v in missed.items() if v} == {5: [4], 9: [8], 10: [8, 9], 11: [8, 9, 10], 13: [12]}
+    seen, inner = [], ref.sparse_inner
+    monkeypatch.setattr(ref, "sparse_inner", lambda a, b: (seen.append(len(a)), inner(a, b))[1])
+    nu, k = run["n_users"], run["k"]
+    P = ref.unhex(run["P0"], nu, k)
+    ref.hyper_side(ref.Stream.seeded(run["seed_gibbs"]), P, ref.inv(ref.cov(P)), ref.column_mean(P))
+    assert set(seen) == set(range(1, 17)) and seen.count(11) >= 2 and seen.count(13) >= 2
+    assert ref.sparse_inner([1.0] * 11, [1.0] * 11) == 8.0 and ref.sparse_inner([1.0] * 13, [1.0] * 13) == 12.0
+
+
+@pytest.mark.parametrize("n", [17, 33, 64])
+def test_cholesky_and_its_literal_walk_agree_past_the_golden_sizes(n):
+    """the golden cases stop at n = 10: above that the row-wise form the runs use is held to the element-by-element walk"""
+    b = np.random.default_rng(20261240 + n).standard_normal((n, n))
+    A = b @ b.T + n * np.eye(n)
+    L, lit = ref.cholesky(A), ref.cholesky_literal(A)
+    assert L is not None and lit is not None and _same(L, lit) and not np.isnan(L).any() and (np.diag(L) > 0.0).all()
+    A[n - 1, n - 1] = -1.0                                   # no factor: both say so
+    assert ref.cholesky(A) is None and ref.cholesky_literal(A) is None
+
+
 @pytest.mark.parametrize("run", G["runs"], ids=lambda r: "%s-k%d" % (r["name"], r["k"]))
 def test_build_model_equals_the_source(run):
     nu, ni, k = run["n_users"], run["n_items"], run["k"]
@@ -96,3 +122,12 @@ def test_handmade_matrix_has_the_edge_rows():
     assert run["row_count"].count(0) >= 2 and run["col_count"].count(0) >= 1 and 1 in run["row_count"]
     cells = ref.golden_cells(run)
     assert any(v == 0.0 for _, _, v in cells) and any(v < 0.0 for _, _, v in cells)
+
+
+def test_generated_matrix_has_the_edge_rows_and_both_sides_longer_than_k():
+    run = next(r for r in G["runs"] if r["name"] == "generated")
+    assert run["k"] == 17 and run["n_users"] > 17 and run["n_items"] > 17 and len(run["iters"]) == 3
+    cells = ref.golden_cells(run)
+    assert run["row_count"].count(0) == 1 and run["col_count"].count(0) == 1 and sum(1 for _, _, v in cells if v == 0.0) == 1
+    per_user = [sum(1 for c in cells if c[0] == u) for u in range(run["n_users"])]
+    assert all(4 <= n <= 8 for n in per_user if n) and sum(per_user) > sum(run["row_count"])   # the stored zero is no entry of row()

@@ -23,6 +23,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "carskit_amd", "bin", "carskit-mi355x")
 
 BLOCK, TILE, CHUNK = capi.BPMF_GAUSS_BLOCK, capi.BPMF_TILE, capi.BPMF_CHUNK
+ROW_BLOCK, STAGE_MIN = capi.BPMF_BLOCK, capi.BPMF_STAGE_MIN
 RUNS = ref.golden()["runs"]
 
 
@@ -143,8 +144,13 @@ def test_gaussians_when_the_first_round_accepts_too_few():
 
 
 # ---- columnMean and cov() ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("k", [1, 3, 64])
-@pytest.mark.parametrize("rows", [1, 2, TILE - 1, TILE, TILE + 1, 3 * TILE + 1])
+# every row count at k = 1, 3, 64 (one workgroup of bpmf_cov_kernel, or only full ones); two row counts at k = 16 (exactly one full
+# workgroup) and at k = 17, 33, 63, whose last workgroup has dead lanes that still stage rows and meet the barriers
+MOMENT_SHAPES = [(rows, k) for k in (1, 3, 64) for rows in (1, 2, TILE - 1, TILE, TILE + 1, 3 * TILE + 1)] + \
+                [(rows, k) for k in (16, 17, 33, 63) for rows in (TILE + 1, 3 * TILE + 1)]
+
+
+@pytest.mark.parametrize("rows,k", MOMENT_SHAPES, ids=["%d-%d" % s for s in MOMENT_SHAPES])
 def test_moments_equal_the_restatement(rows, k):
     rng = np.random.default_rng(1000 * rows + k)
     X = rng.standard_normal((rows, k)) * 2.0 + 0.5
@@ -157,6 +163,34 @@ def test_moments_equal_the_restatement(rows, k):
         mean, cov = capi.bpmf_moments(X)
         assert same_bits(mean, ref.column_mean(X)) and same_bits(cov, ref.cov(X))
         assert np.isnan(mean[k // 2]) and np.isnan(cov[k // 2]).all()
+    if k in (16, 17, 33, 63):
+        # the NaN in the LAST column: its elements (f, k - 1) start in the first workgroup and its row (k - 1, g) ends the last one
+        groups = (k * k + ROW_BLOCK - 1) // ROW_BLOCK
+        assert k - 1 < ROW_BLOCK and (k * k - 1) // ROW_BLOCK == groups - 1
+        assert (groups, k * k % ROW_BLOCK) == {16: (1, 0), 17: (2, 33), 33: (5, 65), 63: (16, 129)}[k]   # the live lanes of the last one
+        X = rng.standard_normal((rows, k)) * 2.0 + 0.5
+        X[rows // 3, k - 1] = np.nan
+        mean, cov = capi.bpmf_moments(X)
+        want = ref.cov(X)
+        assert same_bits(mean, ref.column_mean(X)) and same_bits(cov, want)
+        assert np.isnan(cov[k - 1]).all() and np.isnan(cov[:, k - 1]).all() and np.isnan(cov).sum() == 2 * k - 1
+
+
+def test_moments_with_a_column_that_is_nan_in_every_row():
+    """Stats.mean of that column is 0 / 0: the centred column, and so its row and column of cov(), are NaN; columnMean is NaN as well.
+    Held to the restatement alone: the golden file's `cov` cases record a single NaN entry (`nan_entry`) and no column without a
+    number, so the reference's own answer to this input is not on record."""
+    assert not any(np.isnan(ref.unhex(c["X"], c["rows"], c["k"])).all(axis=0).any() for c in ref.golden()["cov"])
+    rows, k = TILE + 1, 17
+    rng = np.random.default_rng(20270110)
+    X = rng.standard_normal((rows, k)) * 2.0 + 0.5
+    X[:, 0] = np.nan                                     # elements in the first workgroup
+    X[:, k - 1] = np.nan                                 # and in the partial last one
+    want_mean, want_cov = ref.column_mean(X), ref.cov(X)
+    assert np.isnan(want_mean[[0, k - 1]]).all() and np.isnan(want_cov).sum() == 4 * k - 4
+    mean, cov = capi.bpmf_moments(X)
+    assert same_bits(mean, want_mean) and same_bits(cov, want_cov)
+    assert np.array_equal(np.isnan(cov), np.isnan(want_cov))
 
 
 def test_moments_equal_the_golden_cases():
@@ -275,14 +309,22 @@ def test_calls_out_of_order_and_bad_arguments():
 
 
 # ---- the row kernel at the shapes that take another path -------------------------------------------------------------------------------
+def row_per(k):
+    """entries of a row the row kernel stages a pass at k factors"""
+    return min(CHUNK, max(k * k, STAGE_MIN) // k)
+
+
 @functools.lru_cache(maxsize=None)
-def shape_matrix():
-    """14 users x 210 items.  User 0 has no cell and user 1 one; users 2 .. 6 have CHUNK - 2 .. CHUNK + 2 (the staging chunk is CHUNK
-    entries, and CHUNK - 1 at k = 63, where k x k LDS doubles hold 63 rows); user 7 has 200 (several chunks); user 8 has a NaN rating
-    among 5 (the mean goes NaN, the factor does not); user 9 only a stored zero; the others 3 .. 6.  Item 209 has no cell; items have 1 to a dozen entries."""
+def shape_matrix(per=CHUNK, twice=False):
+    """14 users x 210 items (16 users with `twice`).  User 0 has no cell and user 1 one; users 2 .. 6 have per - 2 .. per + 2 (the
+    staging chunk is `per` entries: CHUNK up to k = 16, fewer where 1024 or k x k LDS doubles hold fewer rows); user 7 has 200 (several
+    chunks); user 8 has a NaN rating among 5 (the mean goes NaN, the factor does not); user 9 only a stored zero; the others 3 .. 6;
+    with `twice` users 14 and 15 have 2 per and 2 per + 1.  Item 209 has no cell; items have 1 to a dozen entries."""
     rng = np.random.default_rng(20261231)
-    nu, ni = 14, 210
-    counts = {0: 0, 1: 1, 2: CHUNK - 2, 3: CHUNK - 1, 4: CHUNK, 5: CHUNK + 1, 6: CHUNK + 2, 7: 200, 8: 5, 9: 0, 10: 3, 11: 4, 12: 5, 13: 6}
+    nu, ni = (16 if twice else 14), 210
+    counts = {0: 0, 1: 1, 2: per - 2, 3: per - 1, 4: per, 5: per + 1, 6: per + 2, 7: 200, 8: 5, 9: 0, 10: 3, 11: 4, 12: 5, 13: 6}
+    if twice:
+        counts.update({14: 2 * per, 15: 2 * per + 1})
     cells = []
     for u, c in counts.items():
         for j in sorted(rng.choice(ni - 1, size=c, replace=False).tolist()):
@@ -293,15 +335,29 @@ def shape_matrix():
     return nu, ni, cells
 
 
-@pytest.mark.parametrize("k", [1, 2, 3, 10, 63, 64])
+# k -> (per, element groups a thread): the borders between k = 10 and k = 63
+ROW_BORDERS = {16: (64, 1), 17: (60, 2), 22: (46, 2), 23: (44, 3), 32: (32, 4), 33: (33, 5), 48: (48, 9)}
+
+
+@pytest.mark.parametrize("k", [1, 2, 3, 10, 63, 64] + sorted(ROW_BORDERS))
 def test_row_kernel_shapes_equal_the_restatement(k):
-    nu, ni, cells = shape_matrix()
+    """k = 1, 2, 3, 10, 63, 64 on the matrix cut around CHUNK; every k of ROW_BORDERS on the matrix cut around that k's own `per`, with
+    rows of 2 per and 2 per + 1 entries as well"""
+    per = CHUNK
+    if k in ROW_BORDERS:
+        per, stage = row_per(k), max(k * k, STAGE_MIN)
+        assert (per, (k * k + ROW_BLOCK - 1) // ROW_BLOCK) == ROW_BORDERS[k]
+        assert k != 32 or (stage == STAGE_MIN and 31 * 31 < STAGE_MIN)     # the last k that stages in STAGE_MIN doubles
+        assert k != 33 or (stage == k * k and stage > STAGE_MIN)           # the first that stages in k x k
+    nu, ni, cells = shape_matrix(per, k in ROW_BORDERS)
     rng = np.random.default_rng(4000 + k)
     P, Q = rng.standard_normal((nu, k)), rng.standard_normal((ni, k))
     b = rng.standard_normal((k, k)) * 0.3
     alpha, mu, gm = b @ b.T + np.eye(k), rng.standard_normal(k) * 0.2, 2.75
     m = ref.BPMF(nu, ni, cells, gm)
-    assert [len(r) for r in m.rows][:10] == [0, 1, CHUNK - 2, CHUNK - 1, CHUNK, CHUNK + 1, CHUNK + 2, 200, 5, 0] and not m.cols[209]
+    assert [len(r) for r in m.rows][:10] == [0, 1, per - 2, per - 1, per, per + 1, per + 2, 200, 5, 0] and not m.cols[209]
+    if k in ROW_BORDERS:
+        assert [len(r) for r in m.rows][14:] == [2 * per, 2 * per + 1]
     h = capi.BPMFInstance(k, nu, ni)
     h.set_ratings([c[0] for c in cells], [c[1] for c in cells], [c[2] for c in cells])
     h.set_global_mean(gm)
@@ -339,37 +395,111 @@ def null_matrix(all_null):
     return nu, ni, cells
 
 
-@pytest.mark.parametrize("all_null", [False, True], ids=["mixed", "all_null"])
-def test_null_factor_rows_and_the_exact_draw_offsets(all_null):
-    k = 2
-    nu, ni, cells = null_matrix(all_null)
+def null_cells(counts, n_other, seed):
+    """a side whose row x has counts[x] entries among n_other partners: (x, partner, value)"""
+    rng = np.random.default_rng(seed)
+    cells = []
+    for x, c in enumerate(counts):
+        cells += [(x, j, float(rng.integers(1, 6))) for j in sorted(rng.choice(n_other, size=c, replace=False).tolist())]
+    return cells
+
+
+def null_side0(counts):
+    return len(counts), 40, null_cells(counts, 40, 20270104)
+
+
+def null_side1(counts):
+    """the same kinds among the ITEMS: 40 users, an item per count"""
+    return 40, len(counts), [(u, j, v) for j, u, v in null_cells(counts, 40, 20270105)]
+
+
+# with alpha = -I a row with fewer entries than k has a Gram matrix of lower rank, so 2 G - I is indefinite and covar has no factor; a
+# dozen well-spread entries make it positive definite.  name -> (k, side, start from a cached gaussian, matrix, flags of the side's rows)
+K3_MIXED = (1, 12, 12, 2, 1, 12, 12, 12, 1, 2)            # five rows draw: 15 draws, an odd number
+NULL_CASES = {
+    "mixed": (2, 0, False, lambda: null_matrix(False), [1, 0, 0, 1, 1, 0, 0, 0, 1, 0]),
+    "all_null": (2, 0, False, lambda: null_matrix(True), [1] * 10),
+    "k2_cached": (2, 0, True, lambda: null_matrix(False), [1, 0, 0, 1, 1, 0, 0, 0, 1, 0]),
+    "k3_mixed": (3, 0, False, lambda: null_side0(K3_MIXED), [int(c < 3) for c in K3_MIXED]),
+    "k3_cached": (3, 0, True, lambda: null_side0(K3_MIXED), [int(c < 3) for c in K3_MIXED]),
+    "k2_side1": (2, 1, False, lambda: null_matrix(False), None),      # the items of the users' matrix: what they are is asserted below
+    "k3_side1": (3, 1, False, lambda: null_side1(K3_MIXED), [int(c < 3) for c in K3_MIXED]),
+    "k3_side1_cached": (3, 1, True, lambda: null_side1(K3_MIXED), [int(c < 3) for c in K3_MIXED]),
+    "last_only": (3, 0, False, lambda: null_side0((12, 12, 12, 12, 12, 1)), [0, 0, 0, 0, 0, 1]),
+    "first_only": (3, 0, False, lambda: null_side0((1, 12, 12, 12, 12, 12)), [1, 0, 0, 0, 0, 0]),
+    "first_only_cached": (3, 0, True, lambda: null_side0((1, 12, 12, 12, 12, 12)), [1, 0, 0, 0, 0, 0]),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def null_case(case):
+    """the inputs of a case and the restatement's pass over them"""
+    k, side, cached, matrix, flags = NULL_CASES[case]
+    nu, ni, cells = matrix()
     rng = np.random.default_rng(20270102)
     P, Q = rng.standard_normal((nu, k)), rng.standard_normal((ni, k)) * 1.5
-    alpha, mu, gm = -np.eye(k), np.array([0.25, -0.5]), 3.0
+    if side == 1 and k == 3:
+        P = P * 1.5                                                      # the partners' rows, as spread as Q is for the users
+    alpha, mu, gm = -np.eye(k), np.array([0.25, -0.5, 0.125][:k]), 3.0
     m = ref.BPMF(nu, ni, cells, gm)
     r = ref.Stream.seeded(4242)
-    start = (r.state, False, 0.0)
+    if cached:
+        r.gaussian()
+        assert r.have
+    start = (r.state, r.have, r.cached if r.have else 0.0)
     Pr, Qr = P.copy(), Q.copy()
-    want_flags, want_draws = m.sample_side(r, 0, Pr, Qr, alpha, mu)
+    want_flags, want_draws = m.sample_side(r, side, Pr, Qr, alpha, mu)
+    return k, side, (nu, ni, cells), (P, Q, alpha, mu, gm), start, (Pr, Qr, want_flags, want_draws, (r.state, r.have, r.cached)), m
+
+
+@pytest.mark.parametrize("case", sorted(NULL_CASES, key=list(NULL_CASES).index))
+def test_null_factor_rows_and_the_exact_draw_offsets(case):
+    all_null = case == "all_null"
+    k, side, (nu, ni, cells), (P, Q, alpha, mu, gm), start, (Pr, Qr, want_flags, want_draws, end), m = null_case(case)
+    own0, own_r, other0, other_r = (P, Pr, Q, Qr) if side == 0 else (Q, Qr, P, Pr)
     # the condition on the input, by the restatement: both kinds at least twice and a null row BEFORE a non-null one -- else the
     # first launch's offsets (every row with entries counted) would be right by accident
     if all_null:
-        assert want_flags == [1] * nu and want_draws == 0 and (r.state, r.have) == start[:2] and same_bits(Pr, P)
-    else:
+        assert want_flags == [1] * nu and want_draws == 0 and end[:2] == start[:2] and same_bits(Pr, P)
+    elif case == "mixed":
         assert want_flags == [1, 0, 0, 1, 1, 0, 0, 0, 1, 0] and want_draws == k * 6
         assert want_flags.count(1) >= 2 and want_flags.count(0) >= 2 and want_flags.index(1) < len(want_flags) - 1 - want_flags[::-1].index(0)
+    lists = m.rows if side == 0 else m.cols
+    slots = [x for x in range(len(lists)) if lists[x]]                   # the rows with entries, in the order of the pass
+    slot_null = [want_flags[x] for x in slots]
+    drawing = slot_null.count(0)
+    if NULL_CASES[case][4] is not None:
+        assert want_flags == NULL_CASES[case][4]
+    assert want_draws == k * drawing and all(want_flags[x] == 0 for x in range(len(lists)) if not lists[x])
+    assert start[1] == NULL_CASES[case][2] and end[1] == (start[1] != (want_draws % 2 == 1))
+    if case in ("k3_mixed", "k3_cached", "k2_side1", "k3_side1", "k3_side1_cached", "k2_cached"):
+        assert slot_null.count(1) >= 2 and drawing >= 2 and slot_null.index(1) < len(slot_null) - 1 - slot_null[::-1].index(0)
+    if case.startswith("k3_"):
+        assert drawing % 2 == 1 and end[1] != start[1]                   # the stream flips between cached and not across the pass
+    if case == "k2_side1":
+        assert len(slots) < ni and drawing == 6                          # items without a cell are no slot
+    if case == "last_only":
+        # nothing runs again, yet the stream must stand k (R - 1) draws on: an odd number, so it ends on a cached value
+        assert slot_null == [0] * (len(slots) - 1) + [1] and want_draws == k * (len(slots) - 1) and end[1]
+        rr = ref.Stream(*start)
+        for _ in range(k * (len(slots) - 1)):
+            rr.gaussian()
+        assert (rr.state, rr.have) == end[:2]
+    if case.startswith("first_only"):
+        assert slot_null == [1] + [0] * (len(slots) - 1)                 # every other slot runs again, one rank lower
     h = capi.BPMFInstance(k, nu, ni)
     h.set_ratings([c[0] for c in cells], [c[1] for c in cells], [c[2] for c in cells])
     h.set_global_mean(gm)
     h.set_model(P, Q)
     h.set_stream(*start)
-    flags, draws = h.sample_side(0, alpha, mu)
-    Pd, Qd = h.model()
+    flags, draws = h.sample_side(side, alpha, mu)
+    got = h.model()
+    own_d, other_d = got[side], got[1 - side]
     assert flags.tolist() == want_flags and draws == want_draws
-    assert same_bits(Pd, Pr) and same_bits(Qd, Q)
-    null_rows = [u for u in range(nu) if want_flags[u]]
-    assert same_bits(Pd[null_rows], P[null_rows])                        # the kept old rows
-    assert same_stream(h.stream(), (r.state, r.have, r.cached))
+    assert same_bits(own_d, own_r) and same_bits(other_d, other0) and same_bits(other_r, other0)
+    null_rows = [x for x in range(len(lists)) if want_flags[x]]
+    assert same_bits(own_d[null_rows], own0[null_rows])                  # the kept old rows
+    assert same_stream(h.stream(), end)
     h.close()
 
 

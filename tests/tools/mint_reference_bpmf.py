@@ -9,9 +9,11 @@ objects, both seeded here (`seed_init` for librec's, `seed_gibbs` for happy.codi
 * `runs`: buildModel() on
     - the 26 x 42 `knn_matrix` of tests/golden/reference_knn.json.gz (read from that file, not stored again) at k in {3, 10};
     - the `handmade` 7 x 6 matrix of mint_reference_rankals.py at k in {1, 2}: a user with no cell, a user whose only cell is a stored
-      zero, an item with no cell, a row of one entry, a negative value.
+      zero, an item with no cell, a row of one entry, a negative value;
+    - the `generated` 24 x 22 matrix (generated() below, stored in the file) at k = 17: 4 to 8 cells a user, a user and an item with no
+      cell, a stored zero; wishart() there reaches SparseVector.inner over 11 and 13 indices.
   buildModel has no per-iteration hook, so the state after iteration t is a run with numIters = t from the same seeds, t = 0 (the drawn
-  P and Q), 1, 2, 3: P, Q and the loss.  predict(u, j) of every cell after the last run.  globalMean is the caller's here (the driver
+  P and Q), 1, 2, 3: P, Q and the loss; every (spec, t) is a process of the pool.  predict(u, j) of every cell after the last run.  globalMean is the caller's here (the driver
   takes it from the contextual matrix, Recommender.java:265): the mean of the non-zero cells, stored in the file.
 * from bytecode, apart: `cholesky` (DenseMatrix.cholesky(), the UPPER factor or null), `cov` (cov() and columnMean()), `gamma`
   (Randoms.gamma(alpha, 2), 50 draws each from a seed), `gaussian` (1 000 Randoms.gaussian(0, 1) from a seed), and `wishart`
@@ -64,7 +66,26 @@ def new_this(ref):
     return vm, this
 
 
-def run_bpmf(spec):
+def generated():
+    """24 users x 22 items for the k = 17 run: 4 to 8 cells a user, user 5 with no cell, item 13 with no cell, one stored zero (the third
+    cell of user 9); both sides longer than k, so that cov() is not singular by construction"""
+    rng = np.random.default_rng(20261218)
+    nu, ni = 24, 22
+    cells = []
+    for u in range(nu):
+        if u == 5:
+            continue
+        c = int(rng.integers(4, 9))
+        for j in sorted(rng.choice([j for j in range(ni) if j != 13], size=c, replace=False).tolist()):
+            cells.append((u, j, float(rng.integers(1, 11)) / 2.0))
+    third9 = next(n for n, c in enumerate(cells) if c[0] == 9) + 2
+    cells[third9] = (9, cells[third9][1], 0.0)
+    return nu, ni, cells
+
+
+def run_to(task):
+    """buildModel() with numIters = t from the spec's seeds: what the record holds of that state"""
+    spec, t = task
     ref, name, nu, ni, cells, k, seed_init, seed_gibbs, store_cells = spec
     from oracle.mint_reference_src import sparse
     nz = [v for _, _, v in cells if v != 0.0]
@@ -72,31 +93,36 @@ def run_bpmf(spec):
     for v in nz:
         gm += v
     gm /= len(nz)
-    rec = {"name": name, "n_users": nu, "n_items": ni, "k": k, "seed_init": seed_init, "seed_gibbs": seed_gibbs, "global_mean": hexd(gm),
-           "iters": []}
-    this = None
-    for t in range(0, ITERS + 1):
-        vm, this = new_this(ref)
-        train = sparse(vm, nu, ni, cells)
-        vm.call(LIBREC, "seed", "(J)V", [seed_init])
-        vm.call(HAPPY, "seed", "(J)V", [seed_gibbs])
-        this.fields.update({"train": train, "P": None, "Q": None, "numFactors": k, "numIters": t, "numUsers": nu, "numItems": ni,
-                            "globalMean": gm, "loss": 0.0, "last_loss": 0.0, "measure": 0.0, "last_measure": 0.0, "lRate": -1.0,
-                            "initLRate": -1.0, "maxLRate": -1.0, "decay": -1.0, "isBoldDriver": False, "earlyStopMeasure": None,
-                            "verbose": False, "isResultsOut": False, "isUserSplitting": False, "isItemSplitting": False,
-                            "algoName": "BPMF", "foldInfo": "", "__enums__": ("Measure",)})
-        this.call("buildModel", [])
-        if t == 0:
-            rec["P0"], rec["Q0"] = flat(this.fields["P"]), flat(this.fields["Q"])
-        else:
-            rec["iters"].append({"P": flat(this.fields["P"]), "Q": flat(this.fields["Q"]), "loss": hexd(this.fields["loss"])})
-        if t == 1:
-            rec["row_count"] = [int(vm.call(SV, "getCount", "()I", [vm.call(SM, "row", "(I)L%s;" % SV, [train, u])])) for u in range(nu)]
-            rec["col_count"] = [int(vm.call(SV, "getCount", "()I", [vm.call(SM, "column", "(I)L%s;" % SV, [train, j])])) for j in range(ni)]
-    rec["predict"] = [[hexd(this.call("predict", [u, j])) for j in range(ni)] for u in range(nu)]
+    vm, this = new_this(ref)
+    train = sparse(vm, nu, ni, cells)
+    vm.call(LIBREC, "seed", "(J)V", [seed_init])
+    vm.call(HAPPY, "seed", "(J)V", [seed_gibbs])
+    this.fields.update({"train": train, "P": None, "Q": None, "numFactors": k, "numIters": t, "numUsers": nu, "numItems": ni,
+                        "globalMean": gm, "loss": 0.0, "last_loss": 0.0, "measure": 0.0, "last_measure": 0.0, "lRate": -1.0,
+                        "initLRate": -1.0, "maxLRate": -1.0, "decay": -1.0, "isBoldDriver": False, "earlyStopMeasure": None,
+                        "verbose": False, "isResultsOut": False, "isUserSplitting": False, "isItemSplitting": False,
+                        "algoName": "BPMF", "foldInfo": "", "__enums__": ("Measure",)})
+    this.call("buildModel", [])
+    out = {"global_mean": hexd(gm), "P": flat(this.fields["P"]), "Q": flat(this.fields["Q"]), "loss": hexd(this.fields["loss"])}
+    if t == 1:
+        out["row_count"] = [int(vm.call(SV, "getCount", "()I", [vm.call(SM, "row", "(I)L%s;" % SV, [train, u])])) for u in range(nu)]
+        out["col_count"] = [int(vm.call(SV, "getCount", "()I", [vm.call(SM, "column", "(I)L%s;" % SV, [train, j])])) for j in range(ni)]
+    if t == ITERS:
+        out["predict"] = [[hexd(this.call("predict", [u, j])) for j in range(ni)] for u in range(nu)]
+    print(name, "k =", k, "numIters =", t, flush=True)
+    return out
+
+
+def assemble(spec, parts):
+    """the record of one spec from its runs with numIters = 0 .. ITERS"""
+    ref, name, nu, ni, cells, k, seed_init, seed_gibbs, store_cells = spec
+    rec = {"name": name, "n_users": nu, "n_items": ni, "k": k, "seed_init": seed_init, "seed_gibbs": seed_gibbs,
+           "global_mean": parts[0]["global_mean"], "iters": [{"P": p["P"], "Q": p["Q"], "loss": p["loss"]} for p in parts[1:]]}
+    rec["P0"], rec["Q0"] = parts[0]["P"], parts[0]["Q"]
+    rec["row_count"], rec["col_count"] = parts[1]["row_count"], parts[1]["col_count"]
+    rec["predict"] = parts[ITERS]["predict"]
     if store_cells:
         rec["cells"] = [[u, j, hexd(v)] for u, j, v in cells]
-    print(name, "k =", k, flush=True)
     return rec
 
 
@@ -159,8 +185,13 @@ def main():
              (ref, "knn_matrix", km["n_users"], km["n_items"], kcells, 10, 20261212, 20261213, False),
              (ref, "handmade", nu, ni, hcells, 1, 20261214, 20261215, True),
              (ref, "handmade", nu, ni, hcells, 2, 20261216, 20261217, True)]
-    with multiprocessing.Pool(min(4, os.cpu_count() or 1)) as pool:
-        runs = pool.map(run_bpmf, specs, chunksize=1)
+    gu, gi, gcells = generated()
+    specs.append((ref, "generated", gu, gi, gcells, 17, 20261219, 20261220, True))
+    # every (spec, numIters) is a run of its own: the dearest first (a row costs k^3 in the interpreter)
+    tasks = sorted(((s, t) for s in range(len(specs)) for t in range(ITERS + 1)), key=lambda st: -specs[st[0]][5] ** 3 * specs[st[0]][2] * st[1])
+    with multiprocessing.Pool(min(len(tasks), os.cpu_count() or 1)) as pool:
+        parts = dict(zip(tasks, pool.map(run_to, [(specs[s], t) for s, t in tasks], chunksize=1)))
+    runs = [assemble(spec, [parts[(s, t)] for t in range(ITERS + 1)]) for s, spec in enumerate(specs)]
     out = {"source": "BPMF / IterativeRecommender / Recommender from source, librec and happy.coding from the jars' bytecode "
                      "(tests/tools/mint_reference_bpmf.py)", "runs": runs}
     out.update(run_small(ref))
